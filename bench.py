@@ -28,7 +28,8 @@ N > 1 (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
            ONE RCCL all-gather of the packed per-shard top-k over xGMI, host-side merge) — BASELINE.json configs[4] layout.
            The C5 shape itself: `--mode shard --quant 3 --ef 256 --n 40000000` on 8 GPUs.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `--dump-outputs DIR` also writes the answers of the last timed step to DIR/*.npy (dump_outputs): the
+inputs are generated from fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -82,6 +83,8 @@ def parse():
     ap.add_argument("--no-op-diverse", action="store_true", help="skip op.diverse (a second 10 M build under COLTT_HNSW_DIVERSE, the opt-in NON-reference neighbour selection)")
     ap.add_argument("--no-reserve", dest="reserve", action="store_false", help="let the index arrays grow by halves during the build instead of reserving the known size")
     ap.add_argument("--shard-leg-n", type=int, default=0, help="vectors in the whole sharded collection of the secondary.shard leg (0 = --n)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the answers of the last timed step (ids, scores, counts) as DIR/<name>.npy (see dump_outputs)")
     # ranks started by self_launch() get their arguments through the environment: torch.distributed.run's own parser would read
     # `--n 20000` as an abbreviation of one of ITS options (--nnodes, --nproc-per-node, ...) even behind the script path
     if len(sys.argv) == 1 and os.environ.get("COLTT_BENCH_ARGS"):
@@ -1068,6 +1071,33 @@ def timed(torch, dist, world, cdev, steps, warmup, step, drain=None):
     return dt
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0xD0D0
+
+
+def dump_outputs(dirname, ids, scores, counts, prefix="", max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: the answers the timed path handed its caller in its last step, one row per query, as `dirname/<prefix><name>.npy`:
+    ids.npy (float64: ids < 2^53 are exact), scores.npy and counts.npy (float32), query_index.npy (float64: the query row each output row
+    belongs to).  Slots past a query's count are not written by the search and hold no answer: they are stored as id -1, score +inf.  When
+    the rows exceed `max_bytes`, a fixed seeded sample of query rows (same sample for the same shape) is written instead."""
+    ids, scores, counts = np.asarray(ids), np.asarray(scores, np.float32), np.asarray(counts).astype(np.int64)
+    nq, k = scores.shape
+    rows = np.arange(nq)
+    per_row = k * 8 + k * 4 + 4 + 8
+    fit = (max_bytes - 4 * 256) // per_row     # (four .npy headers)
+    if nq > fit:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(nq, max(1, fit), replace=False))
+    empty = np.arange(k)[None, :] >= counts[rows, None]
+    out = {"ids": np.where(empty, -1.0, ids[rows].astype(np.float64)),
+           "scores": np.where(empty, np.float32(np.inf), scores[rows]).astype(np.float32),
+           "counts": counts[rows].astype(np.float32),
+           "query_index": rows.astype(np.float64)}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, f"{prefix}{name}.npy"), a)
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- the ONE line the driver parses
 LINE_TARGET, LINE_HARD = 4096, 8000      # bytes of the final stdout line: target, and the bound it is trimmed to
 
@@ -1281,6 +1311,9 @@ def main():
                 kernel_ms.append(h.last_kernel_ms())  # hipEvent pair recorded on the library's search stream
                 for kk in stats: stats[kk] += st[kk]
     dt = timed(torch, dist, world, cdev, args.steps, args.warmup, step, drain=gstep.drain if shard else None)
+    if args.dump_outputs:   # now: the recall / ef / host-boundary calls below search into `out` again
+        last = gout[0] if shard else (out.ids.cpu().numpy(), out.sc.cpu().numpy(), out.cnt.cpu().numpy())
+        dump_outputs(args.dump_outputs, *last, prefix=f"rank{rank}_" if world > 1 else "", max_bytes=DUMP_MAX_BYTES // world)
     if shard:
         shard_info["pipeline_ms_per_batch"] = pipeline_timing(gstep.timing())
     if shard and rank == 0 and shard_info["n_total"] <= 200_000:

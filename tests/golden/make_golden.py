@@ -1,12 +1,14 @@
 """Generates tests/golden/*.npz from the CPU oracle (and pins the oracle's distance kernels against the
-reference's own avx.cpp / sse.cpp when oracle/_ref is available).  Inputs are regenerated from seeds by
-orc_fill_normal (integer-exact), so the fixtures hold only seeds' outputs.
+reference's own avx.cpp / sse.cpp when oracle/_ref is available; ref_simd.npz keeps those kernels' outputs,
+and is only rewritten where oracle/_ref is built).  Inputs are regenerated from seeds by orc_fill_normal
+(integer-exact) or numpy's seeded Generator, so the fixtures hold only seeds' outputs.
 
     python tests/golden/make_golden.py
 """
 import ctypes as C
 import os
 import sys
+import zlib
 
 import numpy as np
 
@@ -100,6 +102,78 @@ def hnsw():
     np.savez_compressed(os.path.join(HERE, "hnsw.npz"), **out)
 
 
+def ref_dist_pairs():
+    """the (a, b) pairs of tests/test_oracle.py::test_distance_orders_equal_reference_sources"""
+    rng = np.random.default_rng(1); pairs = []
+    for _ in range(1500):
+        d = int(rng.integers(1, 800))
+        pairs.append((rng.standard_normal(d).astype(np.float32), rng.standard_normal(d).astype(np.float32)))
+    return pairs
+
+
+def ref_manhattan_pairs():
+    """the (a, b) pairs of tests/test_oracle.py::test_manhattan_equals_reference_sources_and_native_order, incl. magnitudes where the
+    reference's vector part (sqrt of the rounded square) and |d| differ"""
+    rng = np.random.default_rng(11); pairs = []
+    for t in range(600):
+        d = int(rng.integers(1, 300))
+        a = rng.standard_normal(d).astype(np.float32); b = rng.standard_normal(d).astype(np.float32)
+        if t % 3 == 1: a *= np.float32(1e-25); b *= np.float32(1e-25)       # d * d underflows: sqrt(d * d) != |d|
+        if t % 3 == 2: a *= np.float32(1e25)                                 # d * d overflows to +Inf in the vector part
+        pairs.append((a, b))
+    return pairs
+
+
+def pairs_crc(pairs):
+    """crc32 of every input byte: a changed input stream fails as such, not as a kernel mismatch"""
+    c = 0
+    for a, b in pairs:
+        c = zlib.crc32(b.tobytes(), zlib.crc32(a.tobytes(), c))
+    return c
+
+
+def ref_dist_bits(fn, pairs):
+    """[pair, order (AVX, SSE), (l2sq, dot, norm product)] score bits; fn(order, a, b) -> (l2sq, dot, norm product)"""
+    return np.array([[[np.float32(v).view(np.uint32) for v in fn(order, a, b)] for order in (O.ORDER_AVX, O.ORDER_SSE)] for a, b in pairs], np.uint32)
+
+
+def oracle_dist(order, a, b):
+    p = O.cosine_parts(a, b, order)
+    return O.l2sq(a, b, order), p[0], np.float32(p[1] * p[2])
+
+
+def ref_dist(r):
+    """the same three numbers from the reference's own avx.cpp / sse.cpp (oracle/_ref)"""
+    def fn(order, a, b):
+        res = C.c_float(); dot = C.c_float(); ns = C.c_float()
+        r.ref_l2sq(order, C.c_size_t(a.size), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.byref(res))
+        r.ref_cos_dot_norm(order, C.c_size_t(a.size), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.byref(dot), C.byref(ns))
+        return res.value, dot.value, ns.value
+    return fn
+
+
+def ref_manhattan_bits(r, pairs):
+    """[pair, order (AVX, SSE)] Manhattan bits from the reference's own avx.cpp / sse.cpp"""
+    out = np.zeros((len(pairs), 2), np.uint32)
+    for i, (a, b) in enumerate(pairs):
+        for j, order in enumerate((O.ORDER_AVX, O.ORDER_SSE)):
+            res = C.c_float()
+            r.ref_manhattan(order, C.c_size_t(a.size), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.byref(res))
+            out[i, j] = np.float32(res.value).view(np.uint32)
+    return out
+
+
+def ref_simd():
+    """tests/golden/ref_simd.npz: what the reference's own avx.cpp / sse.cpp return on the CPU suite's inputs, so that the suite pins the
+    oracle against them on a machine without the reference"""
+    r = O.ref()
+    if r is None:
+        print("oracle/_ref not built: ref_simd.npz kept as it is"); return
+    dp, mp = ref_dist_pairs(), ref_manhattan_pairs()
+    np.savez_compressed(os.path.join(HERE, "ref_simd.npz"), dist_crc=np.array([pairs_crc(dp)], np.uint64), dist=ref_dist_bits(ref_dist(r), dp),
+                        manhattan_crc=np.array([pairs_crc(mp)], np.uint64), manhattan=ref_manhattan_bits(r, mp))
+
+
 def pin_against_reference():
     r = O.ref()
     if r is None:
@@ -122,6 +196,6 @@ def pin_against_reference():
 
 if __name__ == "__main__":
     pin_against_reference()
-    kernels(); flat(); hnsw()
+    kernels(); flat(); hnsw(); ref_simd()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"): print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -6,11 +6,13 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+from util import bits  # noqa: E402
 
 REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "config", "roofline", "cpu_baseline"]
@@ -182,3 +184,57 @@ def test_final_line_of_round_6_record_fits_and_carries_the_new_legs():
     assert op["diverse"]["reference_behaviour"] is False and op["diverse"]["recall_at_10"] >= 0.98 and op["diverse"]["ef"] < op["ef"]
     assert c["pq"]["eq_chain"] is True and c["pq"]["ms"] < c["pq"]["segment_chain_ms"] and 0 < c["pq"]["search_frac"] < c["pq"]["frac"] < 1
     assert c["roofline"]["frac"] == pytest.approx(res["roofline"]["achieved"] / res["roofline"]["peak"], rel=1e-4)
+
+
+def test_dump_outputs_writes_the_answers_as_float_arrays(tmp_path):
+    """--dump-outputs: ids as float64, scores / counts as float32, one row per query; slots past a query's count (never written by the
+    search) are stored as id -1, score +inf so that two runs compare equal"""
+    rng = np.random.default_rng(3)
+    ids = rng.integers(0, 10_000_000, (50, 10), dtype=np.int64)
+    sc = rng.standard_normal((50, 10)).astype(np.float32)
+    cnt = np.full(50, 10, np.int32); cnt[7] = 4; cnt[8] = 0
+    bench.dump_outputs(str(tmp_path / "d"), ids, sc, cnt)
+    got = {n: np.load(tmp_path / "d" / f"{n}.npy") for n in ("ids", "scores", "counts", "query_index")}
+    assert got["ids"].dtype == np.float64 and got["scores"].dtype == np.float32 and got["counts"].dtype == np.float32
+    assert got["query_index"].dtype == np.float64 and np.array_equal(got["query_index"], np.arange(50))
+    full = cnt == 10
+    assert np.array_equal(got["ids"][full], ids[full].astype(np.float64)) and np.array_equal(bits(got["scores"][full]), bits(sc[full]))
+    assert np.array_equal(got["ids"][7], np.r_[ids[7, :4], [-1] * 6]) and np.isposinf(got["scores"][7, 4:]).all()
+    assert (got["ids"][8] == -1).all() and np.array_equal(got["counts"], cnt.astype(np.float32))
+
+
+def test_dump_outputs_stays_within_its_budget_with_a_fixed_sample(tmp_path):
+    """above the budget a seeded sample of query rows is written — the same rows every time — and the files stay under the budget"""
+    ids = np.arange(40_000 * 10, dtype=np.uint64).reshape(40_000, 10)
+    sc = np.arange(40_000 * 10, dtype=np.float32).reshape(40_000, 10)
+    cnt = np.full(40_000, 10, np.uint32)
+    budget = 1 << 20
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), ids, sc, cnt, max_bytes=budget)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= budget
+    qi = np.load(tmp_path / "a" / "query_index.npy")
+    assert 0 < len(qi) < 40_000 and np.all(np.diff(qi) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "ids.npy"), ids[qi.astype(np.int64)].astype(np.float64))
+    for n in ("ids", "scores", "counts", "query_index"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")), n
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_two_identical_runs_are_identical(gpu, tmp_path):
+    """`bench.py --dump-outputs DIR` twice with the same arguments: the same seeded inputs give the same answers of the last timed step,
+    and --steps is the number of timed steps the line reports"""
+    args = ["--n", "20000", "--dim", "64", "--queries", "512", "--legs", "none", "--no-cpu-baseline", "--steps", "3", "--warmup", "1",
+            "--build-batch", "1024"]
+    lines = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *args, "--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines.append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]))
+    assert lines[0]["steps"] == 3 and lines[0]["warmup"] == 1
+    for n in ("ids", "scores", "counts", "query_index"):
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    ids, sc, cnt = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("ids", "scores", "counts"))
+    assert ids.shape == sc.shape == (512, 10) and (cnt == 10).all()
+    assert ((ids >= 0) & (ids < 20000)).all() and (np.diff(sc, axis=1) >= 0).all()

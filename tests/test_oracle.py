@@ -17,43 +17,37 @@ import make_golden as MG  # noqa: E402
 
 
 def test_distance_orders_equal_reference_sources():
+    """the oracle's AVX / SSE orders against the reference's own avx.cpp / sse.cpp: their outputs are stored in golden/ref_simd.npz
+    (make_golden.py) and, where oracle/_ref is built, also taken live"""
+    g = np.load(os.path.join(GOLD, "ref_simd.npz"))
+    pairs = MG.ref_dist_pairs()
+    assert MG.pairs_crc(pairs) == int(g["dist_crc"][0]), "the seeded inputs are not the ones ref_simd.npz was made from"
+    got = MG.ref_dist_bits(MG.oracle_dist, pairs)
+    bad = np.argwhere(got != g["dist"])
+    assert len(bad) == 0, bad[:10]
     r = O.ref()
-    if r is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this box)")
-    rng = np.random.default_rng(1)
-    for _ in range(1500):
-        d = int(rng.integers(1, 800))
-        a = rng.standard_normal(d).astype(np.float32); b = rng.standard_normal(d).astype(np.float32)
-        for order in (O.ORDER_AVX, O.ORDER_SSE):
-            res = C.c_float(); dot = C.c_float(); ns = C.c_float()
-            r.ref_l2sq(order, C.c_size_t(d), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.byref(res))
-            r.ref_cos_dot_norm(order, C.c_size_t(d), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.byref(dot), C.byref(ns))
-            p = O.cosine_parts(a, b, order)
-            assert np.float32(res.value).view(np.uint32) == O.l2sq(a, b, order).view(np.uint32)
-            assert np.float32(dot.value).view(np.uint32) == p[0].view(np.uint32)
-            assert np.float32(ns.value).view(np.uint32) == np.float32(p[1] * p[2]).view(np.uint32)
+    if r is not None:
+        assert np.array_equal(MG.ref_dist_bits(MG.ref_dist(r), pairs), g["dist"])
 
 
 def test_manhattan_equals_reference_sources_and_native_order():
     """Manhattan.Distance (pkg/distance/space.go:77-79): the oracle against the reference's own avx.cpp / sse.cpp (vector part: sqrt of the
-    rounded square, NOT |d|; scalar tail: abs) incl. magnitudes where the two differ, and the native order against a numpy loop."""
-    r = O.ref()
-    rng = np.random.default_rng(11)
-    for t in range(600):
-        d = int(rng.integers(1, 300))
-        a = rng.standard_normal(d).astype(np.float32); b = rng.standard_normal(d).astype(np.float32)
-        if t % 3 == 1: a *= np.float32(1e-25); b *= np.float32(1e-25)       # d * d underflows: sqrt(d * d) != |d|
-        if t % 3 == 2: a *= np.float32(1e25)                                 # d * d overflows to +Inf in the vector part
+    rounded square, NOT |d|; scalar tail: abs) incl. magnitudes where the two differ — stored in golden/ref_simd.npz and, where oracle/_ref
+    is built, also taken live — and the native order against a numpy loop."""
+    g = np.load(os.path.join(GOLD, "ref_simd.npz"))
+    pairs = MG.ref_manhattan_pairs()
+    assert MG.pairs_crc(pairs) == int(g["manhattan_crc"][0]), "the seeded inputs are not the ones ref_simd.npz was made from"
+    for t, (a, b) in enumerate(pairs):
         nat = np.float32(0)
         with np.errstate(over="ignore"):
-            for i in range(d):
+            for i in range(a.size):
                 nat = np.float32(nat + np.float32(abs(np.float32(a[i] - b[i]))))
         assert bits(O.manhattan(a, b, O.ORDER_NATIVE)) == bits(nat)
-        if r is not None:
-            for order in (O.ORDER_AVX, O.ORDER_SSE):
-                res = C.c_float()
-                r.ref_manhattan(order, C.c_size_t(d), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.byref(res))
-                assert np.float32(res.value).view(np.uint32) == O.manhattan(a, b, order).view(np.uint32), (t, d, order)
+        for j, order in enumerate((O.ORDER_AVX, O.ORDER_SSE)):
+            assert O.manhattan(a, b, order).view(np.uint32) == g["manhattan"][t, j], (t, a.size, order)
+    r = O.ref()
+    if r is not None:
+        assert np.array_equal(MG.ref_manhattan_bits(r, pairs), g["manhattan"])
     x = np.array([3e-30] * 8 + [3e-30], np.float32); z = np.zeros(9, np.float32)
     assert O.manhattan(x, z, O.ORDER_AVX) == np.float32(3e-30) and O.manhattan(x, z, O.ORDER_NATIVE) > np.float32(2.6e-29)   # the vector lanes lost their 8 terms
 
