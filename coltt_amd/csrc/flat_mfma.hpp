@@ -302,16 +302,6 @@ template <bool NT> __device__ __forceinline__ void m2_dma16(const void* g, uint3
   if constexpr (NT) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off nt" : : "v"(g), "s"(lds_base) : "memory");
   else asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(g), "s"(lds_base) : "memory");
 }
-#ifndef COLTT_M2_NT
-#define COLTT_M2_NT 0
-#endif
-constexpr bool M2_A_NT = COLTT_M2_NT != 0;   // streamed-once rows: non-temporal hint on the row DMA (measurement knob)
-#ifndef COLTT_M2_ISSUE
-#define COLTT_M2_ISSUE 0
-#endif
-// where a wave issues its DMA pieces inside a K step: 0 all right after the barrier; 1 waves 4-7 (the SIMD partners of
-// waves 0-3) issue theirs between the two MFMA groups instead; 2 every wave spreads its pieces between MFMA groups
-constexpr int M2_ISSUE = COLTT_M2_ISSUE;
 __device__ __forceinline__ void m2_dma4(const void* g, uint32_t lds_base) {
   lds_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_base);
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" : : "v"(g), "s"(lds_base) : "memory");
@@ -650,11 +640,11 @@ __global__ __launch_bounds__(M2_NT, 2) void flat_mfma3_kernel(
       const uint32_t slot = lds0 + (ld_g % NSA) * G::A_STAGE + (uint32_t)(lw * G::NA_I * 1024);
       if constexpr (GATHER) {
 #pragma unroll
-        for (int i = 0; i < G::NA_I; i++) m2_dma16<M2_A_NT || AF32>(gbase[i] + (size_t)ld_ks * G::A_ROWB, slot + (uint32_t)(i * 1024));
+        for (int i = 0; i < G::NA_I; i++) m2_dma16<AF32>(gbase[i] + (size_t)ld_ks * G::A_ROWB, slot + (uint32_t)(i * 1024));
       } else {
         const uint8_t* sb = rows + (row0 + (uint64_t)(lw * G::NA_I * A_RPI)) * stride + (size_t)ld_ks * G::A_ROWB;
 #pragma unroll
-        for (int i = 0; i < G::NA_I; i++) m3_dma16s<M2_A_NT || AF32>((AF32 && (i & 1)) ? voff_odd : voff, sb + (size_t)i * A_RPI * stride, slot + (uint32_t)(i * 1024));
+        for (int i = 0; i < G::NA_I; i++) m3_dma16s<AF32>((AF32 && (i & 1)) ? voff_odd : voff, sb + (size_t)i * A_RPI * stride, slot + (uint32_t)(i * 1024));
       }
     } else {
       const uint32_t slot = lds0 + G::A_BYTES + (ld_g % NSB) * G::B_STAGE + (uint32_t)(lw * G::NB_I * 1024);
@@ -733,12 +723,7 @@ __global__ __launch_bounds__(M2_NT, 2) void flat_mfma3_kernel(
           } else a[tm] = *reinterpret_cast<const half8*>(Ab + tm * 32 * 64 + fa[kk][0]);
         }
 #pragma unroll
-        for (int tn = 0; tn < TN; tn++) {
-#ifdef COLTT_M3_FAKE_FEWER_READS   // ablation only (WRONG answers): a third fewer fragment reads per step, same MFMA count — what a 128 x 128 wave tile would save
-          if (tn & 1) { b[tn] = b[tn - 1]; continue; }
-#endif
-          b[tn] = *reinterpret_cast<const half8*>(Bb + tn * 32 * 64 + fb[kk]);
-        }
+        for (int tn = 0; tn < TN; tn++) b[tn] = *reinterpret_cast<const half8*>(Bb + tn * 32 * 64 + fb[kk]);
 #pragma unroll
         for (int tm = 0; tm < TM; tm++)
 #pragma unroll

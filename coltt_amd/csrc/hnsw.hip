@@ -683,8 +683,8 @@ bool wants_visg(uint32_t ef) {
 }
 
 // Which level-0 walk serves the HBM-visited searches.  COLTT_WALK2=off: hnsw_dev.hpp:search_level (the round-2 kernel);
-// COLTT_WALK2=<n>: hnsw_walk2.hpp with OPT = n & 7 (1 Bloom, 2 delta result set, 4 adjacency-carried norms), n & 8 = the deep
-// profile (one wave per SIMD, whole 2-byte row in flight).  Measurement and test knob, read at every call.
+// COLTT_WALK2=<n>: hnsw_walk2.hpp with OPT = n (1 Bloom, 2 delta result set, 4 adjacency-carried norms); the library carries 6 and 7.
+// Measurement and test knob, read at every call.
 #ifndef COLTT_WALK2_DEFAULT
 #define COLTT_WALK2_DEFAULT 7
 #endif
@@ -695,7 +695,7 @@ int walk2_policy() { const int v = policy().walk2; return v == 7 ? COLTT_WALK2_D
 // search_level (which re-seeds the table from the result set) — never seen on the benchmark collections.
 // 10 M x 768 f32, 10 000 queries, ms per launch (profiles/r03_walk_lds_f32_10m.json): ef 128 off 22.39, 2 22.25, 4 21.19, 6 21.28;
 // ef 64 off 11.80, 2 11.77, 4 11.10, 6 11.25 — the norms riding with the adjacency rows are the gain; the delta set costs a little
-// when the whole result set is two 64-entry chunks.  The default build carries 4 (2 and 6: -DCOLTT_WALK_EXPERIMENTS).
+// when the whole result set is two 64-entry chunks.  The library carries 4.
 #ifndef COLTT_WALK2_LDS_DEFAULT
 #define COLTT_WALK2_LDS_DEFAULT 4
 #endif
@@ -774,8 +774,7 @@ bool rows_nt(const Hnsw* x) {
   return on;
 }
 
-// hnsw_walk2.hpp kernels.  The default build carries the shipped variant (and its Bloom-less twin for geometries whose LDS
-// has no room for the filter); -DCOLTT_WALK_EXPERIMENTS adds every OPT x profile combination for A/B runs (tools/walk_sweep.py).
+// hnsw_walk2.hpp kernels: the shipped variant (and its Bloom-less twin for geometries whose LDS has no room for the filter).
 template <int METRIC, int QUANT>
 int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
                    uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
@@ -786,10 +785,6 @@ int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32
 #define COLTT_W2(V, PROF, OPT) case V: kern = hnsw_search2_kernel<METRIC, QUANT, PROF, OPT>; break;
   if (sg.w2_lds) {
     switch (sg.w2) {
-#ifdef COLTT_WALK_EXPERIMENTS
-      case 2: kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 2, VIS_LDS>; break;
-      case 6: kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 6, VIS_LDS>; break;
-#endif
       case 4:
         kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 4, VIS_LDS>;
         if constexpr (QUANT != Q_F8) {
@@ -800,17 +795,6 @@ int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32
       default: break;
     }
   } else
-#ifdef COLTT_WALK_EXPERIMENTS
-  if constexpr (METRIC == M_COS && QUANT != Q_F8) {
-    switch (sg.w2) {
-      COLTT_W2(0, PROF_SEARCH_HBM, 0) COLTT_W2(1, PROF_SEARCH_HBM, 1) COLTT_W2(2, PROF_SEARCH_HBM, 2) COLTT_W2(3, PROF_SEARCH_HBM, 3)
-      COLTT_W2(4, PROF_SEARCH_HBM, 4) COLTT_W2(5, PROF_SEARCH_HBM, 5) COLTT_W2(6, PROF_SEARCH_HBM, 6) COLTT_W2(7, PROF_SEARCH_HBM, 7)
-      COLTT_W2(8, PROF_SEARCH_HBM_DEEP, 0) COLTT_W2(9, PROF_SEARCH_HBM_DEEP, 1) COLTT_W2(10, PROF_SEARCH_HBM_DEEP, 2) COLTT_W2(11, PROF_SEARCH_HBM_DEEP, 3)
-      COLTT_W2(12, PROF_SEARCH_HBM_DEEP, 4) COLTT_W2(13, PROF_SEARCH_HBM_DEEP, 5) COLTT_W2(14, PROF_SEARCH_HBM_DEEP, 6) COLTT_W2(15, PROF_SEARCH_HBM_DEEP, 7)
-      default: break;
-    }
-  } else
-#endif
   {
     switch (sg.w2) {
       COLTT_W2(6, PROF_SEARCH_HBM, 6) COLTT_W2(7, PROF_SEARCH_HBM, 7)

@@ -314,13 +314,10 @@ __device__ __forceinline__ void greedy_level_lat(const GraphView& g, WaveCtx& w,
 // chosen (search_level2: CHUNK_ADJ); the runner-up's row is requested at pop time.
 template <int METRIC, int QUANT, int TP> struct LatEval {
   static constexpr bool CHUNK_ADJ = true;
-  static constexpr bool SPEC = false;
   static constexpr bool RADJ = true;    // the runner-up's adjacency row is requested at pop time (the chunk's rows come along with its vectors)
   static constexpr bool ROWPF = false;
   static constexpr bool EARLY = false;
   static constexpr bool BOUNDED = false;
-  static constexpr bool SPLIT = false;
-  static constexpr bool SETCACHE = false;
   LatShared* xs; uint8_t* stage;
   __device__ __forceinline__ uint32_t chunk_adj(int idx, int p) const { return xs->adjn[idx][p]; }
   __device__ __forceinline__ void prefetch(uint32_t, bool, int) const {}

@@ -94,56 +94,23 @@ template <int LS = 0, int NP = 0, bool NBR = false> struct AdcEval {
   }
   u32x4e raw[NR];                              // this lane's half of the code row requested by prefetch() / prefetch_at() for the pair's neighbour
   static constexpr bool CHUNK_ADJ = false;
-  // hnsw_walk2.hpp SPEC: visited bytes + code rows of the predicted next candidate's (the runner-up's) neighbours requested one expansion ahead.
-  // Exact (tests + 246 randomised rounds with it on), but measured SLOWER — an A/B knob (-DCOLTT_PQ_SPEC=1), off in the shipped library
-  // (profiles/r05m_pq_spec_ab.md)
-#ifndef COLTT_PQ_SPEC
-#define COLTT_PQ_SPEC 0
-#endif
-  static constexpr bool SPEC = COLTT_PQ_SPEC != 0 && !NBR;
-  // hnsw_walk2.hpp RADJ: the runner-up's adjacency row requested at pop time (it is the next candidate unless this expansion admits a nearer
-  // vertex).  On its own, without the speculation above: 1 % slower (profiles/r05s_pq_ab.md) — the exact prefetch at the end of the expansion already
-  // flies under the admission and the next pop.
-  // Round 6 tried the same over the neighbourhood blocks (-DCOLTT_PQ_RADJ=1: the runner-up's adjacency row AND its 2 KiB block of code rows requested at pop
-  // time into a second set of row registers, taken over when the runner-up is indeed the next candidate): 2.6 % SLOWER in throughput (344.4 against
-  // 353.5 k queries/s on one box, profiles/r06d_pq_radj_ab.md) and no faster for one query alone — 32 more VGPRs and 2 KiB of wasted fetch per misprediction
-  // against a prefetch that the admission, the eviction and the next pop already cover.  Off in the shipped library.
-#ifndef COLTT_PQ_RADJ
-#define COLTT_PQ_RADJ 0
-#endif
-  static constexpr bool RADJ = SPEC || (NBR && COLTT_PQ_RADJ != 0);
-  // A/B knob: the walk keeps the head / tail windows of its result set's main array in registers (hnsw_walk2.hpp: SETCACHE) — three LDS round trips
-  // fewer per expansion, exact (154 GPU tests + 460 randomised rounds with it on), and NOT faster: 403.1 against 408.9 k queries/s (call I; separate
-  // processes on one box differ by +-5 % on identical code, so "no gain" is all that can be said).  Off.
-#ifndef COLTT_PQ_SETCACHE
-#define COLTT_PQ_SETCACHE 0
-#endif
-  static constexpr bool SETCACHE = COLTT_PQ_SETCACHE != 0;
-  static constexpr bool SPLIT = false;
-  static constexpr bool BOUNDED = true;   // hnsw_walk2.hpp: once the set is full, a neighbour whose table distance is not below lowerBound is neither marked nor counted,
-                                          // and the result set itself answers "visited?" (no byte-map probe, no mark)
+  // tried: visited bytes + code rows of the runner-up's neighbours one expansion ahead — measured slower, profiles/r05m_pq_spec_ab.md
+  // tried: the runner-up's adjacency row + neighbourhood block requested at pop time (RADJ) — measured slower, profiles/r06d_pq_radj_ab.md
+  static constexpr bool RADJ = false;
+  static constexpr bool BOUNDED = true;   // hnsw_walk2.hpp: once the set is full, a neighbour whose table distance is not below lowerBound is neither marked nor counted
   static constexpr bool ROWPF = NBR;   // per-neighbour inputs addressed by (candidate, position): requested with the candidate's adjacency row
   static constexpr bool EARLY = NBR;   // the distances of all listed neighbours are computed under the visited probe (early())
   __device__ __forceinline__ uint32_t chunk_adj(int, int) const { return NBR_NONE; }
-#ifndef COLTT_PQ_NT   // A/B knob: non-temporal hint on the code rows / neighbourhood blocks — measured SLOWER (475.6 -> 440.0 k queries/s at ef 1 344, GPU call AG: hub vertices' blocks are re-read by other traversals out of L2 / MALL), off
-#define COLTT_PQ_NT 0
-#endif
-  static __device__ __forceinline__ u32x4e pq_ld(const u32x4e* p) {
-#if COLTT_PQ_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-  }
+  // tried: the non-temporal hint on the code rows / neighbourhood blocks — measured slower, profiles/r06ag_nt_rows_ab.md
   __device__ __forceinline__ void load_from(const uint8_t* row, u32x4e (&r)[NR]) const {
     const u32x4e* p = reinterpret_cast<const u32x4e*>(row) + first_piece();
     if constexpr (NP != 0 && NP % 2 == 0) {
 #pragma unroll
-      for (int i = 0; i < NR; i++) r[i] = pq_ld(p + i);
+      for (int i = 0; i < NR; i++) r[i] = p[i];
     } else {
       const int cnt = my_pieces();
 #pragma unroll
-      for (int i = 0; i < NR; i++) if (i < cnt) r[i] = pq_ld(p + i);
+      for (int i = 0; i < NR; i++) if (i < cnt) r[i] = p[i];
     }
   }
   __device__ __forceinline__ void load(uint32_t slot, u32x4e (&r)[NR]) const { load_from(codes + (size_t)slot * row_bytes, r); }
@@ -152,9 +119,7 @@ template <int LS = 0, int NP = 0, bool NBR = false> struct AdcEval {
   // j order), so what can overlap is the reads' latency: left to the scheduler, hipcc 7.2 emits read / wait lgkmcnt(0) / add per lookup (64 x ~64 cycles of
   // exposed LDS latency per expansion; three reads in flight at best in round 5's form).  The block only ever lowers the outstanding-LDS count it raised
   // itself, so the compiler's own wait counts around it stay conservative-correct.
-#ifndef COLTT_PQ_SUM_WAITS   // A/B knob: s_waitcnt instructions per block of eight lookups (8: one in front of every add; 2: one per four adds — measured the same to 0.3 %, r06d)
-#define COLTT_PQ_SUM_WAITS 8
-#endif
+  // (tried: two waits per block instead of eight — measured the same to 0.3 %, profiles/r06d_pq_radj_ab.md)
   // J = the first lookup's index within the lane's half; kadd: the lane's byte offset into the pair of interleaved rows (ADDK form: 256-entry rows, the half does
   // not fit beside the code in a byte) — 0 in the BIAS form, where v0 / v1 already carry code + h * C' in every byte
   template <int J> static __device__ __forceinline__ float sum8(float s, uint32_t v0, uint32_t v1, uint32_t kadd) {
@@ -213,7 +178,6 @@ template <int LS = 0, int NP = 0, bool NBR = false> struct AdcEval {
         "ds_read_u16 %6, %6 offset:%18\n\t"
         "ds_read_u16 %7, %7 offset:%19\n\t"
         "ds_read_u16 %8, %8 offset:%20\n\t"
-#if COLTT_PQ_SUM_WAITS == 8
         "s_waitcnt lgkmcnt(7)\n\t" "v_fma_mix_f32 %0, %1, %12, %0 op_sel_hi:[1,0,0]\n\t"
         "s_waitcnt lgkmcnt(6)\n\t" "v_fma_mix_f32 %0, %2, %12, %0 op_sel_hi:[1,0,0]\n\t"
         "s_waitcnt lgkmcnt(5)\n\t" "v_fma_mix_f32 %0, %3, %12, %0 op_sel_hi:[1,0,0]\n\t"
@@ -222,16 +186,6 @@ template <int LS = 0, int NP = 0, bool NBR = false> struct AdcEval {
         "s_waitcnt lgkmcnt(2)\n\t" "v_fma_mix_f32 %0, %6, %12, %0 op_sel_hi:[1,0,0]\n\t"
         "s_waitcnt lgkmcnt(1)\n\t" "v_fma_mix_f32 %0, %7, %12, %0 op_sel_hi:[1,0,0]\n\t"
         "s_waitcnt lgkmcnt(0)\n\t" "v_fma_mix_f32 %0, %8, %12, %0 op_sel_hi:[1,0,0]"
-#else   // two waits per block: 14 issue slots fewer per 16 lookups, the first add of each half behind four reads instead of one
-        "s_waitcnt lgkmcnt(4)\n\t" "v_fma_mix_f32 %0, %1, %12, %0 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %0, %2, %12, %0 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %0, %3, %12, %0 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %0, %4, %12, %0 op_sel_hi:[1,0,0]\n\t"
-        "s_waitcnt lgkmcnt(0)\n\t" "v_fma_mix_f32 %0, %5, %12, %0 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %0, %6, %12, %0 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %0, %7, %12, %0 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %0, %8, %12, %0 op_sel_hi:[1,0,0]"
-#endif
         : "+v"(s), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3), "=&v"(t4), "=&v"(t5), "=&v"(t6), "=&v"(t7)
         : "v"(v0), "v"(v1), "v"(one), "v"(onef),
           "n"((J + 0) * R), "n"((J + 1) * R), "n"((J + 2) * R), "n"((J + 3) * R), "n"((J + 4) * R), "n"((J + 5) * R), "n"((J + 6) * R), "n"((J + 7) * R)
@@ -280,18 +234,6 @@ template <int LS = 0, int NP = 0, bool NBR = false> struct AdcEval {
   // NBR: the code row of candidate `cand`'s neighbour at position idx of its level-0 row (in_row: idx < mMax0)
   __device__ __forceinline__ void prefetch_at(uint32_t cand, uint32_t idx, bool in_row, int /*half*/) {
     if (in_row) load_from(nbrc + (size_t)cand * nbr_stride + (size_t)idx * row_bytes, raw);
-  }
-  // RADJ over the neighbourhood blocks: the runner-up's block is requested at POP time into a second set of row registers; if the runner-up is indeed the
-  // next candidate (no nearer vertex admitted meanwhile — the common case once the result set is full) the rows are simply taken over
-  u32x4e spec_raw[NBR ? NR : 1];
-  __device__ __forceinline__ void prefetch_spec(uint32_t cand, uint32_t idx, bool in_row, int /*half*/) {
-    if constexpr (NBR) { if (in_row) load_from(nbrc + (size_t)cand * nbr_stride + (size_t)idx * row_bytes, spec_raw); }
-  }
-  __device__ __forceinline__ void take_spec() {
-    if constexpr (NBR) {
-#pragma unroll
-      for (int i = 0; i < NR; i++) raw[i] = spec_raw[i];
-    }
   }
   float pre_d;   // EARLY: the table sum of this lane pair's neighbour, computed under the visited probe (both lanes hold it)
   __device__ __forceinline__ void early(bool valid, int /*half*/) { float part = 0.f; if (valid) part = sum(raw); pre_d = pair_total(part); }

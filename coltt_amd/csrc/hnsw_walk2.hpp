@@ -88,23 +88,8 @@ __device__ __forceinline__ float eval_pair_n(const GraphView& g, const WaveCtx& 
   else return pair_distance<METRIC, QUANT, U>(g.rows + (size_t)slot * g.stride, w.qs, g.dim, w.qnorm, rn, half);
 }
 
-// a < b for two WAVE-UNIFORM 64-bit keys (d bits << 32 | slot << 1 | expanded), on the scalar unit: the distance words decide unless they are equal
-// (hipcc compares uniform 64-bit integers on the VALU — two v_mov, v_cmp_lt_u64, then s_and / s_cselect behind the VALU's latency — six to eight times
-// per expansion of the large-ef walks)
-// MEASURED (GPU call H, profiles/r06h_setcache_keylt_ab.md): with the scalar form the operating-point row walk lost 11 % (126.1 against 141.6 k queries/s on one
-// box) — the select chains lengthen the scalar dependence of every pop, and the register allocation of the eight-lane walk moved with them.  The
-// compiler's own form is the default; -DCOLTT_KEY_SCALAR=1 is the A/B partner.
-#ifndef COLTT_KEY_SCALAR
-#define COLTT_KEY_SCALAR 0
-#endif
-__device__ __forceinline__ bool key_lt(unsigned long long a, unsigned long long b) {
-#if COLTT_KEY_SCALAR
-  const uint32_t ah = (uint32_t)(a >> 32), bh = (uint32_t)(b >> 32);
-  return ah != bh ? ah < bh : (uint32_t)a < (uint32_t)b;
-#else
-  return a < b;
-#endif
-}
+// a < b for two wave-uniform 64-bit keys (tried: the compare on the scalar unit — measured 11 % slower, profiles/r06h_setcache_keylt_ab.md)
+__device__ __forceinline__ bool key_lt(unsigned long long a, unsigned long long b) { return a < b; }
 __device__ __forceinline__ unsigned long long key_min(unsigned long long a, unsigned long long b) { return key_lt(b, a) ? b : a; }
 
 // The delta: one (hi, lo) key per lane, lanes [0, n) valid and ASCENDING by key (bit 0 of lo = expanded; slots are distinct, so bit 0 never
@@ -181,38 +166,8 @@ __device__ __forceinline__ void delta_flush(unsigned long long* res, uint32_t& l
   wave_sync();
 }
 
-#ifndef COLTT_EVICT_BULK   // A/B knob: evictions of more than two members by one merge-path step (below)
-#define COLTT_EVICT_BULK 1
-#endif
 // Drop the `e` largest members of main ∪ delta ("keep the ef smallest").
-// The main array's TAIL held in registers across expansions (SETCACHE walks): lane t holds res[tb + t] as it was when the window was loaded.  Nothing but
-// a flush adds to or reorders the main array, evictions only shorten it from the end, and the `expanded` bit a pop sets later is masked wherever the
-// window is read — so the window stays usable until a flush (invalidate) or until more than its 64 entries have been evicted (reload).
-struct TailWin {
-  unsigned long long e; uint32_t tb; bool valid;
-  __device__ __forceinline__ void load(const unsigned long long* res, uint32_t len, int lane) {
-    tb = len > 64u ? len - 64u : 0u;
-    e = tb + (uint32_t)lane < len ? res[tb + lane] : 0ull;
-    valid = true;
-  }
-  // the largest main member with the expanded bit cleared (0 when the array is empty)
-  __device__ __forceinline__ unsigned long long last(const unsigned long long* res, uint32_t len, int lane) {
-    if (!len) return 0ull;
-    if (!valid || len <= tb) load(res, len, lane);   // wave-uniform
-    return readlane_u64(e, (int)(len - 1u - tb)) & ~1ull;
-  }
-};
-__device__ __forceinline__ void evict_largest(const unsigned long long* res, uint32_t& len, Delta& dl, uint32_t e, int lane, TailWin* tw = nullptr) {
-  // the main array's tail in registers: lane t holds res[tb + t]; at most 32 members leave per call
-  if (tw) {
-    for (uint32_t t = 0; t < e; t++) {
-      const unsigned long long mt = tw->last(res, len, lane);
-      if (dl.n && (!len || key_lt(mt, dl.max_key()))) dl.n--;   // the largest member is the delta's last lane
-      else len--;
-    }
-    return;
-  }
-#if COLTT_EVICT_BULK
+__device__ __forceinline__ void evict_largest(const unsigned long long* res, uint32_t& len, Delta& dl, uint32_t e, int lane) {
   if (e > 2u && e <= 64u) {
     // MERGE PATH (round 6): the e largest of main ∪ delta in one step instead of e dependent rounds of four v_readlane + a 64-bit compare.  Both are sorted; with
     // D_i = the delta's i-th largest key and M_j = the main array's j-th largest (expanded bits cleared), D_i is among the e largest of the union iff fewer than
@@ -230,7 +185,6 @@ __device__ __forceinline__ void evict_largest(const unsigned long long* res, uin
     dl.n -= x; len -= e - x;
     return;
   }
-#endif
   const uint32_t tb = len > 64u ? len - 64u : 0u;
   const unsigned long long treg = tb + (uint32_t)lane < len ? res[tb + lane] : 0ull;
   for (uint32_t t = 0; t < e; t++) {
@@ -240,54 +194,14 @@ __device__ __forceinline__ void evict_largest(const unsigned long long* res, uin
   }
 }
 
-#ifndef COLTT_PQ_BYSET
-#define COLTT_PQ_BYSET 0
-#endif
-// Is the lane's key (khi = distance bits, klo = slot << 1) a CURRENT member of main ∪ delta?  (COLTT_PQ_BYSET, see search_level2; EVERY lane must call — never
-// behind a per-lane `want && ...` short circuit: the delta's keys sit one per lane, an inactive lane's key is not compared — that bug cost three GPU calls.)  Called by every lane of the wave; the lanes with `want` test.
-// The main array is sorted by key and a member's key differs from the probe in the `expanded` bit at most: a binary search; the delta's <= 64 keys sit one
-// per lane: one broadcast + compare per lane that the array did not settle.  LDS and registers only — no memory request.
-__device__ __forceinline__ bool set_member(const unsigned long long* res, uint32_t len, const Delta& dl, bool want, uint32_t khi, uint32_t klo, uint32_t rej_slot, int lane) {
-  // lower bound of the key in the main array, the SAME number of steps in every lane (a lane without a key searches for ~0): no divergent loop in front of
-  // the cross-lane operations below
-  const unsigned long long key = want ? ((((unsigned long long)khi) << 32) | klo) : ~0ull;
-  uint32_t base = 0;
-  for (uint32_t sz = len; sz > 1u;) {   // wave-uniform trip count
-    const uint32_t h = sz >> 1;
-    base = res[base + h - 1u] < key ? base + h : base;
-    sz -= h;
-  }
-  bool member = false;
-  if (len) {
-    const unsigned long long e0 = res[base];
-    const uint32_t pos = base + (e0 < key ? 1u : 0u);
-    const unsigned long long e = pos < len ? res[pos] : ~0ull;
-    member = want && pos < len && ((e ^ key) >> 1) == 0ull;
-  }
-  // the delta's keys (one per lane) and the vertices the walk REJECTED in the expansion that filled the set (rej_slot, one per lane or NBR_NONE): they were
-  // tested against a lowerBound sampled before that expansion's unconditional admissions raised the worst member, so they may lie under a later bound
-  // without being members — the only visited non-members that can
-  unsigned long long cand = __ballot(want && !member);
-  while (cand) {
-    const int j = __builtin_ctzll(cand); cand &= cand - 1;
-    const uint32_t kh = (uint32_t)__builtin_amdgcn_readlane((int)khi, j), kl = (uint32_t)__builtin_amdgcn_readlane((int)klo, j);
-    const unsigned long long hit = __ballot(((uint32_t)lane < dl.n && dl.hi == kh && ((dl.lo ^ kl) >> 1) == 0u) || rej_slot == (kl >> 1));
-    if (hit && lane == j) member = true;
-  }
-  return member;
-}
-
 // Where the distances of a chunk come from.  The throughput kernels evaluate them in place (one lane pair per row, exact.hpp); the
 // latency kernel (hnsw_lat.hpp) hands the chunk to all four waves of its workgroup.  Called by every lane of the walking wave.
 template <int METRIC, int QUANT, int PROFILE, bool ADJN, bool R8 = false> struct PairEval {
   static constexpr bool CHUNK_ADJ = false;   // the evaluator does not bring the neighbours' adjacency rows along
-  static constexpr bool SPEC = false;        // no speculation on the next expansion's inputs (see AdcEval, hnsw_pq.hpp)
   static constexpr bool RADJ = false;        // the runner-up's adjacency row is not requested at pop time
   static constexpr bool ROWPF = false;       // no per-neighbour input addressed by (candidate, position) (see AdcEval<.., NBR>, hnsw_pq.hpp)
-  static constexpr bool SETCACHE = false;    // the head / tail windows of the main array are not cached in registers (register budget of the row walks)
   static constexpr bool EARLY = false;       // distances are computed for the fresh neighbours only, after the visited test
   static constexpr bool BOUNDED = false;     // the reference's order: visited test first, every fresh neighbour evaluated (hnsw.go:366-373)
-  static constexpr bool SPLIT = false;       // no evaluation pass in front of the visited probe's answer (see Group8Eval)
   __device__ __forceinline__ uint32_t chunk_adj(int, int) const { return NBR_NONE; }
   __device__ __forceinline__ void prefetch(uint32_t, bool, int) const {}   // nothing worth requesting before the visited test (a row is 1.5-3 KB)
   __device__ __forceinline__ float operator()(const GraphView& g, const WaveCtx& w, uint32_t nb, bool fresh, float nrm, int half, int /*lane*/) const {
@@ -322,47 +236,23 @@ template <int METRIC, int QUANT, int PROFILE, bool ADJN, bool R8 = false> struct
 #ifndef COLTT_G8_U_H16
 #define COLTT_G8_U_H16 12
 #endif
-// SPLIT (round 6, third session; A/B knob, exact, measured SLOWER, off): behind the Bloom filter a listed neighbour is either DEFINITELY fresh (a negative
-// answer) or needs the dependent probe of the HBM byte map, and the walk waits for that probe before it requests a single row.  With the knob the probe is
-// issued, the first full pass of definitely-fresh rows (8 x ROWS of them: two thirds of a listed row are Bloom negatives) is requested and evaluated under it,
-// and the probe's answer is looked at only then; the remaining fresh neighbours follow in the usual passes.  Every neighbour's distance is the same function of
-// the same row whichever pass computes it and admission sees all of them at once: ids, score bits and counters are unchanged (GPU call AE: same answers'
-// hash from both libraries).  But the walk under load is bound by the memory system's row gather, not by one wave's dependent chain: 10 M x 768 f16, ef 1 024,
-// same box: 79.5 ms per 10 000 queries without, 80.9 ms with (ef 256 and f32 rows: +-0) — profiles/r06ae_split_pass_ab.md.
-#ifndef COLTT_G8_SPLIT
-#define COLTT_G8_SPLIT 0
-#endif
-// ONEBURST (HBM-visited 2-byte kernels): rows of exactly U lines are read in one burst without a second buffer (rows8.hpp), and the registers that frees
-// carry a second row per lane group — 16 rows per pass instead of 8, i.e. one dependent round trip less per expansion of ~21 fresh neighbours.
-#ifndef COLTT_G8_ONEBURST_H16
-#define COLTT_G8_ONEBURST_H16 0
-#endif
-#ifndef COLTT_G8_STREAM
-#define COLTT_G8_STREAM 1
-#endif
-#ifndef COLTT_G8_ONEBURST   // the same for the other eight-lane kernels (f32 rows; 2-byte rows behind the LDS hash): rows of exactly COLTT_G8_U lines in one burst
-#define COLTT_G8_ONEBURST 0
-#endif
+// tried: a pass of Bloom-negative rows evaluated under the byte-map probe — measured slower, profiles/r06ae_split_pass_ab.md
+// tried: whole rows in one burst, 16 rows per pass — measured +0.5 %, not worth a second code path, profiles/r06af_oneburst_ab.jsonl
 template <int METRIC, int QUANT, bool ADJN, bool HBM16 = false, bool NT = false> struct Group8Eval {   // NT: exact.hpp row_ld
-  static constexpr bool ONEB = HBM16 ? COLTT_G8_ONEBURST_H16 != 0 : COLTT_G8_ONEBURST != 0;
   // f32 rows read with the non-temporal hint (collections far larger than the caches): ONE row per lane group with 12 lines in flight instead of two rows x 6 —
   // 10 M x 768 f32, hint on, same process: ef 128 19.39 -> 19.09 ms per 10 000 queries, ef 256 40.77 -> 40.31, ef 512 78.05 -> 77.46 (call AQ; +2.6 / +3 % on the
   // boxes of calls AO / AP); without the hint, and for 2-byte rows behind the LDS hash with or without it (9.7 -> 11.6 ms), two rows x 6 stay better.
   static constexpr bool F32NT = NT && QUANT == Q_NONE && !HBM16;
-  static constexpr int G8R = (ONEB && HBM16) ? 2 : (HBM16 ? COLTT_G8_ROWS_H16 : (F32NT ? COLTT_G8_ROWS_NT32 : COLTT_G8_ROWS)),
+  static constexpr int G8R = HBM16 ? COLTT_G8_ROWS_H16 : (F32NT ? COLTT_G8_ROWS_NT32 : COLTT_G8_ROWS),
                        G8U = HBM16 ? COLTT_G8_U_H16 : (F32NT ? COLTT_G8_U_NT32 : COLTT_G8_U);
-  // COLTT_G8_STREAM (bit 0: the f32 non-temporal twins, bit 1: the HBM-visited 2-byte walk): rows of a whole number of bursts are evaluated as one stream of
-  // bursts over all passes of the chunk — no bubble at the pass boundaries (rows8.hpp: group8_stream)
-  static constexpr bool STREAM = G8R == 1 && !ONEB && ((F32NT && (COLTT_G8_STREAM & 1)) || (HBM16 && (COLTT_G8_STREAM & 2)) || (!HBM16 && (COLTT_G8_STREAM & 4)));   // bit 2: every other eight-lane kernel built with one row per group (A/B)
+  // one row per lane group, f32 non-temporal twins: rows of a whole number of bursts are evaluated as one stream of bursts over all passes of the chunk —
+  // no bubble at the pass boundaries (rows8.hpp: group8_stream)
+  static constexpr bool STREAM = G8R == 1 && F32NT;
   static constexpr bool CHUNK_ADJ = false;
-  static constexpr bool SPEC = false;
   static constexpr bool RADJ = false;
   static constexpr bool ROWPF = false;
   static constexpr bool EARLY = false;
   static constexpr bool BOUNDED = false;
-  static constexpr bool SETCACHE = false;
-  static constexpr bool SPLIT = COLTT_G8_SPLIT != 0;
-  static constexpr int PASS_ROWS = 8 * G8R;   // rows one pass evaluates
   __device__ __forceinline__ uint32_t chunk_adj(int, int) const { return NBR_NONE; }
   __device__ __forceinline__ void prefetch(uint32_t, bool, int) const {}
   // distances of the chunk's `fresh` neighbours (one per lane pair, held by both lanes); the result is valid in BOTH lanes of a pair
@@ -396,7 +286,7 @@ template <int METRIC, int QUANT, bool ADJN, bool HBM16 = false, bool NT = false>
         rn[i] = 0.f;
         if constexpr (METRIC == M_COS) { if constexpr (ADJN) rn[i] = s_nr[live[i] ? idx[i] : 0]; else rn[i] = g.norms[slot]; }
       }
-      group8_distance<METRIC, QUANT, ROWS, G8U, ONEB, NT>(rp, live, w.qp, nl, w.qnorm, rn, rj, d);
+      group8_distance<METRIC, QUANT, ROWS, G8U, NT>(rp, live, w.qp, nl, w.qnorm, rn, rj, d);
 #pragma unroll
       for (int i = 0; i < ROWS; i++) if (rj == 0 && live[i]) s_d[idx[i]] = d[i];
     }
@@ -412,7 +302,7 @@ template <int METRIC, int QUANT, bool ADJN, bool HBM16 = false, bool NT = false>
     const bool live[1] = {true};
     float rn[1] = {0.f}, d[1];
     if constexpr (METRIC == M_COS) rn[0] = g.norms[slot];
-    group8_distance<METRIC, QUANT, 1, G8U, ONEB, NT>(rp, live, w.qp, (g.dim * (QUANT == Q_NONE ? 4 : 2)) >> 7, w.qnorm, rn, lane & 7, d);
+    group8_distance<METRIC, QUANT, 1, G8U, NT>(rp, live, w.qp, (g.dim * (QUANT == Q_NONE ? 4 : 2)) >> 7, w.qnorm, rn, lane & 7, d);
     return d[0];
   }
 };
@@ -452,18 +342,9 @@ __device__ __forceinline__ void greedy_level8(const GraphView& g, WaveCtx& w, ui
   }
 }
 // Probe of the HBM byte map.  The region is this wave's own for the whole launch; the load must not be served by a stale L1 line (the wave's own marks went
-// to L2): the agent-scope atomic load (`sc1`) bypasses L1 — and so does a non-temporal load (`nt`, MI355X_MICROARCH.md), which in addition tells L2 / MALL that
-// the line will not be used again: a random probe pulls in a whole line for one byte, and what it displaces are the neighbourhood blocks and adjacency rows of hub
-// vertices that other traversals do re-read.  COLTT_VIS_NT: 0 = `sc1` (rounds 2-6), 1 = `nt` (A/B knob).
-#ifndef COLTT_VIS_NT
-#define COLTT_VIS_NT 0
-#endif
+// to L2): the agent-scope atomic load (`sc1`) bypasses L1.  (tried: a non-temporal load — measured 1 % slower, profiles/r06ai_op_visnt.jsonl)
 template <class T> __device__ __forceinline__ T vis_probe(const T* p) {
-#if COLTT_VIS_NT
-  return __builtin_nontemporal_load(p);
-#else
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 enum { VIS_HBM = 0, VIS_LDS = 1 };   // visited set of search_level2: HBM byte map (behind the Bloom filter) | LDS hash that is never reset (err 8)
 
@@ -506,16 +387,7 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
   uint32_t len = 1;
   uint32_t scan_lo = 0;   // every main-array member before this index is expanded (pop scans start at its 64-entry chunk)
   Delta dl; dl.clear();
-  unsigned long long hwin = 1ull; uint32_t hb = 0; bool hvalid = false;   // SETCACHE: the head window (pop)
-  TailWin twin; twin.e = 0ull; twin.tb = 0; twin.valid = false;           // SETCACHE: the tail window (lowerBound, eviction)
   uint32_t pre_slot = NBR_NONE, pre_nb = NBR_NONE; float pre_nn = 0.f;
-  // SPEC evaluators (small per-neighbour inputs: hnsw_pq.hpp): when the next candidate is predicted to be the runner-up — whose adjacency row was
-  // requested at pop time and has arrived by the end of the expansion — the visited bytes and the evaluator's inputs of ITS neighbours are requested
-  // one expansion ahead (spec_slot = that candidate; spec_vis = the byte-map values).  The probe is issued after every visited mark of the current
-  // expansion (program order, agent-scope accesses served by L2) and nothing marks in between, so the values are exactly what the probe of the
-  // next expansion would read.
-  uint32_t spec_slot = NBR_NONE; uint32_t spec_vis = 0;
-  uint32_t rej_slot = NBR_NONE;   // BOUNDED: the fresh neighbour this lane pair rejected in the expansion that filled the set (see set_member)
   const uint32_t width = g.mMax0;
   wave_sync();
   for (uint32_t iters = 0;; iters++) {
@@ -525,38 +397,18 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
     // ---- pop: the smallest unexpanded member of main ∪ delta (cj = the unexpanded main member after the first one).  The keys come out of
     // the registers the scan loaded its chunk into (v_readlane), not out of a second, dependent LDS read.
     typedef typename std::remove_reference<EVAL>::type eval_t;
-    constexpr bool CACHE = DELTA && eval_t::SETCACHE;
     int ci = -1, cj = -1;
     unsigned long long kci = ~0ull, kcj = ~0ull;
-    if constexpr (CACHE) {
-      // SETCACHE: the 64-entry chunk that holds the first unexpanded main member stays in registers from pop to pop (hwin, base hb): only a flush changes
-      // the array's members (it invalidates the window), a pop's `expanded` bit is set in the register too, evictions are a compare against len
-      for (;;) {
-        const uint32_t want = scan_lo & ~63u;
-        if (want >= len) break;
-        if (!hvalid || hb != want) { hb = want; hwin = hb + (uint32_t)lane < len ? res[hb + lane] : 1ull; hvalid = true; }
-        unsigned long long m = __ballot(!(hwin & 1ull) && hb + (uint32_t)lane < len);
-        if (m) {
-          const int l0 = __builtin_ctzll(m);
-          ci = (int)hb + l0; kci = readlane_u64(hwin, l0);
-          m &= m - 1;
-          if (m) { const int l1 = __builtin_ctzll(m); cj = (int)hb + l1; kcj = readlane_u64(hwin, l1); }
-          break;
-        }
-        scan_lo = hb + 64u;   // every member of this chunk is expanded
-      }
-    } else {
-      for (uint32_t base = scan_lo & ~63u; base < len; base += 64) {
-        const uint32_t i = base + lane;
-        const unsigned long long e = i < len ? res[i] : 1ull;
-        unsigned long long m = __ballot(!(e & 1ull));
-        if (m) {
-          const int l0 = __builtin_ctzll(m);
-          ci = (int)base + l0; kci = readlane_u64(e, l0);
-          m &= m - 1;
-          if (m) { const int l1 = __builtin_ctzll(m); cj = (int)base + l1; kcj = readlane_u64(e, l1); }
-          break;
-        }
+    for (uint32_t base = scan_lo & ~63u; base < len; base += 64) {
+      const uint32_t i = base + lane;
+      const unsigned long long e = i < len ? res[i] : 1ull;
+      unsigned long long m = __ballot(!(e & 1ull));
+      if (m) {
+        const int l0 = __builtin_ctzll(m);
+        ci = (int)base + l0; kci = readlane_u64(e, l0);
+        m &= m - 1;
+        if (m) { const int l1 = __builtin_ctzll(m); cj = (int)base + l1; kcj = readlane_u64(e, l1); }
+        break;
       }
     }
     unsigned long long kd = ~0ull; int dlane = -1;
@@ -586,23 +438,17 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
     uint32_t runner_nb = NBR_NONE;
     if constexpr (eval_t::RADJ && PREF) {
       if (runner_key != ~0ull && (uint32_t)p < g.mMax0) runner_nb = g.adj0[(size_t)((uint32_t)runner_key >> 1) * g.mMax0 + p];
-      // ... and with it the evaluator's (candidate, position)-addressed inputs of the runner-up's neighbours (AdcEval<.., NBR>: their code rows): a whole
-      // expansion of lead time instead of the pop's
-      if constexpr (eval_t::ROWPF) { if (runner_key != ~0ull && g.mMax0 <= 32) ev.prefetch_spec((uint32_t)runner_key >> 1, (uint32_t)p, (uint32_t)p < g.mMax0, half); }
     }
     int best_src = -1;   // lane of the smallest key admitted in this expansion's (single) chunk
     COLTT_PT(w, 0)  // pop
     // lowerBound: the distance of the largest member, sampled once per pop (hnsw.go:357)
-    unsigned long long worst;
-    if constexpr (CACHE) worst = twin.last(res, len, lane);
-    else worst = len ? (res[len - 1] & ~1ull) : 0ull;
+    unsigned long long worst = len ? (res[len - 1] & ~1ull) : 0ull;
     if constexpr (DELTA) { const unsigned long long dmx = dl.max_key(); worst = key_lt(worst, dmx) ? dmx : worst; }
     const float lower_bound = __uint_as_float((uint32_t)(worst >> 32));
     wave_sync();
     if (from_delta) { if (lane == dlane) dl.lo |= 1u; }
     else {
       if (lane == 0) res[ci] = ce | 1ull;
-      if constexpr (CACHE) { if ((uint32_t)lane == (uint32_t)ci - hb) hwin |= 1ull; }
       scan_lo = (uint32_t)ci + 1;
     }
     const uint32_t cslot = (uint32_t)ce >> 1;
@@ -613,22 +459,15 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
     // exactly that of the unbounded walk; n_dist counts the evaluations that passed the bound and were fresh.
     // What this buys is the visited MARKS: a byte store into the map is a read-modify-write in HBM, and 22 of them per expansion became ~3.4 — 412.6 -> 467.8 k
     // queries/s at 10 M x 768, ef 1 344 (profiles/r06o_*).
-    // -DCOLTT_PQ_BYSET=1 (A/B knob, exact, measured SLOWER, off): THE RESULT SET AS THE VISITED SET.  A vertex under the bound that was met before was admitted (it
-    // was under the bound then, too: the bound only falls) and is still a member — had it been evicted, it would be above the bound now; the one exception are the
-    // neighbours REJECTED by the expansion that filled the set (rej_slot, see set_member).  So in a full set "visited" == "is a current member", and the byte map
-    // need not be read or written again.  But the membership test — a binary search of 11 dependent LDS reads + the delta's registers — costs more than the probe
-    // it replaces, which flies under the table sums: 467.8 -> 403.9 k queries/s, one query 2.75 -> 3.66 ms (profiles/r06s_*).
-    // (Rows wider than one chunk keep the byte map in any case: the set changes between the chunks of one expansion, the oracle's visited set does not.)
+    // (tried: the result set as the visited set of a full set — measured slower, profiles/r06s_pq_probe_byset.jsonl)
     const bool full_at_pop = free_slots == 0;
-    const bool by_set = COLTT_PQ_BYSET != 0 && full_at_pop && width <= 32;
     w.n_exp++;
     wave_sync();
     const uint32_t* row = g.adj0 + (size_t)cslot * width;
     const float* nrow = ADJN ? g.adj0_n + (size_t)cslot * width : nullptr;
     const bool use_pre = pre_slot == cslot;
     const uint32_t pre_now = pre_nb; const float pre_nn_now = pre_nn;
-    const uint32_t spec_now = spec_slot, spec_vis_now = spec_vis;
-    pre_slot = NBR_NONE; spec_slot = NBR_NONE;
+    pre_slot = NBR_NONE;
     unsigned long long best_new = ~0ull;
 #define COLTT_PREFETCH_NEXT2()                                                                       \
     if constexpr (PREF) {                                                                            \
@@ -639,19 +478,7 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
         else if (eval_t::CHUNK_ADJ && width <= 32 && best_src >= 0) pre_nb = (uint32_t)p < width ? ev.chunk_adj(best_src >> 1, p) : NBR_NONE; \
         else pre_nb = (uint32_t)p < width ? g.adj0[(size_t)pre_slot * width + p] : NBR_NONE;        \
         if constexpr (ADJN) pre_nn = (uint32_t)p < width ? g.adj0_n[(size_t)pre_slot * width + p] : 0.f; \
-        if constexpr (eval_t::ROWPF) {                                                                 \
-          if (eval_t::RADJ && width <= 32 && runner_key < best_new) ev.take_spec();   /* requested at pop time: the runner-up it is */ \
-          else ev.prefetch_at(pre_slot, (uint32_t)p, (uint32_t)p < width, half);       /* the next candidate's neighbours' inputs fly with its adjacency row */ \
-        }                                                                                              \
-        if constexpr (eval_t::SPEC) {                                                                \
-          spec_slot = NBR_NONE;                                                                      \
-          if (width <= 32 && runner_key < best_new) {   /* pre_nb is in registers (requested at pop time) */ \
-            spec_slot = pre_slot;                                                                    \
-            const bool sv_ = pre_nb != NBR_NONE;                                                     \
-            if constexpr (VISMODE == VIS_HBM) { spec_vis = 0; if (sv_ && half == 0) spec_vis = __hip_atomic_load(w.visg + pre_nb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } \
-            ev.prefetch(pre_nb, sv_, half);                                                          \
-          }                                                                                          \
-        }                                                                                            \
+        if constexpr (eval_t::ROWPF) ev.prefetch_at(pre_slot, (uint32_t)p, (uint32_t)p < width, half);   /* the next candidate's neighbours' inputs fly with its adjacency row */ \
       }                                                                                              \
     }
     for (uint32_t c0 = 0; c0 < width; c0 += 32) {
@@ -663,31 +490,18 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
       float nrm = 0.f;
       if constexpr (ADJN) nrm = idx < width ? (pre_hit ? pre_nn_now : nrow[idx]) : 0.f;
       const bool valid = nb != NBR_NONE && !is_deleted(g, nb);
-      bool spec_hit = false;
-      if constexpr (eval_t::SPEC) spec_hit = pre_hit && spec_now == cslot;   // this expansion's inputs were requested during the previous one
       if constexpr (eval_t::ROWPF) { if (!pre_hit) ev.prefetch_at(cslot, idx, idx < width, half); }   // (requested with the adjacency row when that was prefetched)
-      else { if (!spec_hit) ev.prefetch(nb, valid, half); }   // evaluators whose per-neighbour input is small (hnsw_pq.hpp: a 32-128 byte code row) request it NOW, under the visited test
+      else ev.prefetch(nb, valid, half);   // evaluators whose per-neighbour input is small (hnsw_pq.hpp: a 32-128 byte code row) request it NOW, under the visited test
 #ifdef COLTT_PHASE_TIMING
       if (__ballot(valid) == 0xdeadbeefcafeull) w.err |= 64u;  // forces the adjacency values to have arrived
 #endif
       COLTT_PT(w, 1)  // adjacency row
       int fresh_i = 0;
-      bool split_done = false; float split_d = 0.f;   // SPLIT evaluators: this pair's row went through the pass in front of the probe's answer
       if constexpr (eval_t::EARLY && VISMODE == VIS_HBM && !BLOOM) {
         // The probe of the byte map is ISSUED, the evaluator computes the distances of all listed neighbours out of inputs that are already on chip
         // (AdcEval<.., NBR>: the code rows came with the adjacency row), and only then is the probe's answer looked at: its round trip runs under
         // ~200 issue slots of table lookups instead of in front of them.  Test-and-set as below.
-        static_assert(!eval_t::SPEC, "EARLY evaluators take no speculative visited bytes");
         const bool probe = valid && half == 0;
-        if (eval_t::BOUNDED && by_set) {
-          // full set: the table sums, the bound, then membership in the result set (no probe, no mark)
-          ev.early(valid, half);
-          const bool want = probe && ev.pre_d < lower_bound;
-          if (__ballot(want)) {   // (every lane calls: the delta's keys sit one per lane)
-            const bool member = set_member(res, len, dl, want, __float_as_uint(ev.pre_d), nb << 1, rej_slot, lane);
-            fresh_i = (want && !member) ? 1 : 0;
-          }
-        } else {
         // The aligned 32-bit word around the byte is loaded (no zero-extension for the compiler to place — with its s_waitcnt vmcnt — right behind the
         // load) and the byte is taken out of it after early().  The region is this wave's own and its size a multiple of 16; agent scope: served by L2.
         // EVERY lane loads (the others word 0 of the region: one more address in the same request): a load under a divergent branch would leave the
@@ -697,45 +511,15 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
         ev.after_early(vw);   // the probe's value is not looked at (no s_waitcnt vmcnt for it) before the table sums are there
         const uint32_t v = (vw >> ((nb & 3u) * 8u)) & 0xffu;
         fresh_i = probe && v != (w.epoch & 0xffu) ? 1 : 0;
-        if constexpr (eval_t::BOUNDED) { if (full_at_pop && !(ev.pre_d < lower_bound)) fresh_i = 0; }   // (wide rows) the bound: not marked, not counted
-        if (fresh_i) __hip_atomic_store(w.visg + nb, (uint8_t)w.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      } else if constexpr (eval_t::SPLIT && BLOOM && VISMODE == VIS_HBM && !eval_t::EARLY && !eval_t::BOUNDED && !eval_t::SPEC) {
-        // Bloom filter, then the byte-map probe of the positives ISSUED and the first full pass of definitely-fresh rows evaluated under it (see COLTT_G8_SPLIT)
-        const bool want = valid && half == 0;
-        bool maybe = false;
-        if (want) {
-          const uint32_t h = nb * 0x9E3779B1u;
-          const uint32_t bits = (1u << (h & 31u)) | (1u << ((h >> 5) & 31u));
-          const uint32_t old = atomicOr(&w.bloom[h >> w.bloom_shift], bits);
-          maybe = (old & bits) == bits;
-        }
-        const bool sure = want && !maybe;
-        const unsigned long long S = __ballot(sure);
-        // every lane loads (the others byte 0 of the region: one more address in the same request) — no divergent branch around a load in flight
-        const uint8_t pv = vis_probe(w.visg + (maybe ? nb : 0u));
-        if ((uint32_t)__popcll(S) >= (uint32_t)eval_t::PASS_ROWS && __ballot(maybe)) {   // wave-uniform: a full pass of negatives and a probe to hide
-          const uint32_t srank = __builtin_amdgcn_mbcnt_hi((uint32_t)(S >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)S, 0u));
-          int first_i = (sure && srank < (uint32_t)eval_t::PASS_ROWS) ? 1 : 0;
-          first_i = __builtin_amdgcn_mov_dpp(first_i, 0xA0, 0xf, 0xf, true);   // to the odd lane of the pair
-          split_done = first_i != 0;
-          split_d = ev(g, w, nb, split_done, nrm, half, lane);
-        }
-        fresh_i = (sure || (maybe && pv != (uint8_t)w.epoch)) ? 1 : 0;
+        if constexpr (eval_t::BOUNDED) { if (full_at_pop && !(ev.pre_d < lower_bound)) fresh_i = 0; }   // the bound: not marked, not counted
         if (fresh_i) __hip_atomic_store(w.visg + nb, (uint8_t)w.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       } else {
         if constexpr (eval_t::EARLY) ev.early(valid, half);
         bool want = valid && half == 0;
-        if constexpr (eval_t::BOUNDED) {   // full set (see full_at_pop): the table sums of ALL listed neighbours, the bound, then membership in the result set
-          if (full_at_pop) {
-            bounded_d = ev.eval_now(valid, half); want = want && bounded_d < lower_bound;
-            if (by_set && __ballot(want)) {   // (every lane calls: the delta's keys sit one per lane)
-              const bool member = set_member(res, len, dl, want, __float_as_uint(bounded_d), nb << 1, rej_slot, lane);
-              fresh_i = (want && !member) ? 1 : 0;
-            }
-          }
+        if constexpr (eval_t::BOUNDED) {   // full set (see full_at_pop): the table sums of ALL listed neighbours, then the bound
+          if (full_at_pop) { bounded_d = ev.eval_now(valid, half); want = want && bounded_d < lower_bound; }
         }
-        if (want && !(eval_t::BOUNDED && by_set)) {
+        if (want) {
           // Test-and-set.  No two lanes hold the same slot (a row lists a neighbour once), so load + store on the byte map is
           // race-free; agent-scope atomics are served by L2, never by a stale L1 line.
           bool maybe = true;
@@ -748,7 +532,7 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
           if constexpr (VISMODE == VIS_LDS) fresh_i = vis_insert(w.vis, w.hcap_mask, nb) ? 1 : 0;
           else {
             if (maybe) {
-              const uint8_t v = spec_hit ? (uint8_t)spec_vis_now : vis_probe(w.visg + nb);
+              const uint8_t v = vis_probe(w.visg + nb);
               fresh_i = v != (uint8_t)w.epoch ? 1 : 0;
             } else fresh_i = 1;
             if (fresh_i) __hip_atomic_store(w.visg + nb, (uint8_t)w.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -762,18 +546,12 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
       COLTT_PT(w, 2)  // visited test-and-set
       const bool last_chunk = c0 + 32 >= width;
       if (nfresh == 0) { if (last_chunk) { COLTT_PREFETCH_NEXT2() } continue; }
-      w.n_dist += nfresh; vis_count += (eval_t::BOUNDED && by_set) ? 0u : nfresh;   // (vis_count: entries of the LDS hash)
+      w.n_dist += nfresh; vis_count += nfresh;   // (vis_count: entries of the LDS hash)
       float d;
       if constexpr (eval_t::BOUNDED && !eval_t::EARLY) { if (full_at_pop) d = fresh ? bounded_d : 0.f; else d = ev(g, w, nb, fresh, nrm, half, lane); }
-      else if constexpr (eval_t::SPLIT) {
-        const bool rest = fresh && !split_done;
-        d = split_d;
-        if (__ballot(rest)) { const float d2 = ev(g, w, nb, rest, nrm, half, lane); d = split_done ? split_d : d2; }
-      }
       else d = ev(g, w, nb, fresh, nrm, half, lane);
       const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(E >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)E, 0u));   // fresh neighbours in front of this lane
       const bool adm = fresh && half == 0 && (rank < free_slots || d < lower_bound);
-      if constexpr (eval_t::BOUNDED) { if (!full_at_pop && fresh && half == 0 && !adm) rej_slot = nb; }   // only the expansion that fills the set rejects while filling
 #ifdef COLTT_PHASE_TIMING
       if (__ballot(adm) == 0xdeadbeefcafeull) w.err |= 64u;  // forces the distances
 #endif
@@ -801,7 +579,7 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
         }
         if (last_chunk) { COLTT_PREFETCH_NEXT2() }
         if (m == 0) continue;
-        if (dl.n + m > 64u) { delta_flush(res, len, dl, scan_lo, lane); hvalid = false; twin.valid = false; }
+        if (dl.n + m > 64u) delta_flush(res, len, dl, scan_lo, lane);
         {
           unsigned long long am = A;
           while (am) {
@@ -810,7 +588,7 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
           }
         }
         const uint32_t total = len + dl.n;
-        if (total > ef) { if constexpr (CACHE) evict_largest(res, len, dl, total - ef, lane, &twin); else evict_largest(res, len, dl, total - ef, lane); }
+        if (total > ef) evict_largest(res, len, dl, total - ef, lane);
         COLTT_PT(w, 4)  // admission + eviction (+ the occasional flush)
       } else {
         uint32_t myrank = 0;  // rank of my key among the admitted ones (readlane broadcasts: no LDS round trips)

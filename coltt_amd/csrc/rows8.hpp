@@ -75,10 +75,7 @@ __device__ __forceinline__ float group8_hsum(float a) {
 // Distance(query, row) of ROWS rows per 8-lane group at once (ROWS x U..2U 16-byte loads per lane in flight); rj = this lane's
 // residue (lane & 7).  row8[i] -> the rows8 copy of row i, qp -> the permuted query in LDS, nl = 128-byte lines per row.
 // live[i] == false: this group has no i-th row in this pass — row8[i] then points at some live row, the result is dropped by the caller.
-#ifndef COLTT_G8_PEEL   // A/B knob: see the burst loop below
-#define COLTT_G8_PEEL 0
-#endif
-template <int METRIC, int QUANT, int ROWS, int U, bool ONEBURST = false, bool NT = false>
+template <int METRIC, int QUANT, int ROWS, int U, bool NT = false>
 __device__ __forceinline__ void group8_distance(const uint8_t* const (&row8)[ROWS], const bool (&live)[ROWS], const float* __restrict__ qp, int nl,
                                                 float qnorm, const float (&rnorm)[ROWS], int rj, float (&out)[ROWS]) {
   constexpr int S = rows8_steps<QUANT>();
@@ -119,6 +116,7 @@ __device__ __forceinline__ void group8_distance(const uint8_t* const (&row8)[ROW
     }                                                                                                                         \
   }
   // bursts of UU lines, the next burst requested before the current one is consumed (2 x ROWS x UU 16-byte loads per lane in flight at most)
+  // (a lambda called once: written out in place, the same code is register-allocated differently in the eight-lane walks)
   auto bursts = [&](auto uc) {
     constexpr int UU = decltype(uc)::value;
     const int nb = nl / UU;
@@ -127,22 +125,6 @@ __device__ __forceinline__ void group8_distance(const uint8_t* const (&row8)[ROW
 #pragma unroll
       for (int u = 0; u < UU; u++) COLTT_G8_LD(u, cur[u])
     }
-#if COLTT_G8_PEEL
-    // the last burst peeled off: inside the loop the next burst is requested UNCONDITIONALLY (a branch around loads in flight makes the compiler wait for all of
-    // them — vmcnt(0) — in front of the first use of the current burst: see group8_stream)
-    for (int b = 0; b + 1 < nb; b++) {
-#pragma unroll
-      for (int u = 0; u < UU; u++) COLTT_G8_LD((b + 1) * UU + u, nxt[u])
-#pragma unroll
-      for (int u = 0; u < UU; u++) COLTT_G8_CS(cur[u], b * UU + u)
-#pragma unroll
-      for (int u = 0; u < UU; u++) cur[u] = nxt[u];
-    }
-    if (nb > 0) {
-#pragma unroll
-      for (int u = 0; u < UU; u++) COLTT_G8_CS(cur[u], (nb - 1) * UU + u)
-    }
-#else
     for (int b = 0; b < nb; b++) {
       if (b + 1 < nb) {
 #pragma unroll
@@ -153,7 +135,6 @@ __device__ __forceinline__ void group8_distance(const uint8_t* const (&row8)[ROW
 #pragma unroll
       for (int u = 0; u < UU; u++) cur[u] = nxt[u];
     }
-#endif
     // lines beyond whole bursts (nl % UU; the whole row when nl < UU — 128-d f32 rows are 4 lines): ONE predicated burst, every load
     // in flight before the first is consumed (a line-by-line loop here made a short row cost nl dependent round trips: 1 M x 128 f32,
     // one query, 0.111 -> 0.191 ms in the first bench run of this core)
@@ -165,17 +146,7 @@ __device__ __forceinline__ void group8_distance(const uint8_t* const (&row8)[ROW
       for (int u = 0; u < UU; u++) if (l0 + u < nl) COLTT_G8_CS(cur[u], l0 + u)
     }
   };
-  if constexpr (ONEBURST) {
-    // rows of exactly U lines (768 x 2-byte with U = 12): the WHOLE row of every one of the ROWS rows in flight at once, no second buffer — the registers the
-    // double-buffered form spends on `nxt` carry a second row instead (ROWS = 2: 16 rows per pass at the register cost of 8).  Any other length: bursts of U / 2.
-    if (nl == U) {
-      Raw cur[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) COLTT_G8_LD(u, cur[u])
-#pragma unroll
-      for (int u = 0; u < U; u++) COLTT_G8_CS(cur[u], u)
-    } else bursts(std::integral_constant<int, (U / 2 > 0 ? U / 2 : 1)>());
-  } else bursts(std::integral_constant<int, U>());
+  bursts(std::integral_constant<int, U>());
 #undef COLTT_G8_LD
 #undef COLTT_G8_CS
 #pragma unroll
@@ -186,7 +157,7 @@ __device__ __forceinline__ void group8_distance(const uint8_t* const (&row8)[ROW
   }
 }
 
-// ONE row per lane group, the rows of ALL passes as one stream of bursts (COLTT_G8_STREAM): group8_distance leaves a bubble at every pass boundary — the last
+// ONE row per lane group, the rows of ALL passes as one stream of bursts: group8_distance leaves a bubble at every pass boundary — the last
 // burst of a row is consumed with nothing in flight, and the first burst of the next pass's row is requested only after the distance has been reduced and
 // handed over.  Here the next burst is ALWAYS in flight while the current one is consumed, across row boundaries too (its row pointer comes from the compacted
 // list in LDS).  Ping-pong buffers: no register moves.  Same lines, same order per row, same reduction: same bits.  Requires nl % U == 0, nl >= U.

@@ -1,10 +1,8 @@
 #!/usr/bin/env python3
 """A/B of the large-ef level-0 walk variants (coltt_amd/csrc/hnsw_walk2.hpp) on ONE index: COLTT_WALK2 = off (round-2 kernel) and
-every OPT x profile combination compiled into the library (all 16 with a -DCOLTT_WALK_EXPERIMENTS build:
-`COLTT_OUT=coltt_amd/variants/libcoltt_exp.so COLTT_OBJ=coltt_amd/variants/obj_exp COLTT_EXTRA_FLAGS=-DCOLTT_WALK_EXPERIMENTS
-python -m coltt_amd.build`, then COLTT_LIB=<that .so>).
+the variants the library carries (6: delta result set + adjacency-carried norms, 7: the same behind the Bloom filter).
 
-    python tools/walk_sweep.py [--n 10000000] [--quant 1] [--dataset lowrank:32:1.0] [--efs 256,1024] [--variants off,0,2,...]
+    python tools/walk_sweep.py [--n 10000000] [--quant 1] [--dataset lowrank:32:1.0] [--efs 256,1024] [--variants off,6,7]
 
 Every variant must return the SAME ids, score bits and traversal counters as the round-2 kernel (checked here, per ef); the
 table is kernel ms per launch of --queries queries (hipEvent pair on the search stream, best and median of --reps).
@@ -28,10 +26,10 @@ def main():
     ap.add_argument("--dataset", default="lowrank:32:1.0")
     ap.add_argument("--queries", type=int, default=10_000)
     ap.add_argument("--efs", default="256,1024")
-    ap.add_argument("--variants", default="off,0,1,2,3,4,5,6,7,8,10,14,15")
+    ap.add_argument("--variants", default="off,6,7")
     ap.add_argument("--bloom-kb", default="", help="comma list of COLTT_BLOOM_KB values tried for variants with the Bloom bit ('' = the library's choice)")
     ap.add_argument("--waves", default="", help="comma list of COLTT_WAVES_PER_CU values ('' = the library's choice)")
-    ap.add_argument("--env-var", default="COLTT_WALK2", help="COLTT_WALK2 (ef > 128: HBM visited map) or COLTT_WALK2_LDS (ef <= 128: off,2,4,6)")
+    ap.add_argument("--env-var", default="COLTT_WALK2", help="COLTT_WALK2 (ef > 128: HBM visited map) or COLTT_WALK2_LDS (ef <= 128: off,4)")
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
