@@ -448,6 +448,7 @@ struct Hnsw : Object {
   DevBuf w_visg, w_vepoch; uint64_t vis_stride = 0; uint32_t vis_regions = 0, vis_want = 0;
   std::mutex vis_mu; std::condition_variable vis_cv; std::vector<uint8_t> vis_busy;
   coltt_hnsw_stats build_stats{};
+  uint64_t gen = 0;   // bumped whenever the slots are renumbered (Load / bulk_load, a failed install): filters built before are stale
   ~Hnsw() override {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamDestroy(stream);
@@ -707,7 +708,8 @@ size_t waves_per_cu_cap(int quant);
 // COLTT_EV8=0: level-0 distances from the pair-owned rows even when the index carries the line-transposed copy (A/B and test knob)
 bool ev8_policy() { return policy().ev8; }
 
-SearchGeom search_geom(Hnsw* x, uint32_t ef, bool for_search = false, bool no_w2_lds = false) {
+// filt_k > 0: the filtered walk's allowed set (k rounded up to 64 entries) sits beside the result set (hnsw_kernels.hpp: search_one_wave)
+SearchGeom search_geom(Hnsw* x, uint32_t ef, bool for_search = false, bool no_w2_lds = false, uint32_t filt_k = 0) {
   SearchGeom s;
   s.ef = ef;
   s.ef_pad = (ef + 63) & ~63u;
@@ -717,7 +719,7 @@ SearchGeom search_geom(Hnsw* x, uint32_t ef, bool for_search = false, bool no_w2
   const bool vis_hbm = wants_visg(ef) && x->vis_stride != 0 && x->vis_regions > 0;
   const bool want8 = for_search && x->r8 && x->n > 0 && ev8_policy() && x->cfg.m_max0 <= 1024 &&
                      (vis_hbm ? (walk2_policy() == 6 || walk2_policy() == 7) : (!no_w2_lds && walk2_lds_policy() == 4));
-  const size_t fixed = qbytes + (want8 ? 96 * 4 : 0) + (size_t)s.ef_pad * 8;   // query (+ the eight-lane core's scratch) + result set (merged in place)
+  const size_t fixed = qbytes + (want8 ? 96 * 4 : 0) + (size_t)s.ef_pad * 8 + (size_t)((filt_k + 63) & ~63u) * 8;   // query (+ the eight-lane core's scratch) + result set (merged in place) (+ the allowed set)
   // LDS visited set: sized so that a typical traversal (a few dozen evaluations per result slot) never resets
   s.hcap = std::min<uint32_t>(32768u, std::max<uint32_t>(8192u, next_pow2(ef * 48u)));
   // large ef x dim: shrink it until the wave's state fits the CU's 160 KiB (the reset-and-reseed path keeps results exact;
@@ -1465,6 +1467,7 @@ int fill_adj_norms(Hnsw* x) {
 
 // A failed (re)load must not leave a half-installed index behind: fall back to the empty index (memory-safe, searchable).
 void make_empty(Hnsw* x) {
+  x->gen++;
   x->n = 0; x->live = 0; x->n_upper = 0; x->entry = -1; x->entry_level = 0; x->any_deleted = false; x->pq_done = 0;
   x->h_levels.clear(); x->h_upper_off.clear(); x->h_del.clear(); x->h_ids.clear(); x->id2slot.clear();
   x->dense = true; x->dense_base = 0;
@@ -1475,6 +1478,7 @@ void make_empty(Hnsw* x) {
 // nothing but a device failure can go wrong, and a device failure leaves an EMPTY index, never a half-installed one.
 int graph_install(Hnsw* x, const coltt_hnsw_cfg& c, uint64_t n, const uint64_t* ids, const int32_t* levels, const uint8_t* deleted,
                   const int64_t* row_offsets, const int32_t* nbr, const float* nbr_dist, int32_t entry_slot) {
+  x->gen++;   // the slots are about to be renumbered
   if (n >= 0x7fffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_bulk_load: more than 2^31-1 slots");
   if (n && (entry_slot < -1 || entry_slot >= (int64_t)n)) return fail(COLTT_E_INVALID, "hnsw_bulk_load: entry slot out of range");
   const uint32_t W0 = (uint32_t)c.m_max0, WU = (uint32_t)c.m_max;
@@ -2220,6 +2224,219 @@ int coltt_last_kernel_ms(coltt_handle_t h, float* out_ms) {
   if (!out_ms) return fail(COLTT_E_INVALID, "last_kernel_ms: NULL out");
   if (auto x = lookup<Hnsw>(h)) { *out_ms = x->last_ms.load(); return COLTT_OK; }
   return coltt_last_kernel_ms_flat(h, out_ms);
+}
+
+}  // extern "C"
+
+// ---- Filtered search: an allow-list of ids against one index (coltt_hnsw_filter_*, coltt_hnsw_search_filtered) ----------------------
+// An extension the reference does not have (its Core.HybridSearch post-filters an unfiltered search): definitions in include/coltt_gpu.h.
+namespace {
+
+struct HnswFilter : Object {
+  coltt_handle_t index = 0; uint64_t gen = 0;   // built against this index at this generation (Hnsw::gen)
+  uint32_t slots = 0;                           // the index's slots when the filter was built: the bitmap covers [0, slots)
+  uint64_t allowed = 0;
+  DevBuf bits;   // [ceil(slots / 32)] u32, bit s = slot s allowed
+  DevBuf list;   // [allowed] u32, the allowed slots ascending (the exact path's gather list)
+  ~HnswFilter() override { (void)hipSetDevice(device); }
+};
+
+// AUTO: with A allowed vertices out of n_live, a walk at ef meets about ef * A / n_live allowed ones among its result-set-sized share of
+// the walk; ef_need raises the breadth so that about ef of them are met.  The exact scan reads A rows and has no dependent chain; the walk
+// evaluates about 32 rows per unit of ef (n_dist / ef = 4 040 / 128 on the headline collection), so the scan wins on rows read while
+// A <= FILTER_ROWS_PER_EF * ef_walk.
+constexpr uint64_t FILTER_EF_MAX = 4096;
+#ifndef COLTT_FILTER_ROWS_PER_EF
+#define COLTT_FILTER_ROWS_PER_EF 32
+#endif
+int filter_path(uint64_t allowed, uint64_t n_live, uint32_t ef, int mode, uint32_t& ef_walk) {
+  ef_walk = ef;
+  if (mode == COLTT_FILTER_WALK) return COLTT_FILTER_WALK;
+  if (mode == COLTT_FILTER_EXACT || allowed == 0) return COLTT_FILTER_EXACT;
+  const uint64_t ef_need = ((uint64_t)ef * n_live + allowed - 1) / allowed;
+  ef_walk = (uint32_t)std::min<uint64_t>(FILTER_EF_MAX, std::max<uint64_t>(ef, ef_need));
+  if (ef_need > FILTER_EF_MAX || allowed <= (uint64_t)COLTT_FILTER_ROWS_PER_EF * ef_walk) return COLTT_FILTER_EXACT;
+  return COLTT_FILTER_WALK;
+}
+
+template <int METRIC, int QUANT>
+int launch_search_filtered(Hnsw* x, HCtx* c, const SearchGeom& sg, const HnswFilter* f, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k,
+                           uint32_t* counter, uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
+  auto kern = sg.visg ? hnsw_search_filtered_kernel<METRIC, QUANT, true> : hnsw_search_filtered_kernel<METRIC, QUANT, false>;
+  if constexpr (QUANT != Q_F8) { if (x->r8) kern = sg.visg ? hnsw_search_filtered_kernel<METRIC, QUANT, true, true> : hnsw_search_filtered_kernel<METRIC, QUANT, false, true>; }
+  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
+  kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
+                                        k, sg.ef, sg.ef_pad, sg.hcap, counter, oi, os, oc, stats,
+                                        x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
+                                        x->w_vepoch.as<uint32_t>() + region_base, FilterView{f->bits.as<uint32_t>(), f->slots});
+  COLTT_HIP(hipGetLastError());
+  return COLTT_OK;
+}
+
+template <int METRIC, int QUANT>
+int launch_filter_exact(Hnsw* x, HCtx* c, const HnswFilter* f, uint32_t nq, uint32_t k, uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
+  // geometry: up to FILT_QG queries per wave while the wave's LDS (queries + one top-k each) stays within 64 KiB (two waves per SIMD);
+  // enough (group, chunk) waves to fill the device (4096), chunks of >= 256 slots
+  const size_t qbytes = (((size_t)x->dim + 3) & ~(size_t)3) * 4, kbytes = (size_t)((k + 63) & ~63u) * 8;
+  uint32_t qg = FILT_QG;
+  while (qg > 1 && qg * (qbytes + kbytes) > 64 * 1024) qg--;
+  const size_t lds = qg * (qbytes + kbytes);
+  if (lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered: dim %u / k %u need %zu B of LDS (> 160 KiB)", x->dim, k, lds);
+  const uint32_t groups = ceil_div(nq, qg);
+  const uint64_t A = f->allowed;
+  uint64_t nchunks = std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(4096, groups), ceil_div(A, 256)));
+  while (nchunks > 1 && (uint64_t)nq * nchunks * k * 8 > (256ull << 20)) nchunks = (nchunks + 1) / 2;   // the chunk lists' workspace
+  uint64_t chunk = (A + nchunks - 1) / nchunks;
+  chunk = (chunk + 31) & ~31ull;
+  nchunks = (A + chunk - 1) / chunk;
+  COLTT_TRY(c->w_keys.reserve((size_t)nq * nchunks * k * 8));
+  COLTT_TRY(c->w_scnt.reserve((size_t)nq * nchunks * 4));
+  GraphView gv = x->view();
+  auto scan = hnsw_filter_scan_kernel<METRIC, QUANT, false>;
+  if constexpr (QUANT != Q_F8) { if (x->r8) scan = hnsw_filter_scan_kernel<METRIC, QUANT, true>; }
+  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  scan<<<dim3((uint32_t)nchunks, groups), 64, lds, c->stream>>>(gv, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq, qg, f->list.as<uint32_t>(), (uint32_t)A,
+                                                                (uint32_t)chunk, k, (k + 63) & ~63u, c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), stats);
+  COLTT_HIP(hipGetLastError());
+  const size_t lds2 = kbytes;
+  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_filter_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+  hnsw_filter_select_kernel<<<nq, 64, lds2, c->stream>>>(c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), (uint32_t)nchunks, k, gv.ids, oi, os, oc);
+  COLTT_HIP(hipGetLastError());
+  return COLTT_OK;
+}
+
+int filter_search_common(Hnsw* x, HCtx* c, const HnswFilter* f, const float* queries, size_t nq, uint32_t k, uint32_t ef_override, int mode,
+                         uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_filter_stats* st) {
+  coltt_hnsw_filter_stats local{};
+  if (!st) st = &local;
+  std::memset(st, 0, sizeof(*st));
+  if (mode != COLTT_FILTER_AUTO && mode != COLTT_FILTER_WALK && mode != COLTT_FILTER_EXACT) return fail(COLTT_E_INVALID, "hnsw_search_filtered: unknown mode %d", mode);
+  if (nq == 0) return COLTT_OK;
+  if (k == 0) return fail(COLTT_E_INVALID, "hnsw_search_filtered: k must be >= 1");
+  if (nq > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered: more than 2^32-1 queries in one call");
+  const uint32_t ef = std::max<uint32_t>(ef_override ? ef_override : (uint32_t)x->cfg.ef, k);   // as Search (hnsw.go:258)
+  if (ef > FILTER_EF_MAX) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered: ef=%u > %llu", ef, (unsigned long long)FILTER_EF_MAX);
+  uint32_t ef_walk = ef;
+  const int path = filter_path(f->allowed, x->live, ef, mode, ef_walk);
+  st->path = path; st->ef_walk = path == COLTT_FILTER_WALK ? ef_walk : 0;
+  if (x->entry < 0 || f->allowed == 0) {   // empty index or empty filter: counts 0, not an error
+    std::memset(out_counts, 0, nq * 4);
+    return COLTT_OK;
+  }
+  COLTT_TRY(c->w_out_ids.reserve(nq * k * 8));
+  COLTT_TRY(c->w_out_sc.reserve(nq * k * 4));
+  COLTT_TRY(c->w_out_cnt.reserve(nq * 4));
+  uint64_t* d_oi = c->w_out_ids.as<uint64_t>(); float* d_os = c->w_out_sc.as<float>(); uint32_t* d_oc = c->w_out_cnt.as<uint32_t>();
+  SearchGeom sg{};
+  uint32_t grid = 0;
+  RegionLease lease;
+  if (path == COLTT_FILTER_WALK) {
+    if (wants_visg(ef_walk)) COLTT_TRY(ensure_visg(x));
+    sg = search_geom(x, ef_walk, false, true, k);   // the one-wave walk (hnsw_dev.hpp: search_level) over the LDS hash or the HBM byte map
+    if (sg.lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered: dim/ef/k need %zu B of LDS (> 160 KiB)", sg.lds);
+    grid = std::min<uint32_t>((uint32_t)nq, resident_waves(sg, x->quant));
+    if (sg.visg) { acquire_regions(x, grid, lease); grid = lease.count; }
+  }
+  COLTT_TRY(c->w_qraw.reserve(nq * x->dim * 4));
+  COLTT_HIP(hipMemcpyAsync(c->w_qraw.p, queries, nq * x->dim * 4, hipMemcpyHostToDevice, c->stream));
+  COLTT_TRY(c->w_misc.reserve(256));
+  COLTT_TRY(c->h_out.reserve(256));
+  uint8_t* misc = c->w_misc.as<uint8_t>();
+  uint32_t* counter = reinterpret_cast<uint32_t*>(misc);
+  unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(misc + 16);
+  COLTT_TRY(prep_queries_any(x, c, c->w_qraw.as<float>(), nq, reinterpret_cast<uint32_t*>(misc)));   // Normalize / Lower the queries as Search does; clears the counters
+  COLTT_HIP(hipEventRecord(c->ev0, c->stream));
+  int rc = COLTT_OK;
+#define COLTT_FS(Q) rc = path == COLTT_FILTER_WALK \
+    ? (x->metric == COLTT_COSINE ? launch_search_filtered<M_COS, Q>(x, c, sg, f, grid, lease.base, (uint32_t)nq, k, counter, d_oi, d_os, d_oc, d_stats) \
+                                 : launch_search_filtered<M_L2, Q>(x, c, sg, f, grid, lease.base, (uint32_t)nq, k, counter, d_oi, d_os, d_oc, d_stats)) \
+    : (x->metric == COLTT_COSINE ? launch_filter_exact<M_COS, Q>(x, c, f, (uint32_t)nq, k, d_oi, d_os, d_oc, d_stats) \
+                                 : launch_filter_exact<M_L2, Q>(x, c, f, (uint32_t)nq, k, d_oi, d_os, d_oc, d_stats))
+  COLTT_DISPATCH_QUANT(x->quant, COLTT_FS)
+#undef COLTT_FS
+  COLTT_TRY(rc);
+  COLTT_HIP(hipEventRecord(c->ev1, c->stream));
+  if (x->dense && x->dense_base) add_base_kernel<<<ceil_div(nq * k, 256), 256, 0, c->stream>>>(d_oi, nq * k, x->dense_base);
+  COLTT_HIP(hipMemcpyAsync(out_ids, d_oi, nq * k * 8, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipMemcpyAsync(out_scores, d_os, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipMemcpyAsync(out_counts, d_oc, nq * 4, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 48, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipStreamSynchronize(c->stream));   // the lease (destructor) outlives the kernel
+  unsigned long long h_stats[6];
+  std::memcpy(h_stats, c->h_out.p, 48);
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+  x->last_ms.store(ms);
+  if (h_stats[4]) return fail(COLTT_E_DEVICE, "hnsw_search_filtered: traversal watchdog tripped (code %llu)", h_stats[4]);
+  st->n_dist = h_stats[0]; st->n_exp = h_stats[1]; st->n_hops = h_stats[2]; st->n_visit_resets = h_stats[3]; st->n_exact_rows = h_stats[5];
+  return COLTT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int coltt_hnsw_filter_create(coltt_handle_t h, const uint64_t* ids, size_t n, uint64_t* out_allowed, coltt_handle_t* out) {
+  if (!out) return fail(COLTT_E_INVALID, "hnsw_filter_create: out is NULL");
+  if (n && !ids) return fail(COLTT_E_INVALID, "hnsw_filter_create: NULL ids");
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_filter_create: unknown index handle");
+  ReadLock g(x->rw);
+  COLTT_DEVICE(x->device);
+  auto f = std::make_shared<HnswFilter>();
+  f->device = x->device; f->index = h; f->gen = x->gen; f->slots = (uint32_t)x->n;
+  std::vector<uint32_t> words(((size_t)x->n + 31) / 32, 0u);
+  for (size_t i = 0; i < n; i++) {   // ids -> live slots; unknown / removed ids are ignored, duplicates count once
+    const uint64_t id = ids[i];
+    uint32_t s;
+    if (x->dense) {
+      if (id < x->dense_base || id - x->dense_base >= x->n) continue;
+      s = (uint32_t)(id - x->dense_base);
+      if (x->h_del.size() > (s >> 5) && ((x->h_del[s >> 5] >> (s & 31)) & 1u)) continue;
+    } else {
+      auto it = x->id2slot.find(id);
+      if (it == x->id2slot.end()) continue;
+      s = it->second;
+    }
+    words[s >> 5] |= 1u << (s & 31);
+  }
+  std::vector<uint32_t> list;
+  for (size_t w = 0; w < words.size(); w++)
+    for (uint32_t b = words[w]; b; b &= b - 1) list.push_back((uint32_t)(w * 32 + __builtin_ctz(b)));
+  f->allowed = list.size();
+  if (!words.empty()) {
+    COLTT_TRY(f->bits.reserve(words.size() * 4));
+    COLTT_HIP(hipMemcpy(f->bits.p, words.data(), words.size() * 4, hipMemcpyHostToDevice));
+  }
+  if (!list.empty()) {
+    COLTT_TRY(f->list.reserve(list.size() * 4));
+    COLTT_HIP(hipMemcpy(f->list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice));
+  }
+  if (out_allowed) *out_allowed = f->allowed;
+  *out = Registry::get().add(f);
+  return COLTT_OK;
+}
+
+int coltt_hnsw_filter_destroy(coltt_handle_t fh) {
+  if (!lookup<HnswFilter>(fh)) return fail(COLTT_E_NOT_FOUND, "hnsw_filter_destroy: unknown filter handle");
+  Registry::get().erase(fh);
+  return COLTT_OK;
+}
+
+int coltt_hnsw_search_filtered(coltt_handle_t h, coltt_handle_t fh, const float* queries, size_t nq, uint32_t k, uint32_t ef_override, int mode,
+                               uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_filter_stats* stats) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_search_filtered: unknown index handle");
+  auto f = lookup<HnswFilter>(fh);
+  if (!f) return fail(COLTT_E_NOT_FOUND, "hnsw_search_filtered: unknown filter handle");
+  if (nq && (!queries || !out_ids || !out_scores || !out_counts)) return fail(COLTT_E_INVALID, "hnsw_search_filtered: NULL buffer");
+  if (f->index != h) return fail(COLTT_E_INVALID, "hnsw_search_filtered: the filter was built for another index");
+  ReadLock g(x->rw);
+  if (f->gen != x->gen) return fail(COLTT_E_INVALID, "hnsw_search_filtered: the filter is stale (the index was loaded since it was built)");
+  COLTT_DEVICE(x->device);
+  CtxLease<HCtx> ctx(x->pool);
+  if (!ctx.c) return COLTT_E_DEVICE;
+  return filter_search_common(x.get(), ctx.c, f.get(), queries, nq, k, ef_override, mode, out_ids, out_scores, out_counts, stats);
 }
 
 }  // extern "C"

@@ -199,11 +199,72 @@ __device__ __forceinline__ void vis_reset(WaveCtx& w, const unsigned long long* 
   wave_sync();
 }
 
+// Filtered search (coltt_hnsw_search_filtered): the allow-list as the kernels see it — one bit per slot of the index at the time the
+// filter was built; slots at or past `slots` (vertices inserted later) are not allowed.
+struct FilterView { const uint32_t* bits; uint32_t slots; };
+__device__ __forceinline__ bool filter_allows(const FilterView& f, uint32_t slot) {
+  return slot < f.slots && ((f.bits[slot >> 5] >> (slot & 31)) & 1u);
+}
+// The allowed set R of a filtered walk: the cap smallest keys (d bits << 32 | slot << 1, the result set's layout) of the live allowed
+// vertices whose distance the level-0 walk holds.  r[0..len) ascending, in LDS beside the result set.
+struct FiltSet { unsigned long long* r; uint32_t len, cap; FilterView f; };
+
+// Offer each lane's key (where `take`) to the sorted LDS array a[0..len) of capacity cap >= 1 and keep the cap smallest: a pure top-k,
+// independent of the order in which keys arrive.  The keys offered by one call are distinct; `dedup`: a key the array already holds is
+// not taken again (the visited-reset path can evaluate a vertex twice).  The merge is the result set's (search_level): ranks among
+// the offered keys by readlane, insertion points by binary search, members shifted in place from the tail down.  len is wave-uniform.
+__device__ __forceinline__ void sorted_offer(unsigned long long* a, uint32_t& len, uint32_t cap, bool take, unsigned long long key,
+                                             int lane, bool dedup) {
+  const unsigned long long worst = len >= cap ? a[cap - 1] : ~0ull;
+  take = take && key < worst;   // |a| < cap || key < a.worst: nothing else can enter
+  if (!__ballot(take)) return;
+  uint32_t mypos = 0xffffffffu;
+  if (take) {
+    uint32_t lo = 0, hi = len;
+    while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (a[mid] < key) lo = mid + 1; else hi = mid; }
+    mypos = lo;
+    if (dedup && lo < len && a[lo] == key) take = false;
+  }
+  const unsigned long long A = __ballot(take);
+  if (!A) return;
+  const uint32_t m = __popcll(A);
+  uint32_t myrank = 0;
+  {
+    unsigned long long am = A;
+    while (am) {
+      int j = __builtin_ctzll(am); am &= am - 1;
+      myrank += (readlane_u64(key, j) < key) ? 1u : 0u;
+    }
+  }
+  const uint32_t minpos = (uint32_t)__builtin_amdgcn_readlane((int)mypos, __builtin_ctzll(__ballot(take && myrank == 0)));
+  wave_sync();
+  if (len) {
+    for (int base = (int)((len - 1) & ~63u); base >= (int)(minpos & ~63u); base -= 64) {
+      const uint32_t i = (uint32_t)base + lane;
+      const unsigned long long e = i < len ? a[i] : ~0ull;
+      uint32_t shift = 0;
+      unsigned long long am = A;
+      while (am) {
+        int j = __builtin_ctzll(am); am &= am - 1;
+        shift += ((uint32_t)__builtin_amdgcn_readlane((int)mypos, j) <= i) ? 1u : 0u;
+      }
+      wave_sync();
+      const uint32_t np = i + shift;
+      if (i < len && shift && np < cap) a[np] = e;
+    }
+  }
+  wave_sync();
+  if (take && mypos + myrank < cap) a[mypos + myrank] = key;
+  len = len + m < cap ? len + m : cap;
+  wave_sync();
+}
+
 // searchLevel (hnsw.go:345-389).  On return w.res[buf][0..len) holds the result set ascending by (d, slot).
 // The wave must be the only one in its workgroup (wave_sync is a wave-level LDS fence).
-template <int METRIC, int QUANT, bool VISG, int PROFILE, bool R8 = false>
+// FILTER: the filtered walk — the same walk, plus every live allowed vertex it evaluates is offered to *fs (FiltSet above).
+template <int METRIC, int QUANT, bool VISG, int PROFILE, bool R8 = false, bool FILTER = false>
 __device__ __forceinline__ void search_level(const GraphView& g, WaveCtx& w, uint32_t ep, float epd, uint32_t ef,
-                                             int level, int lane_in, uint32_t& out_len, int& out_buf) {
+                                             int level, int lane_in, uint32_t& out_len, int& out_buf, FiltSet* fs = nullptr) {
   int lane = lane_in;
   if constexpr (VISG) {
     if (++w.epoch > 255u) {  // 8-bit epoch wrapped: wipe the region (once per 255 traversals)
@@ -218,6 +279,11 @@ __device__ __forceinline__ void search_level(const GraphView& g, WaveCtx& w, uin
   if (lane == 0) {
     if constexpr (VISG) __hip_atomic_store(w.visg + ep, (uint8_t)w.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else vis_insert(w.vis, w.hcap_mask, ep);
+  }
+  if constexpr (FILTER) {   // the level-0 entry point (the greedy descent only moves to live vertices; tested anyway)
+    fs->len = 0;
+    sorted_offer(fs->r, fs->len, fs->cap, lane == 0 && filter_allows(fs->f, ep) && !is_deleted(g, ep),
+                 ((unsigned long long)__float_as_uint(epd) << 32) | ((unsigned long long)ep << 1), lane, false);
   }
   uint32_t len = 1, vis_count = 1;
   uint32_t scan_lo = 0;   // every member before this index is expanded (pop scans start at its 64-entry chunk)
@@ -298,7 +364,9 @@ __device__ __forceinline__ void search_level(const GraphView& g, WaveCtx& w, uin
 #endif
       COLTT_PT(w, 1)  // adjacency row
       int fresh_i = 0;
+      uint32_t fword = 0;   // FILTER: the neighbour's allow-list word, requested beside the visited probe so its latency hides under it
       if (valid && half == 0) {
+        if constexpr (FILTER) fword = nb < fs->f.slots ? fs->f.bits[nb >> 5] : 0u;
         if constexpr (VISG) {
           // No two lanes hold the same slot (a row lists a neighbour once), so load + store is a race-free test-and-set.
           // Agent-scope atomics: served by L2, never by a stale L1 line; the store is complete (vmcnt) before the next
@@ -332,6 +400,10 @@ __device__ __forceinline__ void search_level(const GraphView& g, WaveCtx& w, uin
       vis_count += nfresh; w.n_dist += nfresh;
       float d = 0.f;
       if (fresh) d = eval_pair<METRIC, QUANT, PROFILE, R8>(g, w, nb, half);
+      if constexpr (FILTER) {   // every evaluated live allowed neighbour, admitted to the walk or not; after a visited reset a key may come twice
+        const bool al = fresh && half == 0 && ((fword >> (nb & 31)) & 1u);
+        sorted_offer(fs->r, fs->len, fs->cap, al, ((unsigned long long)__float_as_uint(d) << 32) | ((unsigned long long)nb << 1), lane, had_reset);
+      }
       uint32_t rank = __popcll(E & lt_mask);
       bool adm = fresh && half == 0 && (rank < free_slots || d < lower_bound);
 #ifdef COLTT_PHASE_TIMING

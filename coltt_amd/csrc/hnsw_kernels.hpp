@@ -14,23 +14,27 @@ namespace coltt {
 namespace kern {
 using namespace coltt::dev;
 
-// Hnsw.Search (hnsw.go:243-278) for a batch: one wave per query, queries pulled from a global counter.
-template <int METRIC, int QUANT, bool VISG, bool R8 = false>   // R8: the index's ONE row array is line-transposed (rows8.hpp)
-__global__ __launch_bounds__(64) void hnsw_search_kernel(GraphView g, int32_t entry, int32_t entry_level,
-                                                        const float* __restrict__ q_eff, const float* __restrict__ qnorms,
-                                                        uint32_t nq, uint32_t k, uint32_t ef, uint32_t ef_pad, uint32_t hcap,
-                                                        uint32_t* __restrict__ counter, uint64_t* __restrict__ out_ids,
-                                                        float* __restrict__ out_scores, uint32_t* __restrict__ out_counts,
-                                                        unsigned long long* __restrict__ stats, uint8_t* __restrict__ visg,
-                                                        size_t vis_stride, uint32_t* __restrict__ vis_epoch) {
+// Hnsw.Search (hnsw.go:243-278) for a batch: one wave per query, queries pulled from a global counter.  The body of hnsw_search_kernel and
+// hnsw_search_filtered_kernel.  FILTER (coltt_hnsw_search_filtered, WALK): the same walk, plus the allowed set R (hnsw_dev.hpp: FiltSet) of
+// k_pad = k rounded up to 64 entries in LDS between the result set and the visited hash; the answer is R instead of the walk's k nearest.
+template <int METRIC, int QUANT, bool VISG, bool R8, bool FILTER>
+__device__ __forceinline__ void search_one_wave(uint8_t* smem, GraphView g, int32_t entry, int32_t entry_level,
+                                                const float* __restrict__ q_eff, const float* __restrict__ qnorms,
+                                                uint32_t nq, uint32_t k, uint32_t ef, uint32_t ef_pad, uint32_t hcap,
+                                                uint32_t* __restrict__ counter, uint64_t* __restrict__ out_ids,
+                                                float* __restrict__ out_scores, uint32_t* __restrict__ out_counts,
+                                                unsigned long long* __restrict__ stats, uint8_t* __restrict__ visg,
+                                                size_t vis_stride, uint32_t* __restrict__ vis_epoch, FilterView fv) {
   constexpr int PROF = VISG ? PROF_SEARCH_HBM : PROF_SEARCH_LDS;
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x;
   WaveCtx w;
   size_t off = ((size_t)g.dim * 4 + 15) & ~(size_t)15;
   w.qs = reinterpret_cast<float*>(smem);
   w.res0 = reinterpret_cast<unsigned long long*>(smem + off);
-  w.vis = reinterpret_cast<uint32_t*>(w.res0 + (size_t)ef_pad);
+  FiltSet fs;
+  uint32_t k_pad = 0;
+  if constexpr (FILTER) { k_pad = (k + 63) & ~63u; fs.r = w.res0 + (size_t)ef_pad; fs.len = 0; fs.cap = k; fs.f = fv; }
+  w.vis = reinterpret_cast<uint32_t*>(w.res0 + (size_t)ef_pad + k_pad);
   w.ef_pad = ef_pad; w.hcap = hcap; w.hcap_mask = hcap - 1;
   w.visg = nullptr; w.vis_bytes = 0; w.epoch = 0;
   if constexpr (VISG) { w.visg = visg + (size_t)blockIdx.x * vis_stride; w.vis_bytes = vis_stride; w.epoch = vis_epoch[blockIdx.x]; }
@@ -60,10 +64,11 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(GraphView g, int32_t en
     // searchLevel re-evaluates the entrypoint distance (hnsw.go:346)
     w.n_dist += 1;
     uint32_t len; int buf;
-    search_level<METRIC, QUANT, VISG, PROF, R8>(g, w, cur, curd, ef, 0, lane, len, buf);  // :258-259
+    search_level<METRIC, QUANT, VISG, PROF, R8, FILTER>(g, w, cur, curd, ef, 0, lane, len, buf, &fs);  // :258-259
     // selectNeighbors + pop into result[n-1..0] (:261-277) == the k smallest, ascending
     uint32_t n = len < k ? len : k;
     const unsigned long long* res = w.res0 + (size_t)buf * ef_pad;
+    if constexpr (FILTER) { n = fs.len; res = fs.r; }   // filtered: R, ascending
     for (uint32_t i = lane; i < n; i += 64) {
       unsigned long long e = res[i];
       uint32_t slot = (uint32_t)e >> 1;
@@ -84,6 +89,31 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(GraphView g, int32_t en
     }
   }
   if constexpr (VISG) { if (lane == 0) vis_epoch[blockIdx.x] = w.epoch; }
+}
+template <int METRIC, int QUANT, bool VISG, bool R8 = false>   // R8: the index's ONE row array is line-transposed (rows8.hpp)
+__global__ __launch_bounds__(64) void hnsw_search_kernel(GraphView g, int32_t entry, int32_t entry_level,
+                                                        const float* __restrict__ q_eff, const float* __restrict__ qnorms,
+                                                        uint32_t nq, uint32_t k, uint32_t ef, uint32_t ef_pad, uint32_t hcap,
+                                                        uint32_t* __restrict__ counter, uint64_t* __restrict__ out_ids,
+                                                        float* __restrict__ out_scores, uint32_t* __restrict__ out_counts,
+                                                        unsigned long long* __restrict__ stats, uint8_t* __restrict__ visg,
+                                                        size_t vis_stride, uint32_t* __restrict__ vis_epoch) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  search_one_wave<METRIC, QUANT, VISG, R8, false>(smem, g, entry, entry_level, q_eff, qnorms, nq, k, ef, ef_pad, hcap, counter, out_ids, out_scores,
+                                                  out_counts, stats, visg, vis_stride, vis_epoch, FilterView{nullptr, 0u});
+}
+// coltt_hnsw_search_filtered, WALK: the one-wave walk with the allowed set (its own instances: the unfiltered ones stay as they are)
+template <int METRIC, int QUANT, bool VISG, bool R8 = false>
+__global__ __launch_bounds__(64) void hnsw_search_filtered_kernel(GraphView g, int32_t entry, int32_t entry_level,
+                                                                 const float* __restrict__ q_eff, const float* __restrict__ qnorms,
+                                                                 uint32_t nq, uint32_t k, uint32_t ef, uint32_t ef_pad, uint32_t hcap,
+                                                                 uint32_t* __restrict__ counter, uint64_t* __restrict__ out_ids,
+                                                                 float* __restrict__ out_scores, uint32_t* __restrict__ out_counts,
+                                                                 unsigned long long* __restrict__ stats, uint8_t* __restrict__ visg,
+                                                                 size_t vis_stride, uint32_t* __restrict__ vis_epoch, FilterView fv) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  search_one_wave<METRIC, QUANT, VISG, R8, true>(smem, g, entry, entry_level, q_eff, qnorms, nq, k, ef, ef_pad, hcap, counter, out_ids, out_scores,
+                                                 out_counts, stats, visg, vis_stride, vis_epoch, fv);
 }
 
 
@@ -422,6 +452,84 @@ __global__ __launch_bounds__(64) void hnsw_pq_select_kernel(const unsigned long 
     wave_sync();
   }
   if (lane_in == 0) out_counts[qi] = n;
+}
+
+// coltt_hnsw_search_filtered, EXACT: the k nearest live allowed vertices by (score bits, slot), over the filter's compacted slot list.
+// Step 1: one wave per (query group of <= FILT_QG queries, chunk of the list).  The group's queries sit in LDS; lane pair p scores slot
+// base + p against each of them in turn with the walk's own evaluator (exact.hpp pair core; over line-transposed rows the pair core that
+// reads them, pair_distance_r8 — same values, same order, same bits), so a row comes from HBM once per group and from the caches after.
+// Each query keeps the chunk's k smallest keys in LDS (hnsw_dev.hpp: sorted_offer); they go to part[q][chunk][0..cnt).
+constexpr uint32_t FILT_QG = 8;
+template <int METRIC, int QUANT, bool R8>
+__global__ __launch_bounds__(64) void hnsw_filter_scan_kernel(GraphView g, const float* __restrict__ q_eff, const float* __restrict__ qnorms, uint32_t nq,
+                                                              uint32_t qg, const uint32_t* __restrict__ slots, uint32_t n_slots, uint32_t chunk, uint32_t k,
+                                                              uint32_t k_pad, unsigned long long* __restrict__ part, uint32_t* __restrict__ part_cnt,
+                                                              unsigned long long* __restrict__ stats) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int lane_in = threadIdx.x;
+  const uint32_t q0 = blockIdx.y * qg, nchunks = gridDim.x;
+  const uint32_t nqg = nq - q0 < qg ? nq - q0 : qg;
+  const size_t qstride = ((size_t)g.dim + 3) & ~(size_t)3;
+  float* const qs = reinterpret_cast<float*>(smem);                                              // [qg][qstride]
+  unsigned long long* const top = reinterpret_cast<unsigned long long*>(qs + (size_t)qg * qstride);   // [qg][k_pad]
+  for (uint32_t j = 0; j < nqg; j++)
+    for (int e = lane_in; e < g.dim; e += 64) qs[(size_t)j * qstride + e] = q_eff[(size_t)(q0 + j) * g.dim + e];
+  wave_sync();
+  const uint32_t s0 = blockIdx.x * chunk, s1 = s0 + chunk < n_slots ? s0 + chunk : n_slots;
+  uint32_t lens[FILT_QG];
+#pragma unroll
+  for (uint32_t j = 0; j < FILT_QG; j++) lens[j] = 0;
+  unsigned long long rows = 0;
+  for (uint32_t base = s0; base < s1; base += 32) {
+    const int lane = opaque_lane(lane_in);
+    const int half = lane & 1, p = lane >> 1;
+    const uint32_t i = base + (uint32_t)p;
+    const bool valid = i < s1;
+    const uint32_t slot = slots[valid ? i : base];   // an idle pair re-evaluates a listed row (DPP partners stay active)
+    const bool live = valid && !is_deleted(g, slot);   // tombstones at search time
+    rows += __popcll(__ballot(live && half == 0));
+#pragma unroll
+    for (uint32_t j = 0; j < FILT_QG; j++) {
+      if (j >= nqg) break;   // wave-uniform
+      const float d = eval_pair_q<METRIC, QUANT, PROF_SEARCH_HBM, R8>(g, qs + (size_t)j * qstride, qnorms[q0 + j], slot, half);
+      sorted_offer(top + (size_t)j * k_pad, lens[j], k, live && half == 0, ((unsigned long long)__float_as_uint(d) << 32) | ((unsigned long long)slot << 1),
+                   lane, false);
+    }
+  }
+#pragma unroll
+  for (uint32_t j = 0; j < FILT_QG; j++) {
+    if (j >= nqg) break;
+    const size_t q = q0 + j;
+    for (uint32_t i = (uint32_t)lane_in; i < lens[j]; i += 64) part[(q * nchunks + blockIdx.x) * k + i] = top[(size_t)j * k_pad + i];
+    if (lane_in == 0) part_cnt[q * nchunks + blockIdx.x] = lens[j];
+  }
+  if (lane_in == 0 && rows) atomicAdd(&stats[5], rows * nqg);
+}
+// step 2: one wave per query merges its chunks' lists (the same top-k in LDS) and writes the answer ascending
+__global__ __launch_bounds__(64) void hnsw_filter_select_kernel(const unsigned long long* __restrict__ part, const uint32_t* __restrict__ part_cnt,
+                                                                uint32_t nchunks, uint32_t k, const uint64_t* __restrict__ ids, uint64_t* __restrict__ out_ids,
+                                                                float* __restrict__ out_scores, uint32_t* __restrict__ out_counts) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  unsigned long long* const top = reinterpret_cast<unsigned long long*>(smem);
+  const size_t q = blockIdx.x;
+  const int lane_in = threadIdx.x;
+  uint32_t len = 0;
+  for (uint32_t c = 0; c < nchunks; c++) {
+    const uint32_t cnt = part_cnt[q * nchunks + c];
+    const unsigned long long* src = part + (q * nchunks + c) * k;
+    for (uint32_t b = 0; b < cnt; b += 64) {
+      const int lane = opaque_lane(lane_in);
+      const bool take = b + (uint32_t)lane < cnt;
+      sorted_offer(top, len, k, take, take ? src[b + lane] : ~0ull, lane, false);
+    }
+  }
+  for (uint32_t i = (uint32_t)lane_in; i < len; i += 64) {
+    const unsigned long long e = top[i];
+    const uint32_t slot = (uint32_t)e >> 1;
+    out_ids[q * k + i] = ids ? ids[slot] : (uint64_t)slot;
+    out_scores[q * k + i] = __uint_as_float((uint32_t)(e >> 32));
+  }
+  if (lane_in == 0) out_counts[q] = len;
 }
 
 }  // namespace kern

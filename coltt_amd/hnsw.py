@@ -24,6 +24,42 @@ class HnswStats(C.Structure):
     _fields_ = [("n_dist", C.c_uint64), ("n_exp", C.c_uint64), ("n_hops", C.c_uint64), ("n_visit_resets", C.c_uint64)]
 
 
+FILTER_AUTO, FILTER_WALK, FILTER_EXACT = 0, 1, 2
+
+
+class HnswFilterStats(C.Structure):
+    _fields_ = [("n_dist", C.c_uint64), ("n_exp", C.c_uint64), ("n_hops", C.c_uint64), ("n_visit_resets", C.c_uint64),
+                ("ef_walk", C.c_uint32), ("path", C.c_int32), ("n_exact_rows", C.c_uint64)]
+
+
+class HnswFilter:
+    """An allow-list of ids against one index (coltt_hnsw_filter_create; include/coltt_gpu.h, "Filtered HNSW search" — an extension the
+    reference does not have).  `.allowed` = the live vertices it allows."""
+
+    def __init__(self, index, ids):
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
+        h = C.c_uint64(0); n = C.c_uint64(0)
+        L.check(L.lib().coltt_hnsw_filter_create(index.h, L.vp(a), C.c_size_t(a.size), C.byref(n), C.byref(h)))
+        self.h, self.allowed = h, n.value
+
+    def close(self):
+        if getattr(self, "h", None) is not None:
+            L.lib().coltt_hnsw_filter_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Hnsw:
     def __init__(self, dim, distance=L.COSINE, cfg=None, quantization=L.Q_NONE):
         self.dim, self.distance, self.quantization = int(dim), distance, quantization
@@ -120,6 +156,22 @@ class Hnsw:
                                           L.vp(cnt), C.byref(st)))
         if with_stats:
             return ids, sc, cnt, {"n_dist": st.n_dist, "n_exp": st.n_exp, "n_hops": st.n_hops, "n_visit_resets": st.n_visit_resets}
+        return ids, sc, cnt
+
+    # -- filtered search (an extension the reference does not have): the k nearest among the ids of `flt`
+    def Filter(self, ids):
+        return HnswFilter(self, ids)
+
+    def SearchFiltered(self, queries, k, flt, ef=0, mode=FILTER_AUTO, with_stats=False):
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        ids = np.zeros((nq, k), np.uint64); sc = np.zeros((nq, k), np.float32); cnt = np.zeros(nq, np.uint32)
+        st = HnswFilterStats()
+        L.check(L.lib().coltt_hnsw_search_filtered(self.h, flt.h, L.vp(q), C.c_size_t(nq), C.c_uint32(k), C.c_uint32(ef), C.c_int(int(mode)),
+                                                   L.vp(ids), L.vp(sc), L.vp(cnt), C.byref(st)))
+        if with_stats:
+            return ids, sc, cnt, {"n_dist": st.n_dist, "n_exp": st.n_exp, "n_hops": st.n_hops, "n_visit_resets": st.n_visit_resets,
+                                  "ef_walk": st.ef_walk, "path": st.path, "n_exact_rows": st.n_exact_rows}
         return ids, sc, cnt
 
     def SearchDevice(self, d_q, nq, k, d_ids, d_scores, d_counts, ef=0):

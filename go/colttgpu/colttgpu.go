@@ -170,6 +170,49 @@ func HnswSearch(h Handle, dim uint32, queries []float32, nq int, k uint32, ef ui
 	})
 	return ids, sc, cnt, err
 }
+// HnswFilterCreate: an allow-list of ids against index h (coltt_hnsw_filter_create — an extension the reference does not have);
+// returns the filter's handle and how many live vertices it allows.  Release it with HnswFilterDestroy.
+func HnswFilterCreate(h Handle, ids []uint64) (Handle, uint64, error) {
+	var f Handle
+	var allowed C.uint64_t
+	err := call(func() C.int {
+		var p *C.uint64_t
+		if len(ids) > 0 {
+			p = (*C.uint64_t)(unsafe.Pointer(&ids[0]))
+		}
+		return C.coltt_hnsw_filter_create(h, p, C.size_t(len(ids)), &allowed, &f)
+	})
+	return f, uint64(allowed), err
+}
+func HnswFilterDestroy(f Handle) error {
+	return call(func() C.int { return C.coltt_hnsw_filter_destroy(f) })
+}
+
+// Filter modes of HnswSearchFiltered (coltt_gpu.h: COLTT_FILTER_*)
+const (
+	FilterAuto  = 0
+	FilterWalk  = 1
+	FilterExact = 2
+)
+
+// HnswSearchFiltered: as HnswSearch, among the vertices filter f allows.
+func HnswSearchFiltered(h, f Handle, dim uint32, queries []float32, nq int, k uint32, ef uint32, mode int) ([]uint64, []float32, []uint32, error) {
+	if nq == 0 || k == 0 {
+		return nil, nil, make([]uint32, nq), nil
+	}
+	if err := checkDim(queries, dim, nq); err != nil {
+		return nil, nil, nil, err
+	}
+	ids := make([]uint64, nq*int(k))
+	sc := make([]float32, nq*int(k))
+	cnt := make([]uint32, nq)
+	err := call(func() C.int {
+		return C.coltt_hnsw_search_filtered(h, f, fptr(queries), C.size_t(nq), C.uint32_t(k), C.uint32_t(ef), C.int(mode), uptr(ids), fptr(sc),
+			(*C.uint32_t)(unsafe.Pointer(&cnt[0])), nil)
+	})
+	return ids, sc, cnt, err
+}
+
 func HnswRandomLevel(h Handle, u float32) (int, error) {
 	var lv C.int32_t
 	err := call(func() C.int { return C.coltt_hnsw_random_level(h, C.float(u), &lv) })

@@ -381,6 +381,49 @@ func (xx *Hnsw) Search(_ context.Context, query edge.Vector, k uint) (SearchResu
 	return xx.attach(ids, sc, int(cnt[0])), nil
 }
 
+// HnswFilter — an allow-list of ids for SearchFiltered.  NOT reference behaviour: the reference has no filtered HNSW search (its
+// Core.HybridSearch post-filters an unfiltered one, core/core.go:760-836).  Built against one index; ids inserted later are not allowed,
+// removed ones are never returned; a Load makes it stale (SearchFiltered then fails).  Close releases its device memory.
+type HnswFilter struct {
+	h       colttgpu.Handle
+	index   *Hnsw
+	Allowed uint64 // live vertices the filter allows
+}
+
+// NewFilter builds a filter from ids (unknown / removed ids are ignored, duplicates count once).
+func (xx *Hnsw) NewFilter(ids []uint64) (*HnswFilter, error) {
+	if xx.err != nil {
+		return nil, xx.err
+	}
+	f, n, err := colttgpu.HnswFilterCreate(xx.h, ids)
+	if err != nil {
+		return nil, err
+	}
+	return &HnswFilter{h: f, index: xx, Allowed: n}, nil
+}
+
+func (f *HnswFilter) Close() error {
+	if f.h == 0 {
+		return nil
+	}
+	err := colttgpu.HnswFilterDestroy(f.h)
+	f.h = 0
+	return err
+}
+
+// SearchFiltered(ctx, query, k, f) — the k nearest among the vertices f allows (the library's AUTO path: a filtered walk, or an exact
+// scan of the allowed rows when the filter is selective).
+func (xx *Hnsw) SearchFiltered(_ context.Context, query edge.Vector, k uint, f *HnswFilter) (SearchResult, error) {
+	if xx.err != nil {
+		return nil, xx.err
+	}
+	ids, sc, cnt, err := colttgpu.HnswSearchFiltered(xx.h, f.h, uint32(xx.dim), query, 1, uint32(k), 0, colttgpu.FilterAuto)
+	if err != nil {
+		return nil, err
+	}
+	return xx.attach(ids, sc, int(cnt[0])), nil
+}
+
 func (xx *Hnsw) attach(ids []uint64, sc []float32, n int) SearchResult {
 	res := make(SearchResult, n)
 	for i := 0; i < n; i++ {

@@ -216,6 +216,52 @@ int coltt_hnsw_search(coltt_handle_t h, const float* queries, size_t nq, uint32_
                       uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_stats* stats);
 int coltt_hnsw_search_device(coltt_handle_t h, const float* d_queries, size_t nq, uint32_t k, uint32_t ef_override,
                              uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_counts, coltt_hnsw_stats* stats);
+/* ---- Filtered HNSW search: an allow-list of ids — an extension the reference does NOT have ---------------------------------------
+ * The reference's Core.HybridSearch (core/core.go:760-836) runs an unfiltered Hnsw.Search for 3 k candidates, looks the filter's matches
+ * up among them and then returns the first k - 1 unfiltered candidates anyway; even a corrected post-filter finds nothing at a selective
+ * filter.  These entry points answer "the k nearest among these ids" on the GPU.
+ *
+ * FILTER.  Built from a list of ids against one index; it allows the vertices that hold those ids WHEN IT IS BUILT.  Duplicate ids count
+ * once; unknown or already removed ids are ignored (*out_allowed = the vertices allowed).  Slots are insertion indices and are never
+ * reused, so a filter stays valid across later Inserts (not allowed by it) and Removes (tombstoned vertices are never returned).
+ * coltt_hnsw_load / coltt_hnsw_bulk_load renumber the index: a filter built before them is stale and searching with it is
+ * COLTT_E_INVALID; so is using a filter with another index.  The filter lives on the index's device: a slot bitmap of ceil(slots / 32)
+ * words and the list of allowed slots.  Creation and searches take the index's lock shared.
+ *
+ * WALK (COLTT_FILTER_WALK).  Hnsw.Search at walk breadth ef_walk (= max(ef_override or cfg.ef, k), as coltt_hnsw_search) with one
+ * addition.  The greedy descent and the level-0 searchLevel are the unfiltered canonical walk (oracle/coltt_oracle.cpp:
+ * search_level_canon: ascending-slot neighbour order, lowerBound sampled once per pop, keys (d bits, slot)), so n_dist / n_exp / n_hops
+ * equal an unfiltered search at ef_walk.  An allowed set R of capacity k receives every LIVE ALLOWED vertex whose distance the level-0
+ * walk holds: the level-0 entry point and every neighbour it evaluates, admitted to the walk's result set or not.  R = the k smallest of
+ * those by (d bits, slot) — a pure top-k over a set, independent of when keys arrive.  The answer is R ascending; count = |R| <= k.
+ *
+ * EXACT (COLTT_FILTER_EXACT).  The k nearest live allowed vertices by the index's own distance, ascending by (score bits, slot): cosine
+ * normalises the query, quantised indexes lower it (as coltt_hnsw_search does), a row's score bits equal the walk's evaluation of that
+ * row, tombstones are tested at search time.
+ *
+ * AUTO (COLTT_FILTER_AUTO, the default).  With A = the filter's allowed count, n_live = coltt_hnsw_len and ef as in WALK:
+ *   ef_need = ceil(ef * n_live / A),  ef_walk = min(4096, max(ef, ef_need));
+ *   EXACT when ef_need > 4096 or A <= 32 * ef_walk, else WALK at ef_walk.
+ * 32 is the walk's row evaluations per unit of ef (n_dist / ef ~ 4 040 / 128 on the headline collection): below it the scan reads no
+ * more rows than the walk would, and has no dependent chain (measured crossover: DESIGN.md, "Filtered search").
+ *
+ * An empty filter or an empty index gives counts of 0 and is not an error.  Not served: product-quantised walks, collection groups,
+ * per-query filters within one batch. */
+#define COLTT_FILTER_AUTO 0
+#define COLTT_FILTER_WALK 1
+#define COLTT_FILTER_EXACT 2
+typedef struct coltt_hnsw_filter_stats {   /* per call, summed over the batch */
+  uint64_t n_dist, n_exp, n_hops, n_visit_resets;   /* the walk's counters (coltt_hnsw_stats); 0 when EXACT served the call */
+  uint32_t ef_walk;                        /* the walk's breadth; 0 when EXACT served the call */
+  int32_t path;                            /* COLTT_FILTER_WALK or COLTT_FILTER_EXACT: what served the call (what AUTO chose) */
+  uint64_t n_exact_rows;                   /* (query, row) pairs the exact path scored */
+} coltt_hnsw_filter_stats;
+int coltt_hnsw_filter_create(coltt_handle_t hnsw, const uint64_t* ids, size_t n, uint64_t* out_allowed, coltt_handle_t* out);
+int coltt_hnsw_filter_destroy(coltt_handle_t filter);
+int coltt_hnsw_search_filtered(coltt_handle_t hnsw, coltt_handle_t filter, const float* queries, size_t nq, uint32_t k,
+                               uint32_t ef_override, int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                               coltt_hnsw_filter_stats* stats);
+
 /* Capacity for n_slots vertices (and n_upper_rows upper-level adjacency rows; 0 = the expectation for this index's M) in ONE allocation per
  * array, before the inserts.  Optional — Insert grows the arrays by half their size when they are full — but an index whose final size is
  * known should reserve it: growth copies every array (30 GB of rows at 10 M x 768 f32), and arrays allocated once from an empty heap get the

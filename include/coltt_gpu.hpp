@@ -169,6 +169,27 @@ class Hnsw {
     for (uint32_t i = 0; i < n; i++) r[i] = {ids[i], sc[i]};
     return r;
   }
+  // Filtered search — an extension the reference does not have (coltt_gpu.h, "Filtered HNSW search"): the k nearest among the ids of a
+  // Filter built against this index.  mode: COLTT_FILTER_AUTO / _WALK / _EXACT.
+  class Filter {
+   public:
+    Filter(const Hnsw& index, const std::vector<uint64_t>& ids) { check(coltt_hnsw_filter_create(index.h_, ids.data(), ids.size(), &allowed_, &h_)); }
+    ~Filter() { if (h_) coltt_hnsw_filter_destroy(h_); }
+    Filter(const Filter&) = delete;
+    Filter& operator=(const Filter&) = delete;
+    uint64_t Allowed() const { return allowed_; }
+    coltt_handle_t handle() const { return h_; }
+   private:
+    coltt_handle_t h_ = 0; uint64_t allowed_ = 0;
+  };
+  SearchResult SearchFiltered(const Vector& query, unsigned k, const Filter& f, unsigned ef = 0, int mode = COLTT_FILTER_AUTO,
+                              coltt_hnsw_filter_stats* stats = nullptr) const {
+    std::vector<uint64_t> ids(k); std::vector<float> sc(k); uint32_t n = 0;
+    check(coltt_hnsw_search_filtered(h_, f.handle(), query.data(), 1, k, ef, mode, ids.data(), sc.data(), &n, stats));
+    SearchResult r(n);
+    for (uint32_t i = 0; i < n; i++) r[i] = {ids[i], sc[i]};
+    return r;
+  }
   int Len() const { uint64_t n = 0; check(coltt_hnsw_len(h_, &n)); return (int)n; }
   // the collection's size is known (bulk import, Load): every array allocated once; never shrinks, never limits an Insert
   void Reserve(uint64_t vertices, uint64_t upper_rows = 0) { check(coltt_hnsw_reserve(h_, vertices, upper_rows)); }
