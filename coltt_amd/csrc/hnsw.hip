@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <map>
 
 #include "common.hpp"
 #include "exact.hpp"
@@ -395,6 +396,7 @@ struct HCtx {
   DevBuf w_qraw, w_qeff, w_qn, w_out_ids, w_out_sc, w_out_cnt, w_misc, w_pack;
   DevBuf w_surv, w_scnt, w_keys;   // product-quantised walk: survivors (slots), their count, their exact keys
   DevBuf w_mbox;                   // latency kernel: the walking workgroups' hint mailboxes (hnsw_lat.hpp: cache-warming helper workgroups)
+  DevBuf w_fdesc;                  // filtered batch: the walks' per-query descriptors, the exact path's queries and tiles
   PinnedBuf h_in, h_out;   // small calls: see PinnedBuf
   int init() {  // the caller has selected the index's device
     COLTT_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -2372,6 +2374,197 @@ int filter_search_common(Hnsw* x, HCtx* c, const HnswFilter* f, const float* que
   return COLTT_OK;
 }
 
+
+// ---- coltt_hnsw_search_filtered_batch: a filter per query.  Row i is the single-filter call on query i alone: its path from its own filter's
+// allowed count (filter_path), its walk at the geometry search_geom gives its ef_walk, its exact scan chunked by today's rules (the answer
+// is a pure top-k, so the chunking cannot change it).  One call launches at most two walks (LDS hash, HBM byte map), one scan, one select.
+template <int METRIC, int QUANT>
+int launch_search_filtered_batch(Hnsw* x, HCtx* c, bool visg, size_t lds, uint32_t grid, uint32_t region_base, uint32_t nw, uint32_t k,
+                                 const FiltQuery* fq, uint32_t* counter, uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
+  auto kern = visg ? hnsw_search_filtered_batch_kernel<METRIC, QUANT, true> : hnsw_search_filtered_batch_kernel<METRIC, QUANT, false>;
+  if constexpr (QUANT != Q_F8) { if (x->r8) kern = visg ? hnsw_search_filtered_batch_kernel<METRIC, QUANT, true, true> : hnsw_search_filtered_batch_kernel<METRIC, QUANT, false, true>; }
+  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  kern<<<grid, 64, lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nw, k, fq, counter, oi, os, oc, stats,
+                                     x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
+                                     x->w_vepoch.as<uint32_t>() + region_base);
+  COLTT_HIP(hipGetLastError());
+  return COLTT_OK;
+}
+
+template <int METRIC, int QUANT>
+int launch_filter_exact_batch(Hnsw* x, HCtx* c, uint32_t qg, uint32_t ntiles, uint32_t nexact, uint64_t nlists, const FiltTile* tiles,
+                              const FiltExactQ* eq, uint32_t k, uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
+  const size_t qbytes = (((size_t)x->dim + 3) & ~(size_t)3) * 4, kbytes = (size_t)((k + 63) & ~63u) * 8;
+  const size_t lds = qg * (qbytes + kbytes);
+  COLTT_TRY(c->w_keys.reserve((size_t)nlists * k * 8));
+  COLTT_TRY(c->w_scnt.reserve((size_t)nlists * 4));
+  GraphView gv = x->view();
+  auto scan = hnsw_filter_scan_batch_kernel<METRIC, QUANT, false>;
+  if constexpr (QUANT != Q_F8) { if (x->r8) scan = hnsw_filter_scan_batch_kernel<METRIC, QUANT, true>; }
+  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  scan<<<ntiles, 64, lds, c->stream>>>(gv, c->w_qeff.as<float>(), c->w_qn.as<float>(), tiles, eq, qg, k, (k + 63) & ~63u,
+                                       c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), stats);
+  COLTT_HIP(hipGetLastError());
+  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_filter_select_batch_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kbytes));
+  hnsw_filter_select_batch_kernel<><<<nexact, 64, kbytes, c->stream>>>(c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), eq, k, gv.ids, oi, os, oc);
+  COLTT_HIP(hipGetLastError());
+  return COLTT_OK;
+}
+
+int filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,
+                        int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, int32_t* out_paths, coltt_hnsw_filter_stats* st) {
+  coltt_hnsw_filter_stats local{};
+  if (!st) st = &local;
+  std::memset(st, 0, sizeof(*st));
+  if (mode != COLTT_FILTER_AUTO && mode != COLTT_FILTER_WALK && mode != COLTT_FILTER_EXACT) return fail(COLTT_E_INVALID, "hnsw_search_filtered_batch: unknown mode %d", mode);
+  if (nq == 0) return COLTT_OK;
+  if (k == 0) return fail(COLTT_E_INVALID, "hnsw_search_filtered_batch: k must be >= 1");
+  if (nq > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered_batch: more than 2^32-1 queries in one call");
+  const uint32_t ef = std::max<uint32_t>(ef_override ? ef_override : (uint32_t)x->cfg.ef, k);
+  if (ef > FILTER_EF_MAX) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered_batch: ef=%u > %llu", ef, (unsigned long long)FILTER_EF_MAX);
+  // each query's path, as its single-filter call would take it (n_live read once, under the caller's read lock)
+  const uint64_t n_live = x->live;
+  std::vector<uint32_t> efw(nq);
+  std::vector<uint32_t> walk_q, exact_q;   // the served queries (a non-empty filter on a non-empty index)
+  bool any_walk = false, any_exact = false, want_visg = false;
+  for (size_t i = 0; i < nq; i++) {
+    const int path = filter_path(fl[i]->allowed, n_live, ef, mode, efw[i]);
+    if (out_paths) out_paths[i] = path;
+    if (path == COLTT_FILTER_WALK) { any_walk = true; st->ef_walk = std::max(st->ef_walk, efw[i]); }
+    else any_exact = true;
+    if (x->entry < 0 || fl[i]->allowed == 0) continue;
+    if (path == COLTT_FILTER_WALK) { walk_q.push_back((uint32_t)i); want_visg |= wants_visg(efw[i]); }
+    else exact_q.push_back((uint32_t)i);
+  }
+  st->path = any_walk && any_exact ? COLTT_FILTER_AUTO : any_walk ? COLTT_FILTER_WALK : COLTT_FILTER_EXACT;
+  if (walk_q.empty() && exact_q.empty()) {   // only empty filters, or an empty index: counts 0, not an error
+    std::memset(out_counts, 0, nq * 4);
+    return COLTT_OK;
+  }
+  // the walks: each query's geometry is the single call's, search_geom(x, ef_walk, false, true, k); split by visited set
+  if (want_visg) COLTT_TRY(ensure_visg(x));
+  std::map<uint32_t, SearchGeom> geoms;
+  std::vector<FiltQuery> wq[2];
+  SearchGeom wmax[2]{};
+  for (uint32_t i : walk_q) {
+    auto it = geoms.find(efw[i]);
+    if (it == geoms.end()) it = geoms.emplace(efw[i], search_geom(x, efw[i], false, true, k)).first;
+    const SearchGeom& sg = it->second;
+    if (sg.lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered_batch: dim/ef/k need %zu B of LDS (> 160 KiB)", sg.lds);
+    const int v = sg.visg ? 1 : 0;
+    wq[v].push_back(FiltQuery{fl[i]->bits.as<uint32_t>(), fl[i]->slots, sg.ef, sg.ef_pad, sg.hcap, i, 0u});
+    if (wq[v].size() == 1 || sg.lds > wmax[v].lds) wmax[v] = sg;   // the launch's LDS: its largest query's
+  }
+  // the exact path: queries sorted by filter, groups of <= qg sharing one, chunk lists as launch_filter_exact sizes them
+  const size_t qbytes = (((size_t)x->dim + 3) & ~(size_t)3) * 4, kbytes = (size_t)((k + 63) & ~63u) * 8;
+  uint32_t qg = FILT_QG;
+  while (qg > 1 && qg * (qbytes + kbytes) > 64 * 1024) qg--;
+  std::vector<FiltExactQ> eq;
+  std::vector<FiltTile> tiles;
+  uint64_t nlists = 0;
+  if (!exact_q.empty()) {
+    if (qg * (qbytes + kbytes) > 160 * 1024)
+      return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered_batch: dim %u / k %u need %zu B of LDS (> 160 KiB)", x->dim, k, qg * (qbytes + kbytes));
+    std::stable_sort(exact_q.begin(), exact_q.end(), [&](uint32_t a, uint32_t b) { return std::less<const HnswFilter*>()(fl[a], fl[b]); });
+    struct Run { size_t first, len; uint64_t nch, chunk; };
+    std::vector<Run> runs;
+    uint64_t groups = 0;
+    for (size_t a = 0; a < exact_q.size();) {
+      size_t b = a;
+      while (b < exact_q.size() && fl[exact_q[b]] == fl[exact_q[a]]) b++;
+      runs.push_back(Run{a, b - a, 0, 0});
+      groups += ceil_div(b - a, qg);
+      a = b;
+    }
+    for (Run& r : runs) r.nch = std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(4096, groups), ceil_div(fl[exact_q[r.first]]->allowed, 256)));
+    auto lists = [&] { uint64_t t = 0; for (const Run& r : runs) t += r.len * r.nch; return t; };
+    while (lists() * k * 8 > (256ull << 20)) {   // the chunk lists' workspace
+      bool any = false;
+      for (Run& r : runs) if (r.nch > 1) { r.nch = (r.nch + 1) / 2; any = true; }
+      if (!any) break;
+    }
+    for (Run& r : runs) {
+      const HnswFilter* f = fl[exact_q[r.first]];
+      const uint64_t A = f->allowed;
+      r.chunk = (((A + r.nch - 1) / r.nch) + 31) & ~31ull;
+      r.nch = (A + r.chunk - 1) / r.chunk;
+      for (size_t j = 0; j < r.len; j++) {
+        eq.push_back(FiltExactQ{exact_q[r.first + j], (uint32_t)nlists, (uint32_t)r.nch, 0u});
+        nlists += r.nch;
+      }
+      for (size_t g0 = 0; g0 < r.len; g0 += qg)
+        for (uint64_t ch = 0; ch < r.nch; ch++)
+          tiles.push_back(FiltTile{f->list.as<uint32_t>(), (uint32_t)(ch * r.chunk), (uint32_t)std::min<uint64_t>(A, (ch + 1) * r.chunk),
+                                   (uint32_t)(r.first + g0), (uint32_t)std::min<size_t>(qg, r.len - g0), (uint32_t)ch, 0u});
+    }
+    if (nlists > 0xffffffffull || tiles.size() > 0x7fffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered_batch: too many exact-path chunk lists");
+  }
+  // one upload of every table: [walks over the LDS hash][walks over the byte map][exact queries][tiles]
+  const size_t o_w1 = wq[0].size() * sizeof(FiltQuery), o_eq = o_w1 + wq[1].size() * sizeof(FiltQuery);
+  const size_t o_t = (o_eq + eq.size() * sizeof(FiltExactQ) + 31) & ~(size_t)31, o_end = o_t + tiles.size() * sizeof(FiltTile);
+  std::vector<uint8_t> blob(o_end);
+  if (!wq[0].empty()) std::memcpy(blob.data(), wq[0].data(), wq[0].size() * sizeof(FiltQuery));
+  if (!wq[1].empty()) std::memcpy(blob.data() + o_w1, wq[1].data(), wq[1].size() * sizeof(FiltQuery));
+  if (!eq.empty()) std::memcpy(blob.data() + o_eq, eq.data(), eq.size() * sizeof(FiltExactQ));
+  if (!tiles.empty()) std::memcpy(blob.data() + o_t, tiles.data(), tiles.size() * sizeof(FiltTile));
+  COLTT_TRY(c->w_fdesc.reserve(o_end));
+  uint8_t* d_desc = c->w_fdesc.as<uint8_t>();
+  COLTT_HIP(hipMemcpyAsync(d_desc, blob.data(), o_end, hipMemcpyHostToDevice, c->stream));
+  COLTT_TRY(c->w_out_ids.reserve(nq * k * 8));
+  COLTT_TRY(c->w_out_sc.reserve(nq * k * 4));
+  COLTT_TRY(c->w_out_cnt.reserve(nq * 4));
+  uint64_t* d_oi = c->w_out_ids.as<uint64_t>(); float* d_os = c->w_out_sc.as<float>(); uint32_t* d_oc = c->w_out_cnt.as<uint32_t>();
+  COLTT_HIP(hipMemsetAsync(d_oc, 0, nq * 4, c->stream));   // rows of empty filters stay at count 0
+  uint32_t grid[2] = {0, 0};
+  RegionLease lease;
+  for (int v = 0; v < 2; v++) if (!wq[v].empty()) grid[v] = std::min<uint32_t>((uint32_t)wq[v].size(), resident_waves(wmax[v], x->quant));
+  if (grid[1]) { acquire_regions(x, grid[1], lease); grid[1] = lease.count; }
+  COLTT_TRY(c->w_qraw.reserve(nq * x->dim * 4));
+  COLTT_HIP(hipMemcpyAsync(c->w_qraw.p, queries, nq * x->dim * 4, hipMemcpyHostToDevice, c->stream));
+  COLTT_TRY(c->w_misc.reserve(256));
+  COLTT_TRY(c->h_out.reserve(256));
+  uint8_t* misc = c->w_misc.as<uint8_t>();
+  uint32_t* counters = reinterpret_cast<uint32_t*>(misc);   // [0]: the LDS-hash walk's work counter, [1]: the byte-map walk's
+  unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(misc + 16);
+  COLTT_TRY(prep_queries_any(x, c, c->w_qraw.as<float>(), nq, reinterpret_cast<uint32_t*>(misc)));   // as the single call; clears the counters
+  COLTT_HIP(hipEventRecord(c->ev0, c->stream));
+  int rc = COLTT_OK;
+  const bool cos = x->metric == COLTT_COSINE;
+  for (int v = 0; v < 2 && rc == COLTT_OK; v++) {
+    if (!grid[v]) continue;
+    const FiltQuery* fq = reinterpret_cast<const FiltQuery*>(d_desc + (v ? o_w1 : 0));
+    const uint32_t nw = (uint32_t)wq[v].size();
+#define COLTT_FW(Q) rc = cos ? launch_search_filtered_batch<M_COS, Q>(x, c, v == 1, wmax[v].lds, grid[v], lease.base, nw, k, fq, counters + v, d_oi, d_os, d_oc, d_stats) \
+                         : launch_search_filtered_batch<M_L2, Q>(x, c, v == 1, wmax[v].lds, grid[v], lease.base, nw, k, fq, counters + v, d_oi, d_os, d_oc, d_stats)
+    COLTT_DISPATCH_QUANT(x->quant, COLTT_FW)
+#undef COLTT_FW
+  }
+  COLTT_TRY(rc);
+  if (!eq.empty()) {
+    const FiltTile* d_tiles = reinterpret_cast<const FiltTile*>(d_desc + o_t);
+    const FiltExactQ* d_eq = reinterpret_cast<const FiltExactQ*>(d_desc + o_eq);
+#define COLTT_FE(Q) rc = cos ? launch_filter_exact_batch<M_COS, Q>(x, c, qg, (uint32_t)tiles.size(), (uint32_t)eq.size(), nlists, d_tiles, d_eq, k, d_oi, d_os, d_oc, d_stats) \
+                         : launch_filter_exact_batch<M_L2, Q>(x, c, qg, (uint32_t)tiles.size(), (uint32_t)eq.size(), nlists, d_tiles, d_eq, k, d_oi, d_os, d_oc, d_stats)
+    COLTT_DISPATCH_QUANT(x->quant, COLTT_FE)
+#undef COLTT_FE
+    COLTT_TRY(rc);
+  }
+  COLTT_HIP(hipEventRecord(c->ev1, c->stream));
+  if (x->dense && x->dense_base) add_base_kernel<<<ceil_div(nq * k, 256), 256, 0, c->stream>>>(d_oi, nq * k, x->dense_base);
+  COLTT_HIP(hipMemcpyAsync(out_ids, d_oi, nq * k * 8, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipMemcpyAsync(out_scores, d_os, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipMemcpyAsync(out_counts, d_oc, nq * 4, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 48, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipStreamSynchronize(c->stream));   // the lease, the host tables and the callers' filters outlive the kernels
+  unsigned long long h_stats[6];
+  std::memcpy(h_stats, c->h_out.p, 48);
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+  x->last_ms.store(ms);
+  if (h_stats[4]) return fail(COLTT_E_DEVICE, "hnsw_search_filtered_batch: traversal watchdog tripped (code %llu)", h_stats[4]);
+  st->n_dist = h_stats[0]; st->n_exp = h_stats[1]; st->n_hops = h_stats[2]; st->n_visit_resets = h_stats[3]; st->n_exact_rows = h_stats[5];
+  return COLTT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2437,6 +2630,35 @@ int coltt_hnsw_search_filtered(coltt_handle_t h, coltt_handle_t fh, const float*
   CtxLease<HCtx> ctx(x->pool);
   if (!ctx.c) return COLTT_E_DEVICE;
   return filter_search_common(x.get(), ctx.c, f.get(), queries, nq, k, ef_override, mode, out_ids, out_scores, out_counts, stats);
+}
+
+int coltt_hnsw_search_filtered_batch(coltt_handle_t h, const coltt_handle_t* filters, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,
+                                     int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, int32_t* out_paths,
+                                     coltt_hnsw_filter_stats* stats) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_search_filtered_batch: unknown index handle");
+  if (nq && !filters) return fail(COLTT_E_INVALID, "hnsw_search_filtered_batch: NULL filters");
+  if (nq && (!queries || !out_ids || !out_scores || !out_counts)) return fail(COLTT_E_INVALID, "hnsw_search_filtered_batch: NULL buffer");
+  ReadLock g(x->rw);
+  // every handle is checked before anything is launched; each distinct filter is held until the call returns (a concurrent destroy
+  // only unregisters it)
+  std::unordered_map<coltt_handle_t, std::shared_ptr<HnswFilter>> held;
+  std::vector<HnswFilter*> fl(nq);
+  for (size_t i = 0; i < nq; i++) {
+    auto it = held.find(filters[i]);
+    if (it == held.end()) {
+      auto f = lookup<HnswFilter>(filters[i]);
+      if (!f) return fail(COLTT_E_NOT_FOUND, "hnsw_search_filtered_batch: unknown filter handle at position %zu", i);
+      if (f->index != h) return fail(COLTT_E_INVALID, "hnsw_search_filtered_batch: the filter at position %zu was built for another index", i);
+      if (f->gen != x->gen) return fail(COLTT_E_INVALID, "hnsw_search_filtered_batch: the filter at position %zu is stale (the index was loaded since it was built)", i);
+      it = held.emplace(filters[i], std::move(f)).first;
+    }
+    fl[i] = it->second.get();
+  }
+  COLTT_DEVICE(x->device);
+  CtxLease<HCtx> ctx(x->pool);
+  if (!ctx.c) return COLTT_E_DEVICE;
+  return filter_batch_common(x.get(), ctx.c, fl, queries, nq, k, ef_override, mode, out_ids, out_scores, out_counts, out_paths, stats);
 }
 
 }  // extern "C"

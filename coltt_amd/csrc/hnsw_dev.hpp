@@ -208,6 +208,9 @@ __device__ __forceinline__ bool filter_allows(const FilterView& f, uint32_t slot
 // The allowed set R of a filtered walk: the cap smallest keys (d bits << 32 | slot << 1, the result set's layout) of the live allowed
 // vertices whose distance the level-0 walk holds.  r[0..len) ascending, in LDS beside the result set.
 struct FiltSet { unsigned long long* r; uint32_t len, cap; FilterView f; };
+// coltt_hnsw_search_filtered_batch, WALK: one query's walk as the single-filter call would run it — its filter, its breadth ef, the
+// LDS geometry search_geom gives that ef (ef_pad, hcap), and the batch row it reads its query from and writes its answer to.
+struct FiltQuery { const uint32_t* bits; uint32_t slots, ef, ef_pad, hcap, row, pad_; };
 
 // Offer each lane's key (where `take`) to the sorted LDS array a[0..len) of capacity cap >= 1 and keep the cap smallest: a pure top-k,
 // independent of the order in which keys arrive.  The keys offered by one call are distinct; `dedup`: a key the array already holds is

@@ -17,14 +17,17 @@ using namespace coltt::dev;
 // Hnsw.Search (hnsw.go:243-278) for a batch: one wave per query, queries pulled from a global counter.  The body of hnsw_search_kernel and
 // hnsw_search_filtered_kernel.  FILTER (coltt_hnsw_search_filtered, WALK): the same walk, plus the allowed set R (hnsw_dev.hpp: FiltSet) of
 // k_pad = k rounded up to 64 entries in LDS between the result set and the visited hash; the answer is R instead of the walk's k nearest.
-template <int METRIC, int QUANT, bool VISG, bool R8, bool FILTER>
+// PERQ (coltt_hnsw_search_filtered_batch, with FILTER): the claimed index selects a descriptor fq[qi] (hnsw_dev.hpp: FiltQuery) that
+// gives the query's filter, ef, LDS geometry and batch row; ef / ef_pad / hcap / fv are then ignored.
+template <int METRIC, int QUANT, bool VISG, bool R8, bool FILTER, bool PERQ = false>
 __device__ __forceinline__ void search_one_wave(uint8_t* smem, GraphView g, int32_t entry, int32_t entry_level,
                                                 const float* __restrict__ q_eff, const float* __restrict__ qnorms,
                                                 uint32_t nq, uint32_t k, uint32_t ef, uint32_t ef_pad, uint32_t hcap,
                                                 uint32_t* __restrict__ counter, uint64_t* __restrict__ out_ids,
                                                 float* __restrict__ out_scores, uint32_t* __restrict__ out_counts,
                                                 unsigned long long* __restrict__ stats, uint8_t* __restrict__ visg,
-                                                size_t vis_stride, uint32_t* __restrict__ vis_epoch, FilterView fv) {
+                                                size_t vis_stride, uint32_t* __restrict__ vis_epoch, FilterView fv,
+                                                const FiltQuery* __restrict__ fq = nullptr) {
   constexpr int PROF = VISG ? PROF_SEARCH_HBM : PROF_SEARCH_LDS;
   const int lane = threadIdx.x;
   WaveCtx w;
@@ -45,14 +48,24 @@ __device__ __forceinline__ void search_one_wave(uint8_t* smem, GraphView g, int3
     const uint32_t qt = atomicAdd(counter, lane == 0 ? 1u : 0u);
     const uint32_t qi = (uint32_t)__shfl((int)qt, 0, 64);
     if (qi >= nq) break;
+    uint32_t row = qi;
+    if constexpr (PERQ) {   // the descriptor is wave-uniform: its words go to scalar registers
+      const uint32_t* dw = reinterpret_cast<const uint32_t*>(fq + qi);
+      auto rf = [&](int i) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)dw[i]); };
+      fs.f = FilterView{reinterpret_cast<const uint32_t*>(((uint64_t)rf(1) << 32) | rf(0)), rf(2)};
+      ef = rf(3); ef_pad = rf(4); hcap = rf(5); row = rf(6);
+      fs.r = w.res0 + (size_t)ef_pad;
+      w.vis = reinterpret_cast<uint32_t*>(w.res0 + (size_t)ef_pad + k_pad);
+      w.ef_pad = ef_pad; w.hcap = hcap; w.hcap_mask = hcap - 1;
+    }
     w.n_dist = w.n_exp = w.n_hops = w.n_resets = 0; w.err = 0;
 #ifdef COLTT_PHASE_TIMING
     for (int i_ = 0; i_ < 8; i_++) w.pt[i_] = 0;
     w.t_last = __builtin_amdgcn_s_memtime();
 #endif
     wave_sync();
-    for (int e = lane; e < g.dim; e += 64) w.qs[e] = q_eff[(size_t)qi * g.dim + e];
-    w.qnorm = qnorms[qi];
+    for (int e = lane; e < g.dim; e += 64) w.qs[e] = q_eff[(size_t)row * g.dim + e];
+    w.qnorm = qnorms[row];
     wave_sync();
     // minDistance := Distance(query, entrypoint.vector) (hnsw.go:253)
     uint32_t cur = (uint32_t)entry;
@@ -72,11 +85,11 @@ __device__ __forceinline__ void search_one_wave(uint8_t* smem, GraphView g, int3
     for (uint32_t i = lane; i < n; i += 64) {
       unsigned long long e = res[i];
       uint32_t slot = (uint32_t)e >> 1;
-      out_ids[(size_t)qi * k + i] = g.ids ? g.ids[slot] : (uint64_t)slot;
-      out_scores[(size_t)qi * k + i] = __uint_as_float((uint32_t)(e >> 32));
+      out_ids[(size_t)row * k + i] = g.ids ? g.ids[slot] : (uint64_t)slot;
+      out_scores[(size_t)row * k + i] = __uint_as_float((uint32_t)(e >> 32));
     }
     if (lane == 0) {
-      out_counts[qi] = n;
+      out_counts[row] = n;
       atomicAdd(&stats[0], (unsigned long long)w.n_dist);
       atomicAdd(&stats[1], (unsigned long long)w.n_exp);
       atomicAdd(&stats[2], (unsigned long long)w.n_hops);
@@ -114,6 +127,21 @@ __global__ __launch_bounds__(64) void hnsw_search_filtered_kernel(GraphView g, i
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   search_one_wave<METRIC, QUANT, VISG, R8, true>(smem, g, entry, entry_level, q_eff, qnorms, nq, k, ef, ef_pad, hcap, counter, out_ids, out_scores,
                                                  out_counts, stats, visg, vis_stride, vis_epoch, fv);
+}
+
+// coltt_hnsw_search_filtered_batch, WALK: the same walk with one filter, breadth and LDS geometry per query (fq[0..nq)); the launch's
+// dynamic LDS is the largest of its queries'.  A third instance family: the two above stay as they are.
+template <int METRIC, int QUANT, bool VISG, bool R8 = false>
+__global__ __launch_bounds__(64) void hnsw_search_filtered_batch_kernel(GraphView g, int32_t entry, int32_t entry_level,
+                                                                       const float* __restrict__ q_eff, const float* __restrict__ qnorms,
+                                                                       uint32_t nq, uint32_t k, const FiltQuery* __restrict__ fq,
+                                                                       uint32_t* __restrict__ counter, uint64_t* __restrict__ out_ids,
+                                                                       float* __restrict__ out_scores, uint32_t* __restrict__ out_counts,
+                                                                       unsigned long long* __restrict__ stats, uint8_t* __restrict__ visg,
+                                                                       size_t vis_stride, uint32_t* __restrict__ vis_epoch) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  search_one_wave<METRIC, QUANT, VISG, R8, true, true>(smem, g, entry, entry_level, q_eff, qnorms, nq, k, 0u, 0u, 64u, counter, out_ids, out_scores,
+                                                       out_counts, stats, visg, vis_stride, vis_epoch, FilterView{nullptr, 0u}, fq);
 }
 
 
@@ -517,6 +545,93 @@ __global__ __launch_bounds__(64) void hnsw_filter_select_kernel(const unsigned l
   for (uint32_t c = 0; c < nchunks; c++) {
     const uint32_t cnt = part_cnt[q * nchunks + c];
     const unsigned long long* src = part + (q * nchunks + c) * k;
+    for (uint32_t b = 0; b < cnt; b += 64) {
+      const int lane = opaque_lane(lane_in);
+      const bool take = b + (uint32_t)lane < cnt;
+      sorted_offer(top, len, k, take, take ? src[b + lane] : ~0ull, lane, false);
+    }
+  }
+  for (uint32_t i = (uint32_t)lane_in; i < len; i += 64) {
+    const unsigned long long e = top[i];
+    const uint32_t slot = (uint32_t)e >> 1;
+    out_ids[q * k + i] = ids ? ids[slot] : (uint64_t)slot;
+    out_scores[q * k + i] = __uint_as_float((uint32_t)(e >> 32));
+  }
+  if (lane_in == 0) out_counts[q] = len;
+}
+
+// coltt_hnsw_search_filtered_batch, EXACT: the two steps above with a filter per query.  The host sorts the exact-path queries by filter
+// and cuts groups of <= qg queries that share one; FiltExactQ e = such a query: its batch row and its run of chunk lists in part.  A tile
+// = (group, chunk of the group's filter list): one wave of the scan, the same evaluator and the same top-k as hnsw_filter_scan_kernel.
+struct FiltTile { const uint32_t* slots; uint32_t s0, s1, e0, nqg, chunk, pad_; };   // list[s0, s1) against queries e0 .. e0 + nqg - 1
+struct FiltExactQ { uint32_t row, pbase, nchunks, pad_; };                        // part lists pbase .. pbase + nchunks - 1
+template <int METRIC, int QUANT, bool R8>
+__global__ __launch_bounds__(64) void hnsw_filter_scan_batch_kernel(GraphView g, const float* __restrict__ q_eff, const float* __restrict__ qnorms,
+                                                                    const FiltTile* __restrict__ tiles, const FiltExactQ* __restrict__ eq, uint32_t qg,
+                                                                    uint32_t k, uint32_t k_pad, unsigned long long* __restrict__ part,
+                                                                    uint32_t* __restrict__ part_cnt, unsigned long long* __restrict__ stats) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int lane_in = threadIdx.x;
+  const uint32_t* tw = reinterpret_cast<const uint32_t*>(tiles + blockIdx.x);
+  auto rf = [&](int i) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)tw[i]); };   // the tile is wave-uniform
+  const uint32_t* const slots = reinterpret_cast<const uint32_t*>(((uint64_t)rf(1) << 32) | rf(0));
+  const uint32_t s0 = rf(2), s1 = rf(3), e0 = rf(4), nqg = rf(5), c = rf(6);
+  const size_t qstride = ((size_t)g.dim + 3) & ~(size_t)3;
+  float* const qs = reinterpret_cast<float*>(smem);                                              // [qg][qstride]
+  unsigned long long* const top = reinterpret_cast<unsigned long long*>(qs + (size_t)qg * qstride);   // [qg][k_pad]
+  uint32_t rows_of[FILT_QG];
+#pragma unroll
+  for (uint32_t j = 0; j < FILT_QG; j++) rows_of[j] = j < nqg ? (uint32_t)__builtin_amdgcn_readfirstlane((int)eq[e0 + j].row) : 0u;
+  for (uint32_t j = 0; j < nqg; j++)
+    for (int e = lane_in; e < g.dim; e += 64) qs[(size_t)j * qstride + e] = q_eff[(size_t)eq[e0 + j].row * g.dim + e];
+  wave_sync();
+  uint32_t lens[FILT_QG];
+#pragma unroll
+  for (uint32_t j = 0; j < FILT_QG; j++) lens[j] = 0;
+  unsigned long long rows = 0;
+  for (uint32_t base = s0; base < s1; base += 32) {
+    const int lane = opaque_lane(lane_in);
+    const int half = lane & 1, p = lane >> 1;
+    const uint32_t i = base + (uint32_t)p;
+    const bool valid = i < s1;
+    const uint32_t slot = slots[valid ? i : base];   // an idle pair re-evaluates a listed row (DPP partners stay active)
+    const bool live = valid && !is_deleted(g, slot);   // tombstones at search time
+    rows += __popcll(__ballot(live && half == 0));
+#pragma unroll
+    for (uint32_t j = 0; j < FILT_QG; j++) {
+      if (j >= nqg) break;   // wave-uniform
+      const float d = eval_pair_q<METRIC, QUANT, PROF_SEARCH_HBM, R8>(g, qs + (size_t)j * qstride, qnorms[rows_of[j]], slot, half);
+      sorted_offer(top + (size_t)j * k_pad, lens[j], k, live && half == 0, ((unsigned long long)__float_as_uint(d) << 32) | ((unsigned long long)slot << 1),
+                   lane, false);
+    }
+  }
+#pragma unroll
+  for (uint32_t j = 0; j < FILT_QG; j++) {
+    if (j >= nqg) break;
+    const size_t l = (size_t)eq[e0 + j].pbase + c;
+    for (uint32_t i = (uint32_t)lane_in; i < lens[j]; i += 64) part[l * k + i] = top[(size_t)j * k_pad + i];
+    if (lane_in == 0) part_cnt[l] = lens[j];
+  }
+  if (lane_in == 0 && rows) atomicAdd(&stats[5], rows * nqg);
+}
+// step 2: one wave per exact-path query merges its own chunk lists and writes its batch row.  (A template, like every kernel added with it,
+// so that it is instantiated after the pre-existing kernels and their assembly stays byte-identical.)
+template <int = 0>
+__global__ __launch_bounds__(64) void hnsw_filter_select_batch_kernel(const unsigned long long* __restrict__ part, const uint32_t* __restrict__ part_cnt,
+                                                                      const FiltExactQ* __restrict__ eq, uint32_t k, const uint64_t* __restrict__ ids,
+                                                                      uint64_t* __restrict__ out_ids, float* __restrict__ out_scores,
+                                                                      uint32_t* __restrict__ out_counts) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  unsigned long long* const top = reinterpret_cast<unsigned long long*>(smem);
+  const FiltExactQ d = eq[blockIdx.x];
+  const size_t q = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.row);
+  const size_t pbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.pbase);
+  const uint32_t nchunks = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.nchunks);
+  const int lane_in = threadIdx.x;
+  uint32_t len = 0;
+  for (uint32_t c = 0; c < nchunks; c++) {
+    const uint32_t cnt = part_cnt[pbase + c];
+    const unsigned long long* src = part + (pbase + c) * k;
     for (uint32_t b = 0; b < cnt; b += 64) {
       const int lane = opaque_lane(lane_in);
       const bool take = b + (uint32_t)lane < cnt;

@@ -26,6 +26,7 @@ type BatchItem struct {
 type Batcher struct {
 	dim      int
 	backend  Backend
+	fbackend FilteredBackend // set by NewFilteredBatcher: the filtered mode
 	MaxBatch int
 	MaxWait  time.Duration
 	in       chan *pending
@@ -34,9 +35,10 @@ type Batcher struct {
 }
 
 type pending struct {
-	q    []float32
-	k    uint32
-	done chan batchResult
+	q      []float32
+	k      uint32
+	filter Handle // filtered mode: the caller's filter
+	done   chan batchResult
 }
 type batchResult struct {
 	items []BatchItem
@@ -71,15 +73,53 @@ func FlatBackend(h Handle, dim uint32, sel, mode int) Backend {
 	}
 }
 
+// Filtered mode (same semantics as coltt::FilteredBatcher in include/coltt_batcher.hpp): every caller brings its own filter handle
+// (HnswFilterCreate), batches are grouped by k only and mix any number of filters.  The batch call checks every handle before it runs
+// anything, so one caller's bad filter (destroyed, stale, of another index) fails the whole call: the batch is then re-issued one query
+// at a time and only the callers whose own call fails get its error.
+type FilteredBackend func(filters []Handle, queries []float32, nq int, k uint32) (ids []uint64, scores []float32, counts []uint32, err error)
+
+func HnswFilteredBackend(h Handle, dim uint32, ef uint32) FilteredBackend {
+	return func(f []Handle, q []float32, nq int, k uint32) ([]uint64, []float32, []uint32, error) {
+		ids, sc, cnt, _, err := HnswSearchFilteredBatch(h, f, dim, q, nq, k, ef, FilterAuto)
+		return ids, sc, cnt, err
+	}
+}
+
+func NewFilteredBatcher(dim int, backend FilteredBackend, maxBatch int, maxWait time.Duration) *Batcher {
+	if maxBatch < 1 {
+		maxBatch = 1
+	}
+	b := &Batcher{dim: dim, fbackend: backend, MaxBatch: maxBatch, MaxWait: maxWait, in: make(chan *pending, 4*maxBatch),
+		quit: make(chan struct{})}
+	go b.loop()
+	return b
+}
+
+// SearchFiltered (filtered mode) blocks until the batch this query rode in has been answered.
+func (b *Batcher) SearchFiltered(q []float32, k uint, filter Handle) ([]BatchItem, error) {
+	if b.fbackend == nil {
+		return nil, fmt.Errorf("SearchFiltered: not a filtered batcher (NewFilteredBatcher)")
+	}
+	return b.search(q, k, filter)
+}
+
 // Search blocks until the batch this query rode in has been answered.  The query is copied before it is queued.
 func (b *Batcher) Search(q []float32, k uint) ([]BatchItem, error) {
+	if b.fbackend != nil {
+		return nil, fmt.Errorf("Search: a filtered batcher takes SearchFiltered")
+	}
+	return b.search(q, k, 0)
+}
+
+func (b *Batcher) search(q []float32, k uint, filter Handle) ([]BatchItem, error) {
 	if len(q) != b.dim {
 		return nil, fmt.Errorf("Dim Length UnmatchdError: expect dimension: [%d], but got [%d]", b.dim, len(q))
 	}
 	if k == 0 {
 		return []BatchItem{}, nil
 	}
-	p := &pending{q: append([]float32(nil), q...), k: uint32(k), done: make(chan batchResult, 1)}
+	p := &pending{q: append([]float32(nil), q...), k: uint32(k), filter: filter, done: make(chan batchResult, 1)}
 	select {
 	case b.in <- p:
 	case <-b.quit:
@@ -163,6 +203,10 @@ func (b *Batcher) flush(batch []*pending) {
 		for i, p := range grp {
 			copy(flat[i*b.dim:], p.q)
 		}
+		if b.fbackend != nil {
+			b.flushFiltered(grp, flat, k)
+			continue
+		}
 		ids, sc, cnt, err := b.backend(flat, nq, k)
 		for i, p := range grp {
 			if err != nil {
@@ -176,5 +220,40 @@ func (b *Batcher) flush(batch []*pending) {
 			}
 			p.done <- batchResult{items, nil}
 		}
+	}
+}
+
+func rows(ids []uint64, sc []float32, cnt uint32, k uint32, i int) []BatchItem {
+	items := make([]BatchItem, int(cnt))
+	for j := range items {
+		items[j] = BatchItem{Id: ids[i*int(k)+j], Score: sc[i*int(k)+j]}
+	}
+	return items
+}
+
+// flushFiltered: one backend call for the group; if it fails as a whole, one call per query (each caller gets its own call's result)
+func (b *Batcher) flushFiltered(grp []*pending, flat []float32, k uint32) {
+	fh := make([]Handle, len(grp))
+	for i, p := range grp {
+		fh[i] = p.filter
+	}
+	ids, sc, cnt, err := b.fbackend(fh, flat, len(grp), k)
+	if err == nil || len(grp) == 1 {
+		for i, p := range grp {
+			if err != nil {
+				p.done <- batchResult{nil, err}
+				continue
+			}
+			p.done <- batchResult{rows(ids, sc, cnt[i], k, i), nil}
+		}
+		return
+	}
+	for i, p := range grp {
+		ids1, sc1, cnt1, err1 := b.fbackend(fh[i:i+1], flat[i*b.dim:(i+1)*b.dim], 1, k)
+		if err1 != nil {
+			p.done <- batchResult{nil, err1}
+			continue
+		}
+		p.done <- batchResult{rows(ids1, sc1, cnt1[0], k, 0), nil}
 	}
 }

@@ -213,6 +213,30 @@ func HnswSearchFiltered(h, f Handle, dim uint32, queries []float32, nq int, k ui
 	return ids, sc, cnt, err
 }
 
+// HnswSearchFilteredBatch: a filter per query (coltt_hnsw_search_filtered_batch).  Row i equals HnswSearchFiltered(h, filters[i], query i,
+// 1, k, ef, mode); paths[i] is the path that call takes (FilterWalk / FilterExact).  Every handle is checked before anything runs: one bad
+// filter fails the whole call, and the error names its position.
+func HnswSearchFilteredBatch(h Handle, filters []Handle, dim uint32, queries []float32, nq int, k uint32, ef uint32, mode int) ([]uint64, []float32, []uint32, []int32, error) {
+	if nq == 0 || k == 0 {
+		return nil, nil, make([]uint32, nq), make([]int32, nq), nil
+	}
+	if len(filters) != nq {
+		return nil, nil, nil, nil, fmt.Errorf("HnswSearchFilteredBatch: %d filters for %d queries", len(filters), nq)
+	}
+	if err := checkDim(queries, dim, nq); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	ids := make([]uint64, nq*int(k))
+	sc := make([]float32, nq*int(k))
+	cnt := make([]uint32, nq)
+	paths := make([]int32, nq)
+	err := call(func() C.int {
+		return C.coltt_hnsw_search_filtered_batch(h, &filters[0], fptr(queries), C.size_t(nq), C.uint32_t(k),
+			C.uint32_t(ef), C.int(mode), uptr(ids), fptr(sc), (*C.uint32_t)(unsafe.Pointer(&cnt[0])), (*C.int32_t)(unsafe.Pointer(&paths[0])), nil)
+	})
+	return ids, sc, cnt, paths, err
+}
+
 func HnswRandomLevel(h Handle, u float32) (int, error) {
 	var lv C.int32_t
 	err := call(func() C.int { return C.coltt_hnsw_random_level(h, C.float(u), &lv) })

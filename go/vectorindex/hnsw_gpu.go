@@ -402,6 +402,12 @@ func (xx *Hnsw) NewFilter(ids []uint64) (*HnswFilter, error) {
 	return &HnswFilter{h: f, index: xx, Allowed: n}, nil
 }
 
+// Handle: the library's handle of the filter (colttgpu.Batcher.SearchFiltered takes it)
+func (f *HnswFilter) Handle() colttgpu.Handle { return f.h }
+
+// Handle: the library's handle of the index (colttgpu.HnswFilteredBackend takes it)
+func (xx *Hnsw) Handle() colttgpu.Handle { return xx.h }
+
 func (f *HnswFilter) Close() error {
 	if f.h == 0 {
 		return nil
@@ -422,6 +428,37 @@ func (xx *Hnsw) SearchFiltered(_ context.Context, query edge.Vector, k uint, f *
 		return nil, err
 	}
 	return xx.attach(ids, sc, int(cnt[0])), nil
+}
+
+// SearchFilteredBatch(ctx, queries, k, filters) — a filter per query in one call: result i == SearchFiltered(ctx, queries[i], k, filters[i]).
+// One bad filter (closed, stale, of another index) fails the whole call; the micro-batcher's filtered mode (colttgpu.FilteredBatcher)
+// re-issues such a batch one query at a time.
+func (xx *Hnsw) SearchFilteredBatch(_ context.Context, queries []edge.Vector, k uint, filters []*HnswFilter) ([]SearchResult, error) {
+	if xx.err != nil {
+		return nil, xx.err
+	}
+	if len(filters) != len(queries) {
+		return nil, fmt.Errorf("SearchFilteredBatch: %d filters for %d queries", len(filters), len(queries))
+	}
+	nq := len(queries)
+	flat := make([]float32, 0, nq*int(xx.dim))
+	fh := make([]colttgpu.Handle, nq)
+	for i, q := range queries {
+		if filters[i] == nil {
+			return nil, fmt.Errorf("SearchFilteredBatch: no filter at position %d", i)
+		}
+		flat = append(flat, q...)
+		fh[i] = filters[i].h
+	}
+	ids, sc, cnt, _, err := colttgpu.HnswSearchFilteredBatch(xx.h, fh, uint32(xx.dim), flat, nq, uint32(k), 0, colttgpu.FilterAuto)
+	if err != nil {
+		return nil, err
+	}
+	out := make([]SearchResult, nq)
+	for i := range out {
+		out[i] = xx.attach(ids[i*int(k):], sc[i*int(k):], int(cnt[i]))
+	}
+	return out, nil
 }
 
 func (xx *Hnsw) attach(ids []uint64, sc []float32, n int) SearchResult {

@@ -9,6 +9,9 @@
 //
 // Backend = any callable  int(const float* queries, size_t nq, uint32_t k, uint64_t* ids, float* scores, uint32_t* counts)
 // returning COLTT_OK or an error code, e.g. a lambda around coltt_hnsw_search / coltt_flat_search.
+//
+// FilteredBatcher: the same collector for filtered searches, each caller with its own filter handle (coltt_hnsw_filter_create).  One
+// batch mixes any number of filters; its backend takes one handle per query, e.g. a lambda around coltt_hnsw_search_filtered_batch.
 #pragma once
 #include <chrono>
 #include <condition_variable>
@@ -21,6 +24,8 @@
 #include <mutex>
 #include <thread>
 #include <vector>
+
+#include "coltt_gpu.h"
 
 namespace coltt {
 
@@ -109,6 +114,113 @@ class Batcher {
   const uint32_t dim_; const size_t max_batch_; const std::chrono::microseconds max_wait_; Backend backend_;
   mutable std::mutex mu_; std::condition_variable cv_; std::deque<std::shared_ptr<Pending>> queue_;
   bool stop_ = false; uint64_t n_batches_ = 0, n_queries_ = 0; size_t largest_ = 0;
+  std::thread worker_;  // last member: started after everything else is initialised
+};
+
+// The micro-batcher for filtered searches (coltt_hnsw_search_filtered_batch): callers bring their own filter, batches are grouped by k
+// only.  Backend = int(const coltt_handle_t* filters, const float* queries, size_t nq, uint32_t k, uint64_t* ids, float* scores,
+// uint32_t* counts).  The batch call validates every handle before it runs anything, so one caller's bad filter (destroyed, stale, of
+// another index) fails the whole call: the batch is then re-issued one query at a time, and only the callers whose own call fails get
+// its error.
+class FilteredBatcher {
+ public:
+  using Backend = std::function<int(const coltt_handle_t*, const float*, size_t, uint32_t, uint64_t*, float*, uint32_t*)>;
+
+  FilteredBatcher(uint32_t dim, size_t max_batch, std::chrono::microseconds max_wait, Backend backend)
+      : dim_(dim), max_batch_(max_batch ? max_batch : 1), max_wait_(max_wait), backend_(std::move(backend)),
+        worker_([this] { loop(); }) {}
+  ~FilteredBatcher() {
+    { std::lock_guard<std::mutex> g(mu_); stop_ = true; }
+    cv_.notify_all();
+    worker_.join();
+  }
+  FilteredBatcher(const FilteredBatcher&) = delete;
+  FilteredBatcher& operator=(const FilteredBatcher&) = delete;
+
+  // blocks until answered; the query is copied before returning to the collector
+  BatchAnswer SearchFiltered(const float* query, uint32_t k, coltt_handle_t filter) {
+    auto p = std::make_shared<Pending>();
+    p->q.assign(query, query + dim_);
+    p->k = k; p->filter = filter;
+    std::future<BatchAnswer> f = p->done.get_future();
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      queue_.push_back(p);
+    }
+    cv_.notify_all();
+    return f.get();
+  }
+
+  // statistics (for tests / tuning); retried_batches: batches the backend refused as a whole and that were re-issued per query
+  uint64_t batches() const { std::lock_guard<std::mutex> g(mu_); return n_batches_; }
+  uint64_t queries() const { std::lock_guard<std::mutex> g(mu_); return n_queries_; }
+  size_t largest_batch() const { std::lock_guard<std::mutex> g(mu_); return largest_; }
+  uint64_t retried_batches() const { std::lock_guard<std::mutex> g(mu_); return n_retried_; }
+
+ private:
+  struct Pending { std::vector<float> q; uint32_t k = 0; coltt_handle_t filter = 0; std::promise<BatchAnswer> done; };
+
+  void loop() {
+    std::unique_lock<std::mutex> lk(mu_);
+    for (;;) {
+      cv_.wait(lk, [this] { return stop_ || !queue_.empty(); });
+      if (queue_.empty()) { if (stop_) return; continue; }
+      const uint32_t k = queue_.front()->k;
+      const auto deadline = std::chrono::steady_clock::now() + max_wait_;
+      while (!stop_ && count_k(k) < max_batch_) {
+        if (cv_.wait_until(lk, deadline) == std::cv_status::timeout) break;
+      }
+      std::vector<std::shared_ptr<Pending>> batch;
+      for (auto it = queue_.begin(); it != queue_.end() && batch.size() < max_batch_;) {
+        if ((*it)->k == k) { batch.push_back(*it); it = queue_.erase(it); } else ++it;
+      }
+      n_batches_++; n_queries_ += batch.size(); if (batch.size() > largest_) largest_ = batch.size();
+      lk.unlock();
+      flush(batch, k);
+      lk.lock();
+    }
+  }
+  size_t count_k(uint32_t k) const { size_t c = 0; for (auto& p : queue_) c += p->k == k; return c; }
+
+  // hands one caller its answer: rc, and on success the first min(cnt, k) of ids / sc
+  static void answer(std::shared_ptr<Pending>& p, int rc, uint32_t k, const uint64_t* ids, const float* sc, uint32_t cnt) {
+    BatchAnswer a; a.rc = rc;
+    if (rc == 0) {
+      const uint32_t n = cnt < k ? cnt : k;
+      a.items.resize(n);
+      for (uint32_t j = 0; j < n; j++) a.items[j] = {ids[j], sc[j]};
+    }
+    p->done.set_value(std::move(a));
+  }
+
+  void flush(std::vector<std::shared_ptr<Pending>>& batch, uint32_t k) {
+    const size_t nq = batch.size();
+    if (k == 0) { for (auto& p : batch) answer(p, 0, 0, nullptr, nullptr, 0); return; }
+    std::vector<float> flat(nq * dim_);
+    std::vector<coltt_handle_t> fh(nq);
+    for (size_t i = 0; i < nq; i++) {
+      std::memcpy(flat.data() + i * dim_, batch[i]->q.data(), dim_ * sizeof(float));
+      fh[i] = batch[i]->filter;
+    }
+    std::vector<uint64_t> ids(nq * (size_t)k);
+    std::vector<float> sc(nq * (size_t)k);
+    std::vector<uint32_t> cnt(nq, 0);
+    const int rc = backend_(fh.data(), flat.data(), nq, k, ids.data(), sc.data(), cnt.data());
+    if (rc == 0 || nq == 1) {
+      for (size_t i = 0; i < nq; i++) answer(batch[i], rc, k, ids.data() + i * k, sc.data() + i * k, cnt[i]);
+      return;
+    }
+    { std::lock_guard<std::mutex> g(mu_); n_retried_++; }   // counted before any caller of the batch is answered
+    for (size_t i = 0; i < nq; i++) {   // the whole batch was refused: one query at a time, each caller gets its own call's result
+      uint32_t c = 0;
+      const int r = backend_(fh.data() + i, flat.data() + i * dim_, 1, k, ids.data(), sc.data(), &c);
+      answer(batch[i], r, k, ids.data(), sc.data(), c);
+    }
+  }
+
+  const uint32_t dim_; const size_t max_batch_; const std::chrono::microseconds max_wait_; Backend backend_;
+  mutable std::mutex mu_; std::condition_variable cv_; std::deque<std::shared_ptr<Pending>> queue_;
+  bool stop_ = false; uint64_t n_batches_ = 0, n_queries_ = 0, n_retried_ = 0; size_t largest_ = 0;
   std::thread worker_;  // last member: started after everything else is initialised
 };
 

@@ -245,15 +245,25 @@ int coltt_hnsw_search_device(coltt_handle_t h, const float* d_queries, size_t nq
  * 32 is the walk's row evaluations per unit of ef (n_dist / ef ~ 4 040 / 128 on the headline collection): below it the scan reads no
  * more rows than the walk would, and has no dependent chain (measured crossover: DESIGN.md, "Filtered search").
  *
- * An empty filter or an empty index gives counts of 0 and is not an error.  Not served: product-quantised walks, collection groups,
- * per-query filters within one batch. */
+ * An empty filter or an empty index gives counts of 0 and is not an error.  Not served: product-quantised walks, collection groups.
+ *
+ * A FILTER PER QUERY (coltt_hnsw_search_filtered_batch).  filters[i] is query i's filter; row i equals
+ * coltt_hnsw_search_filtered(hnsw, filters[i], query i, 1, k, ef_override, mode, ...) on the same index state: the same ids, the same
+ * score bits, the same count (entries past the count are unspecified).  AUTO decides per query from that query's filter (n_live is read
+ * once per call); out_paths[i] (may be NULL) = the path that single call takes.  A handle may repeat; an empty filter gives its row
+ * count 0 and the other rows are served.  Every handle is checked before anything runs, with the single call's codes: NULL filters
+ * (nq > 0), an unknown handle, a filter of another index, a stale filter; coltt_last_error() names the first bad position.  Stats:
+ * n_dist, n_exp, n_hops, n_visit_resets and n_exact_rows are the sums of the single calls'; ef_walk is the largest over the queries that
+ * walk (0 if none does); path is WALK or EXACT when every query takes that path and COLTT_FILTER_AUTO (0) when the batch is mixed.
+ * The call holds every filter it reads: destroying one meanwhile is safe.  One call launches at most two walks, one scan and one merge. */
 #define COLTT_FILTER_AUTO 0
 #define COLTT_FILTER_WALK 1
 #define COLTT_FILTER_EXACT 2
 typedef struct coltt_hnsw_filter_stats {   /* per call, summed over the batch */
   uint64_t n_dist, n_exp, n_hops, n_visit_resets;   /* the walk's counters (coltt_hnsw_stats); 0 when EXACT served the call */
   uint32_t ef_walk;                        /* the walk's breadth; 0 when EXACT served the call */
-  int32_t path;                            /* COLTT_FILTER_WALK or COLTT_FILTER_EXACT: what served the call (what AUTO chose) */
+  int32_t path;                            /* COLTT_FILTER_WALK or COLTT_FILTER_EXACT: what served the call (what AUTO chose);
+                                              a batch with a filter per query whose queries took both: COLTT_FILTER_AUTO */
   uint64_t n_exact_rows;                   /* (query, row) pairs the exact path scored */
 } coltt_hnsw_filter_stats;
 int coltt_hnsw_filter_create(coltt_handle_t hnsw, const uint64_t* ids, size_t n, uint64_t* out_allowed, coltt_handle_t* out);
@@ -261,6 +271,9 @@ int coltt_hnsw_filter_destroy(coltt_handle_t filter);
 int coltt_hnsw_search_filtered(coltt_handle_t hnsw, coltt_handle_t filter, const float* queries, size_t nq, uint32_t k,
                                uint32_t ef_override, int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                coltt_hnsw_filter_stats* stats);
+int coltt_hnsw_search_filtered_batch(coltt_handle_t hnsw, const coltt_handle_t* filters /*[nq]*/, const float* queries, size_t nq,
+                                     uint32_t k, uint32_t ef_override, int mode, uint64_t* out_ids, float* out_scores,
+                                     uint32_t* out_counts, int32_t* out_paths /*[nq], may be NULL*/, coltt_hnsw_filter_stats* stats);
 
 /* Capacity for n_slots vertices (and n_upper_rows upper-level adjacency rows; 0 = the expectation for this index's M) in ONE allocation per
  * array, before the inserts.  Optional — Insert grows the arrays by half their size when they are full — but an index whose final size is

@@ -6,6 +6,7 @@
 //   coltt::Hnsw      <->  *vectorindex.Hnsw           (core/vectorindex/hnsw.go:43-54)
 // Metadata maps stay with the caller: results carry ids and scores only.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <map>
@@ -189,6 +190,30 @@ class Hnsw {
     SearchResult r(n);
     for (uint32_t i = 0; i < n; i++) r[i] = {ids[i], sc[i]};
     return r;
+  }
+  // a filter per query (coltt_hnsw_search_filtered_batch): answer i == SearchFiltered(queries[i], k, *filters[i], ef, mode); paths (may be
+  // null) receives the path each query took
+  std::vector<SearchResult> SearchFilteredBatch(const std::vector<Vector>& queries, unsigned k, const std::vector<const Filter*>& filters,
+                                                unsigned ef = 0, int mode = COLTT_FILTER_AUTO, std::vector<int>* paths = nullptr,
+                                                coltt_hnsw_filter_stats* stats = nullptr) const {
+    const size_t nq = queries.size();
+    if (filters.size() != nq) throw Error(COLTT_E_INVALID, "SearchFilteredBatch: one filter per query");
+    std::vector<float> flat(nq * dim_);
+    std::vector<coltt_handle_t> fh(nq);
+    for (size_t i = 0; i < nq; i++) {
+      if (queries[i].size() != dim_) throw Error(COLTT_E_INVALID, "SearchFilteredBatch: query of the wrong dimension");
+      std::copy(queries[i].begin(), queries[i].end(), flat.begin() + i * dim_);
+      fh[i] = filters[i] ? filters[i]->handle() : 0;
+    }
+    std::vector<uint64_t> ids(nq * k); std::vector<float> sc(nq * k); std::vector<uint32_t> n(nq); std::vector<int32_t> p(nq);
+    check(coltt_hnsw_search_filtered_batch(h_, fh.data(), flat.data(), nq, k, ef, mode, ids.data(), sc.data(), n.data(), p.data(), stats));
+    std::vector<SearchResult> out(nq);
+    for (size_t i = 0; i < nq; i++) {
+      out[i].resize(n[i]);
+      for (uint32_t j = 0; j < n[i]; j++) out[i][j] = {ids[i * k + j], sc[i * k + j]};
+    }
+    if (paths) paths->assign(p.begin(), p.end());
+    return out;
   }
   int Len() const { uint64_t n = 0; check(coltt_hnsw_len(h_, &n)); return (int)n; }
   // the collection's size is known (bulk import, Load): every array allocated once; never shrinks, never limits an Insert
