@@ -398,6 +398,7 @@ struct HCtx {
   DevBuf w_mbox;                   // latency kernel: the walking workgroups' hint mailboxes (hnsw_lat.hpp: cache-warming helper workgroups)
   DevBuf w_fdesc;                  // filtered batch: the walks' per-query descriptors, the exact path's queries and tiles
   PinnedBuf h_in, h_out;   // small calls: see PinnedBuf
+  bool flt_launch = false;   // launch_search2 took the row-filter twin for the call in flight
   int init() {  // the caller has selected the index's device
     COLTT_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     COLTT_HIP(hipEventCreate(&ev0));
@@ -426,6 +427,13 @@ struct Hnsw : Object {
   bool r8 = false;
   DevBuf w_stage;   // natural-order rows of the batch being ingested (r8 indexes)
   std::atomic<uint64_t> ev8_launches{0};   // search launches whose level-0 distances came from rows8
+  // The level-0 row filter (row_filter.hpp, rows8.hpp): rows_h = one binary16 value per stored element of a line-transposed f32 cosine index, dim * 2 bytes
+  // per slot — DERIVED data, written wherever `rows` is written (prep_rows_any), grown with it, never part of a stream or a read-back.  shadow: the index
+  // keeps one (decided at create: shape, COLTT_ROW_SHADOW; dropped for good when its allocation fails — the index then works without the filter).
+  bool shadow = false;
+  DevBuf rows_h;
+  std::atomic<uint64_t> flt_launches{0}, flt_rejected{0}, flt_f32_rows{0}, flt_shadow_rows{0};   // filtered launches whose call completed; evaluations the filter rejected; f32 rows / shadow rows they read at level 0
+  void drop_shadow() { shadow = false; if (rows_h.p) { (void)hipFree(rows_h.p); rows_h.p = nullptr; rows_h.cap = 0; } (void)hipGetLastError(); }
   // hnsw_pq.hpp: a snapshot of a trained product quantiser and one row-major code per slot (derived data, maintained like rows8:
   // writers encode the slots they added before they release the exclusive lock)
   bool pq_on = false; PqShape pq_shape; uint32_t pq_row = 0 /* bytes per code row: m rounded up to 16 */; uint64_t pq_done = 0;
@@ -465,12 +473,14 @@ struct Hnsw : Object {
     g.adjU = adjU.as<uint32_t>(); g.adjU_d = adjU_d.as<float>();
     g.del_bits = any_deleted ? del_bits.as<uint32_t>() : nullptr;
     g.mMax = (uint32_t)cfg.m_max; g.mMax0 = (uint32_t)cfg.m_max0; g.dim = (int)dim;
+    g.rows_h = shadow ? rows_h.as<uint8_t>() : nullptr;
     return g;
   }
   int reserve(uint64_t slots, uint64_t upper_rows) {
     if (slots > cap) {
       uint64_t nc = std::max<uint64_t>({slots, cap + cap / 2, 1024});
       COLTT_TRY(rows.reserve(nc * stride, true, stream));
+      if (shadow && rows_h.reserve(nc * (size_t)dim * 2, true, stream) != COLTT_OK) drop_shadow();   // not an error: no shadow, no filter
       COLTT_TRY(norms.reserve(nc * 4, true, stream));
       if (!dense) COLTT_TRY(ids.reserve(nc * 8, true, stream));
       COLTT_TRY(adj0.reserve(nc * cfg.m_max0 * 4, true, stream));
@@ -505,6 +515,11 @@ int prep_rows_any(Hnsw* x, const float* d_raw, uint64_t n, uint64_t slot_base, b
       launch_prep_rows<Q_NONE>(x->stream, d_raw, n, (int)x->dim, nrm, nullptr, 0, S, x->stride);
       row_norms_kernel<Q_NONE><<<ceil_div(n * 2, 256), 256, 0, x->stream>>>(S, x->stride, nullptr, 0, n, (int)x->dim, N + slot_base);
       rows8_permute_kernel<Q_NONE><<<ceil_div(n * chunks, 256), 256, 0, x->stream>>>(S, R + slot_base * x->stride, x->stride, (int)x->dim, n);
+      if (x->shadow) {   // the binary16 shadow of the same rows, from the same staging block
+        const size_t hs = (size_t)x->dim * 2;
+        if (x->rows_h.cap < (slot_base + n) * hs) x->drop_shadow();   // (reserve keeps it as large as `rows`: not reached)
+        else rows_shadow_kernel<<<ceil_div(n * (x->dim / 8), 256), 256, 0, x->stream>>>(S, x->stride, x->rows_h.as<uint8_t>() + slot_base * hs, hs, (int)x->dim, n);
+      }
     } else {
       launch_prep_rows<Q_F16>(x->stream, d_raw, n, (int)x->dim, nrm, nullptr, 0, S, x->stride);
       row_norms_kernel<Q_F16><<<ceil_div(n * 2, 256), 256, 0, x->stream>>>(S, x->stride, nullptr, 0, n, (int)x->dim, N + slot_base);
@@ -769,6 +784,19 @@ uint32_t resident_waves(const SearchGeom& sg, int quant) {
 // Non-temporal row loads for the eight-lane walks (exact.hpp: row_ld): worth it when the row array is far larger than L2 + MALL, costly when later queries
 // would have found the rows there.  COLTT_ROWS_NT = 0 / 1 forces, COLTT_ROWS_NT_MIN_MB moves the threshold (default 12 GiB of rows: 768-d rows, same box — f16 0.5 M -24 %, 1 M -10 %,
 // 2 M -2 %, 4 M +0.8 %, 10 M +-0; f32 1 M -4 %, 3 M +0.7 %, 10 M +4.5 %: profiles/r06ag_nt_rows_ab.md).
+// The certified row filter of the eight-lane f32 cosine walks (hnsw_walk2.hpp: Group8FilterEval).  COLTT_ROW_FILTER = 0 / 1 forces (read per call: one index in
+// one process runs both kernels, tools/row_filter_ab.py); unset: on for the LDS-hash walk (ef <= 128, the measured instance: 10 M x 768, ef 128, 1.41 x in one
+// process, profiles/r07a_row_filter.md) where the row array is far larger than the caches: every row read is then an HBM read and the kernel sits at what the
+// memory system delivers, so bytes are time.
+bool row_filter_on(const Hnsw* x, bool vis_hbm) {
+  if (!x->shadow || !x->rows_h.p) return false;
+  const Policy p = policy();
+  if (p.row_filter >= 0) return p.row_filter != 0;
+  if (vis_hbm) return false;   // the ef > 128 twins (HBM visited map) have not been timed against their unfiltered partners: COLTT_ROW_FILTER=1 only
+  // the SIZE rule of the non-temporal hint (not its forcing knob COLTT_ROWS_NT: an A/B of the hint must not toggle the filter too).  The threshold is
+  // inherited from that rule's measured crossover, the filter's own crossover on 1 M / 3 M has not been measured.
+  return (unsigned long long)x->n * (unsigned long long)x->stride >= ((unsigned long long)p.rows_nt_min_mb << 20);
+}
 bool rows_nt(const Hnsw* x) {
   const Policy p = policy();
   const unsigned long long bytes = (unsigned long long)x->n * (unsigned long long)x->stride, least = (unsigned long long)p.rows_nt_min_mb << 20;
@@ -786,6 +814,7 @@ int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32
                          uint64_t*, float*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*);
   kern_t kern = nullptr;
   const bool nt = rows_nt(x);   // non-temporal row loads (eight-lane kernels): see exact.hpp: row_ld
+  bool flt = false;             // the row-filter twin (row_filter_on)
 #define COLTT_W2(V, PROF, OPT) case V: kern = hnsw_search2_kernel<METRIC, QUANT, PROF, OPT>; break;
   if (sg.w2_lds) {
     switch (sg.w2) {
@@ -794,6 +823,9 @@ int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32
         if constexpr (QUANT != Q_F8) {
           if (sg.ev8) kern = nt ? hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 4, VIS_LDS, false, true, false, true> : hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 4, VIS_LDS, false, true>;
           else if (x->r8) kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 4, VIS_LDS, false, false, true>;   // the pair-owned core over the line-transposed rows
+        }
+        if constexpr (METRIC == M_COS && QUANT == Q_NONE) {   // the row-filter twin of the eight-lane instance just chosen
+          if (sg.ev8 && row_filter_on(x, false)) { kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false>; flt = true; }
         }
         break;   // (adjacency prefetch for f32 rows in small batches: measured, no gain — 1 M x 128, ef 20, one query 105 vs 111 us)
       default: break;
@@ -804,18 +836,24 @@ int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32
       COLTT_W2(6, PROF_SEARCH_HBM, 6) COLTT_W2(7, PROF_SEARCH_HBM, 7)
       default: break;
     }
-    if constexpr (QUANT != Q_F8) {
+    if constexpr (METRIC == M_COS && QUANT == Q_NONE) {   // W2_ADJN: both shipped HBM-visited variants carry the neighbours' norms
+      if (sg.ev8 && row_filter_on(x, true) && (sg.w2 == 6 || sg.w2 == 7)) flt = true;
+      if (flt && sg.w2 == 6) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false>;
+      if (flt && sg.w2 == 7) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false>;
+    }
+    if constexpr (QUANT != Q_F8) { if (!flt) {
       if (sg.ev8 && sg.w2 == 6) kern = nt ? hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 6, VIS_HBM, false, true, false, true> : hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 6, VIS_HBM, false, true>;
       if (sg.ev8 && sg.w2 == 7) kern = nt ? hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 7, VIS_HBM, false, true, false, true> : hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 7, VIS_HBM, false, true>;
       if (!sg.ev8 && x->r8 && sg.w2 == 6) kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 6, VIS_HBM, false, false, true>;
       if (!sg.ev8 && x->r8 && sg.w2 == 7) kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 7, VIS_HBM, false, false, true>;
-    }
+    } }
   }
 #undef COLTT_W2
   if (!kern) return fail(COLTT_E_UNSUPPORTED, "hnsw_search: walk variant %d is not compiled into this build (COLTT_WALK2)", sg.w2);
   if (x->r8 && !sg.ev8 && !(sg.w2_lds ? sg.w2 == 4 : (sg.w2 == 6 || sg.w2 == 7)))
     return fail(COLTT_E_UNSUPPORTED, "hnsw_search: walk variant %d has no instance for line-transposed rows (create the index with COLTT_ROWS8=0 for this experiment)", sg.w2);
   if (sg.ev8) x->ev8_launches.fetch_add(1);
+  c->flt_launch = flt;
   COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
   kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
                                         k, sg.ef, sg.ef_pad, sg.w2_lds ? sg.hcap : sg.bloom_words, counter, oi, os, oc, stats,
@@ -976,7 +1014,7 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
   COLTT_TRY(rc);
   COLTT_HIP(hipEventRecord(c->ev1, c->stream));
   if (x->dense && x->dense_base) add_base_kernel<<<ceil_div(nq * k, 256), 256, 0, c->stream>>>(d_oi, nq * k, x->dense_base);
-  unsigned long long h_stats[5] = {0, 0, 0, 0, 0};
+  unsigned long long h_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // [6], [7]: the row filter's counters (hnsw_kernels.hpp: hnsw_search2_rowfilter_kernel)
   if (packed) COLTT_HIP(hipMemcpyAsync(c->h_out.p, c->w_pack.p, pack_bytes, hipMemcpyDeviceToHost, c->stream));
   else {
     if (!on_device) {
@@ -984,17 +1022,17 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
       COLTT_HIP(hipMemcpyAsync(out_scores, d_os, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
       COLTT_HIP(hipMemcpyAsync(out_counts, d_oc, nq * 4, hipMemcpyDeviceToHost, c->stream));
     }
-    COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 40, hipMemcpyDeviceToHost, c->stream));
+    COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 64, hipMemcpyDeviceToHost, c->stream));
   }
 #ifdef COLTT_PHASE_TIMING
   unsigned long long h_pt[8] = {0};
   COLTT_HIP(hipMemcpyAsync(h_pt, d_stats + 8, 64, hipMemcpyDeviceToHost, c->stream));
 #endif
   COLTT_HIP(hipStreamSynchronize(c->stream));  // the lease (destructor) outlives the kernel
-  if (!packed) std::memcpy(h_stats, c->h_out.p, 40);
+  if (!packed) std::memcpy(h_stats, c->h_out.p, 64);
   if (packed) {
     const uint8_t* hb = c->h_out.as<uint8_t>();
-    std::memcpy(h_stats, hb + 16, 40);
+    std::memcpy(h_stats, hb + 16, 64);
     std::memcpy(out_ids, hb + 256, nq * k * 8);
     std::memcpy(out_scores, hb + 256 + nq * k * 8, nq * k * 4);
     std::memcpy(out_counts, hb + 256 + nq * k * 12, nq * 4);
@@ -1019,6 +1057,7 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
     return search_common(x, c, queries, on_device, nq, k, ef_override, out_ids, out_scores, out_counts, stats, force | 3);
   if (h_stats[4]) return fail(COLTT_E_DEVICE, "hnsw_search: traversal watchdog tripped (code %llu)", h_stats[4]);
   if (stats) { stats->n_dist = h_stats[0]; stats->n_exp = h_stats[1]; stats->n_hops = h_stats[2]; stats->n_visit_resets = h_stats[3]; }
+  if (c->flt_launch && sg.w2 >= 0 && !mw) { x->flt_launches.fetch_add(1); x->flt_rejected.fetch_add(h_stats[6]); x->flt_f32_rows.fetch_add(h_stats[7]); x->flt_shadow_rows.fetch_add(h_stats[5]); }   // (a call re-run after err 8 returned above: only the launch that answered counts)
   return COLTT_OK;
 }
 
@@ -1592,6 +1631,7 @@ int coltt::hnsw_create_on(int device, uint32_t dim, int metric, int quant, const
   if (c.ef <= 0 || c.ef_construction <= 0) return fail(COLTT_E_INVALID, "hnsw_create: ef and efConstruction must be > 0");
   x->cfg = c;
   x->r8 = rows8_shape(dim, quant);
+  x->shadow = x->r8 && quant == COLTT_Q_NONE && metric == COLTT_COSINE && rows_h_shape((int)dim) && policy().row_shadow;
   COLTT_DEVICE(device); device = coltt_dev_scope_.device();
   x->device = device;
   COLTT_HIP(hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
@@ -2219,6 +2259,18 @@ int coltt_hnsw_rows8_searches(coltt_handle_t h, uint64_t* out_launches, int32_t*
   ReadLock g(x->rw);
   if (out_launches) *out_launches = x->ev8_launches.load();
   if (out_has_copy) *out_has_copy = x->r8 ? 1 : 0;
+  return COLTT_OK;
+}
+
+int coltt_hnsw_row_filter_stats(coltt_handle_t h, uint64_t* out_rejected, uint64_t* out_f32_rows, uint64_t* out_shadow_rows, uint64_t* out_launches, int32_t* out_has_shadow) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_row_filter_stats: unknown handle");
+  ReadLock g(x->rw);
+  if (out_rejected) *out_rejected = x->flt_rejected.load();
+  if (out_f32_rows) *out_f32_rows = x->flt_f32_rows.load();
+  if (out_launches) *out_launches = x->flt_launches.load();
+  if (out_shadow_rows) *out_shadow_rows = x->flt_shadow_rows.load();
+  if (out_has_shadow) *out_has_shadow = (x->shadow && x->rows_h.p) ? 1 : 0;
   return COLTT_OK;
 }
 

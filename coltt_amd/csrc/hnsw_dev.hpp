@@ -40,6 +40,7 @@ struct GraphView {
   const uint32_t* del_bits;           // tombstones (hnswVertex.deleted, hnsw_vertex.go:70-76) or null when none
   uint32_t mMax, mMax0;
   int dim;
+  const uint8_t* rows_h;              // rows8.hpp: binary16 shadow of line-transposed f32 cosine rows (the level-0 row filter), or null
 };
 
 struct WaveCtx {

@@ -240,6 +240,88 @@ void hnsw_search2_kernel(GraphView g, int32_t entry, int32_t entry_level,
   if constexpr (VISMODE == VIS_HBM) { if (lane == 0) vis_epoch[blockIdx.x] = w.epoch; }
 }
 
+// The ROW-FILTER twin of the eight-lane f32 cosine instances above (COLTT_ROW_FILTER; hnsw.hip: row_filter_on).  A kernel of its own, so that the instances
+// above stay, instruction for instruction, what they were: the same prologue (query in rows8 order, entrypoint, upper levels through Group8Eval), then the
+// level-0 walk with Group8FilterEval (hnsw_walk2.hpp) — binary16 shadow rows first, f32 rows for what the shadow cannot reject.
+// stats[6] / stats[7] / stats[5]: evaluations the filter rejected / f32 rows read at level 0 / shadow rows read.
+template <int PROFILE, int OPT, int VISMODE, bool NT>
+__global__ __launch_bounds__(64) void hnsw_search2_rowfilter_kernel(GraphView g, int32_t entry, int32_t entry_level,
+                                                                   const float* __restrict__ q_eff, const float* __restrict__ qnorms,
+                                                                   uint32_t nq, uint32_t k, uint32_t ef, uint32_t ef_pad, uint32_t bloom_words,
+                                                                   uint32_t* __restrict__ counter, uint64_t* __restrict__ out_ids,
+                                                                   float* __restrict__ out_scores, uint32_t* __restrict__ out_counts,
+                                                                   unsigned long long* __restrict__ stats, uint8_t* __restrict__ visg,
+                                                                   size_t vis_stride, uint32_t* __restrict__ vis_epoch) {
+  static_assert((OPT & W2_ADJN) != 0, "the filter takes the neighbours' norms from the adjacency rows");
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int lane = threadIdx.x;
+  WaveCtx w;
+  size_t off = ((size_t)g.dim * 4 + 15) & ~(size_t)15;
+  w.qp = reinterpret_cast<float*>(smem); w.qs = nullptr;   // [query in rows8 order | scratch | result set | visited hash or Bloom filter], as hnsw_search2_kernel<.., EV8>
+  w.scr = reinterpret_cast<uint32_t*>(smem + off);
+  off += 96 * 4;
+  w.res0 = reinterpret_cast<unsigned long long*>(smem + off);
+  w.ef_pad = ef_pad;
+  if constexpr (VISMODE == VIS_LDS) {
+    w.vis = reinterpret_cast<uint32_t*>(w.res0 + (size_t)ef_pad);
+    w.hcap = bloom_words; w.hcap_mask = bloom_words - 1;
+    w.bloom = nullptr; w.bloom_words = 0; w.bloom_shift = 0;
+    w.visg = nullptr; w.vis_bytes = 0; w.epoch = 0;
+  } else {
+    w.vis = nullptr;
+    w.bloom = reinterpret_cast<uint32_t*>(w.res0 + (size_t)ef_pad);
+    w.bloom_words = bloom_words; w.bloom_shift = 32u - (uint32_t)__builtin_ctz(bloom_words | 0x80000000u);
+    w.hcap = 0; w.hcap_mask = 0;
+    w.visg = visg + (size_t)blockIdx.x * vis_stride; w.vis_bytes = vis_stride; w.epoch = vis_epoch[blockIdx.x];
+  }
+  for (;;) {
+    const uint32_t qt = atomicAdd(counter, lane == 0 ? 1u : 0u);  // branch-free work fetch, see hnsw_search_kernel
+    const uint32_t qi = (uint32_t)__shfl((int)qt, 0, 64);
+    if (qi >= nq) break;
+    w.n_dist = w.n_exp = w.n_hops = w.n_resets = 0; w.err = 0;
+#ifdef COLTT_PHASE_TIMING
+    for (int i_ = 0; i_ < 8; i_++) w.pt[i_] = 0;
+    w.t_last = __builtin_amdgcn_s_memtime();
+#endif
+    wave_sync();
+    for (int e = lane; e < g.dim; e += 64) w.qp[rows8_qindex<Q_NONE>(e)] = q_eff[(size_t)qi * g.dim + e];
+    w.qnorm = qnorms[qi];
+    wave_sync();
+    uint32_t cur = (uint32_t)entry;
+    float curd = Group8Eval<M_COS, Q_NONE, false, false, NT>().one(g, w, cur, lane);   // hnsw.go:253
+    curd = __shfl(curd, 0, 64);
+    w.n_dist += 1;
+    for (int l = entry_level; l > 0; l--) greedy_level8<M_COS, Q_NONE, false, NT>(g, w, cur, curd, l, lane);  // :254-256
+    COLTT_PT(w, 5)
+    w.n_dist += 1;  // searchLevel re-evaluates the entrypoint distance (hnsw.go:346)
+    uint32_t len;
+    Group8FilterEval<M_COS, Q_NONE, true, NT> fev;
+    search_level2<M_COS, Q_NONE, PROFILE, OPT, VISMODE, false>(g, w, cur, curd, ef, lane, len, fev);  // :258-259
+    const uint32_t n = len < k ? len : k;  // selectNeighbors + pop (:261-277) == the k smallest, ascending
+    for (uint32_t i = lane; i < n; i += 64) {
+      const unsigned long long e = w.res0[i];
+      const uint32_t slot = (uint32_t)e >> 1;
+      out_ids[(size_t)qi * k + i] = g.ids ? g.ids[slot] : (uint64_t)slot;
+      out_scores[(size_t)qi * k + i] = __uint_as_float((uint32_t)(e >> 32));
+    }
+    if (lane == 0) {
+      out_counts[qi] = n;
+      atomicAdd(&stats[0], (unsigned long long)w.n_dist);
+      atomicAdd(&stats[1], (unsigned long long)w.n_exp);
+      atomicAdd(&stats[2], (unsigned long long)w.n_hops);
+      if (w.err) atomicOr(&stats[4], (unsigned long long)w.err);
+      atomicAdd(&stats[6], (unsigned long long)fev.n_rej);
+      atomicAdd(&stats[7], (unsigned long long)fev.n_f32);
+      atomicAdd(&stats[5], (unsigned long long)fev.n_h16);
+#ifdef COLTT_PHASE_TIMING
+      COLTT_PT(w, 6)
+      for (int i_ = 0; i_ < 8; i_++) atomicAdd(&stats[8 + i_], w.pt[i_]);
+#endif
+    }
+  }
+  if constexpr (VISMODE == VIS_HBM) { if (lane == 0) vis_epoch[blockIdx.x] = w.epoch; }
+}
+
 
 // Hnsw.Search with a 256-thread workgroup per query (hnsw_lat.hpp): the latency path for small batches — the reference serves one
 // query per RPC (core/core.go:633-667).  One workgroup per CU, queries pulled from a global counter.  Same answers, score bits and

@@ -307,6 +307,77 @@ template <int METRIC, int QUANT, bool ADJN, bool HBM16 = false, bool NT = false>
   }
 };
 
+// Group8Eval for f32 cosine rows with the CERTIFIED ROW FILTER (row_filter.hpp; rows8.hpp: the binary16 shadow GraphView::rows_h).  Once the result set is
+// full at a pop, a fresh neighbour's distance decides one thing — d < lowerBound — and 84 % of them fail it (40 k x 768, ef 128).  Phase A reads the
+// SHADOW rows of the chunk's fresh neighbours (half the bytes) and forms a lower bound d_lo on the distance the exact kernel would return; a neighbour
+// with d_lo >= lowerBound is rejected on the spot (it keeps its visited mark and its place in n_dist: an evaluation in the reference's counting, hnsw.go:366-373)
+// and gets d_lo as its distance, which fails `d < lowerBound` like the exact one would and reaches nothing else.  Phase B compacts the survivors and evaluates
+// them with the exact stream (same lines, same order, same reduction: same bits).  While the set is still filling up every fresh neighbour is admitted and
+// needs its score: straight to the exact stream.  one() and the upper levels are Group8Eval's.
+// n_rej / n_f32 / n_h16: evaluations rejected by the filter / f32 rows read / shadow rows read, of this traversal at level 0 (wave-uniform).  A survivor of a
+// full-set chunk reads BOTH its shadow row and its f32 row: n_h16 - n_rej = the survivors, n_f32 - (n_h16 - n_rej) = rows read while the set was filling.
+template <int METRIC, int QUANT, bool ADJN, bool NT> struct Group8FilterEval {
+  static_assert(METRIC == M_COS && QUANT == Q_NONE && ADJN, "the row filter covers f32 cosine rows whose norms ride with the adjacency rows");
+  typedef Group8Eval<METRIC, QUANT, ADJN, false, NT> base_t;
+  static constexpr bool ROW_FILTER = true;
+  static constexpr bool CHUNK_ADJ = false;
+  static constexpr bool RADJ = false;
+  static constexpr bool ROWPF = false;
+  static constexpr bool EARLY = false;
+  static constexpr bool BOUNDED = false;
+  uint32_t n_rej = 0, n_f32 = 0, n_h16 = 0;
+  __device__ __forceinline__ uint32_t chunk_adj(int, int) const { return NBR_NONE; }
+  __device__ __forceinline__ void prefetch(uint32_t, bool, int) const {}
+  __device__ __forceinline__ float operator()(const GraphView& g, const WaveCtx& w, uint32_t nb, bool fresh, float nrm, int half, int lane) const {
+    return base_t()(g, w, nb, fresh, nrm, half, lane);
+  }
+  __device__ __forceinline__ float one(const GraphView& g, const WaveCtx& w, uint32_t slot, int lane) const { return base_t().one(g, w, slot, lane); }
+  // the chunk's distances given the pop's lowerBound and whether the set was full at the pop (search_level2)
+  __device__ __forceinline__ float filtered(const GraphView& g, const WaveCtx& w, uint32_t nb, bool fresh, float nrm, int half, int lane, float lower_bound, bool full_at_pop) {
+    const int nl = (g.dim * 4) >> 7, nlh = nl >> 1;   // rows_h_shape: dim % 256 == 0, so nl % 8 == 0 and nlh % 4 == 0
+    const bool mine = fresh && half == 0;
+    const unsigned long long E = __ballot(mine);
+    const uint32_t nf = (uint32_t)__popcll(E);
+    if (!full_at_pop) {   // (wave-uniform) the set is filling up: every fresh neighbour is admitted
+      n_f32 += nf;
+      return base_t()(g, w, nb, fresh, nrm, half, lane);
+    }
+    const uint32_t rank = (uint32_t)__popcll(E & ((1ull << lane) - 1ull));
+    uint32_t* const s_nb = w.scr; float* const s_nr = reinterpret_cast<float*>(w.scr + 32); float* const s_d = reinterpret_cast<float*>(w.scr + 64);
+    if (mine) { s_nb[rank] = nb; s_nr[rank] = nrm; }
+    wave_sync();
+    const int grp = lane >> 3, rj = lane & 7;
+    const size_t hstride = (size_t)g.dim * 2;
+    // phase A: shadow rows.  Whole rows of 12 lines per burst where they divide (768-d: one row per step, as the exact stream), else bursts of 4.
+    if (nlh % 12 == 0) group8_stream_h<12, NT>(g.rows_h, hstride, s_nb, s_nr, s_d, nf, grp, rj, w.qp, nlh, w.qnorm, g.dim);
+    else group8_stream_h<4, NT>(g.rows_h, hstride, s_nb, s_nr, s_d, nf, grp, rj, w.qp, nlh, w.qnorm, g.dim);
+    wave_sync();
+    const float d_lo = mine ? s_d[rank] : 0.f;
+    const bool surv = mine && !row_filter_rejects(d_lo, lower_bound);
+    const unsigned long long S = __ballot(surv);
+    const uint32_t ns = (uint32_t)__popcll(S);
+    n_rej += nf - ns; n_f32 += ns; n_h16 += nf;
+    float r = d_lo;
+    wave_sync();   // every lane holds its bound before the scratch is rewritten
+    if (ns) {      // phase B (wave-uniform): the survivors' f32 rows through the exact stream
+      const uint32_t srank = (uint32_t)__popcll(S & ((1ull << lane) - 1ull));
+      if (surv) { s_nb[srank] = nb; s_nr[srank] = nrm; }
+      wave_sync();
+      if (nl % 12 == 0) group8_stream<METRIC, QUANT, 12, NT, ADJN>(g.rows8, g.stride, g.norms, s_nb, s_nr, s_d, ns, grp, rj, w.qp, nl, w.qnorm);
+      else group8_stream<METRIC, QUANT, 4, NT, ADJN>(g.rows8, g.stride, g.norms, s_nb, s_nr, s_d, ns, grp, rj, w.qp, nl, w.qnorm);
+      wave_sync();
+      if (surv) r = s_d[srank];
+      wave_sync();   // the next chunk rewrites the scratch
+    }
+    if (!mine) r = 0.f;
+    r = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, r), 0xA0, 0xf, 0xf, true));   // even lane's value to its pair: quad_perm [0,0,2,2]
+    return r;
+  }
+};
+// does the evaluator take the pop's lowerBound (Group8FilterEval)?  Every other evaluator is called as before.
+template <class E, class = void> struct eval_row_filter : std::false_type {};
+template <class E> struct eval_row_filter<E, std::void_t<decltype(E::ROW_FILTER)>> : std::true_type {};
+
 // greedyClosestNeighbor (hnsw.go:320-343) with the eight-lane core: hnsw_dev.hpp:greedy_level with the distances of a chunk coming
 // from Group8Eval (the upper rows carry no norms: the 4-byte gather serves the handful of evaluations up here)
 template <int METRIC, int QUANT, bool HBM16, bool NT = false>
@@ -549,6 +620,7 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
       w.n_dist += nfresh; vis_count += nfresh;   // (vis_count: entries of the LDS hash)
       float d;
       if constexpr (eval_t::BOUNDED && !eval_t::EARLY) { if (full_at_pop) d = fresh ? bounded_d : 0.f; else d = ev(g, w, nb, fresh, nrm, half, lane); }
+      else if constexpr (eval_row_filter<eval_t>::value) d = ev.filtered(g, w, nb, fresh, nrm, half, lane, lower_bound, full_at_pop);
       else d = ev(g, w, nb, fresh, nrm, half, lane);
       const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(E >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)E, 0u));   // fresh neighbours in front of this lane
       const bool adm = fresh && half == 0 && (rank < free_slots || d < lower_bound);

@@ -23,6 +23,7 @@
 #pragma once
 #include <type_traits>
 #include "exact.hpp"
+#include "row_filter.hpp"
 
 namespace coltt {
 namespace dev {
@@ -236,6 +237,90 @@ __device__ __forceinline__ void group8_stream(const uint8_t* __restrict__ rows8,
   if (total - t == 2u) { COLTT_G8S_STEP(A, B, 1) COLTT_G8S_STEP(B, A, 0) }
   else if (total - t == 1u) { COLTT_G8S_STEP(A, B, 0) }
 #undef COLTT_G8S_STEP
+}
+
+// ---- the binary16 SHADOW of line-transposed f32 cosine rows (rows_h; row_filter.hpp has the margin and its proof) ------------------------------
+// One binary16 value (round to nearest even) per stored f32 element, dim * 2 bytes per slot.  The layout is the filter's own (its sum
+// is a bound, no order to reproduce) and chosen so that the eight-lane core reuses the f32-permuted query copy in LDS: shadow line l' holds the
+// elements of the f32 lines 2 l' and 2 l' + 1, its 16-byte chunk r residue r's 4 + 4 steps:
+//        rows_h element (l' * 8 + r) * 8 + (l & 1) * 4 + t   =   row element 8 * (4 * l + t) + r        l = f32 line, l' = l >> 1
+// Lane r reads chunk r of a shadow line and the two f32x4 of the query it would read for the f32 lines 2 l' and 2 l' + 1.
+// Shapes: dim % 256 == 0 (256, 512, 768, 1024, 1536 ...: a whole number of 4-line shadow bursts and of 4-line f32 bursts per row).
+__device__ __host__ __forceinline__ constexpr bool rows_h_shape(int dim) { return dim % 256 == 0 && dim <= ROW_FILTER_MAX_DIM; }
+
+// n natural-order f32 rows at `rows` (the ingest staging block) -> their shadow at `rows_h`.  One thread per 16-byte destination chunk.
+__global__ __launch_bounds__(256) void rows_shadow_kernel(const uint8_t* __restrict__ rows, size_t stride, uint8_t* __restrict__ rows_h, size_t hstride, int dim, uint64_t n) {
+  const int chunks = dim >> 3;
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * (uint64_t)chunks) return;
+  const uint64_t row = t / chunks;
+  const int c = (int)(t % chunks), lp = c >> 3, r = c & 7;
+  const float* src = reinterpret_cast<const float*>(rows + row * stride);
+  unsigned short h[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const int l = 2 * lp + (j >> 2), s = j & 3;
+    h[j] = __builtin_bit_cast(unsigned short, (_Float16)src[8 * (4 * l + s) + r]);   // fptrunc: round to nearest even, overflow -> infinity
+  }
+  const u32x4e v = {(uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16), (uint32_t)h[4] | ((uint32_t)h[5] << 16),
+                    (uint32_t)h[6] | ((uint32_t)h[7] << 16)};
+  *reinterpret_cast<u32x4e*>(rows_h + row * hstride + (size_t)c * 16) = v;
+}
+
+// Phase A of the filter: group8_stream's stream of bursts over the SHADOW rows of the chunk's compacted fresh neighbours (one row per lane group, the
+// next burst always in flight, no load under a branch); s_d[i] = row_filter_dlo of neighbour i, a lower bound on the distance the exact kernel would
+// return (NaN / not finite: no verdict).  nlh = 128-byte shadow lines per row (dim / 64); requires nlh % U == 0, nlh >= U.
+template <int U, bool NT>
+__device__ __forceinline__ void group8_stream_h(const uint8_t* __restrict__ rows_h, size_t hstride, const uint32_t* s_nb, const float* s_nr, float* s_d, uint32_t nf,
+                                                int grp, int rj, const float* __restrict__ qp, int nlh, float qnorm, int dim) {
+  const float* qb = qp + rj * 4;
+  const int nbur = nlh / U;
+  const uint32_t total = ((nf + 7u) >> 3) * (uint32_t)nbur;
+  u32x4e A[U], B[U];
+  auto row_of = [&](uint32_t pass) -> const uint8_t* {
+    const uint32_t idx = pass * 8u + (uint32_t)grp;
+    return rows_h + (size_t)s_nb[idx < nf ? idx : 0u] * hstride + rj * 16;   // an idle group re-reads a live row
+  };
+  const uint8_t* rp = row_of(0);
+#pragma unroll
+  for (int u = 0; u < U; u++) A[u] = row_ld<NT>(reinterpret_cast<const u32x4e*>(rp + (size_t)u * 128));
+  float acc = 0.f;
+  uint32_t pass = 0; int b = 0;
+#define COLTT_G8H_STEP(CUR, NXT, LOADNEXT)                                                                                   \
+  {                                                                                                                         \
+    int nb_ = b + 1; uint32_t np_ = pass; const uint8_t* nrp = rp;                                                          \
+    if (nb_ == nbur) { nb_ = 0; np_ = pass + 1u; }                                                                          \
+    if (LOADNEXT) {                                                                                                         \
+      if (nb_ == 0) nrp = row_of(np_);                                                                                      \
+      _Pragma("unroll") for (int u = 0; u < U; u++) NXT[u] = row_ld<NT>(reinterpret_cast<const u32x4e*>(nrp + (size_t)(nb_ * U + u) * 128)); \
+    }                                                                                                                       \
+    _Pragma("unroll") for (int u = 0; u < U; u++) {                                                                         \
+      const int L = b * U + u;                                                                                              \
+      const f32x4 q0 = *reinterpret_cast<const f32x4*>(qb + L * 64), q1 = *reinterpret_cast<const f32x4*>(qb + L * 64 + 32); \
+      const u32x2e lo = {CUR[u].x, CUR[u].y}, hi = {CUR[u].z, CUR[u].w};                                                    \
+      const f32x4 x0 = __builtin_convertvector(__builtin_bit_cast(f16x4, lo), f32x4);                                       \
+      const f32x4 x1 = __builtin_convertvector(__builtin_bit_cast(f16x4, hi), f32x4);                                       \
+      _Pragma("unroll") for (int s_ = 0; s_ < 4; s_++) acc = __builtin_fmaf(q0[s_], x0[s_], acc);                           \
+      _Pragma("unroll") for (int s_ = 0; s_ < 4; s_++) acc = __builtin_fmaf(q1[s_], x1[s_], acc);                           \
+    }                                                                                                                       \
+    if (b == nbur - 1) {   /* wave-uniform: every group is at the same burst of its row */                                   \
+      const float sum = group8_hsum(acc);                                                                                   \
+      const uint32_t idx = pass * 8u + (uint32_t)grp;                                                                       \
+      const bool live = idx < nf;                                                                                           \
+      const float out = row_filter_dlo(sum, dim, qnorm, s_nr[live ? idx : 0u]);                                             \
+      if (rj == 0 && live) s_d[idx] = out;                                                                                  \
+      acc = 0.f;                                                                                                            \
+    }                                                                                                                       \
+    b = nb_; pass = np_; rp = nrp;                                                                                          \
+  }
+  uint32_t t = 0;
+  for (; t + 3u <= total; t += 2) {   // both steps have a successor
+    COLTT_G8H_STEP(A, B, 1)
+    COLTT_G8H_STEP(B, A, 1)
+  }
+  if (total - t == 2u) { COLTT_G8H_STEP(A, B, 1) COLTT_G8H_STEP(B, A, 0) }
+  else if (total - t == 1u) { COLTT_G8H_STEP(A, B, 0) }
+#undef COLTT_G8H_STEP
 }
 
 }  // namespace dev

@@ -250,6 +250,13 @@ class Hnsw:
         L.check(L.lib().coltt_hnsw_rows8_searches(self.h, C.byref(a), C.byref(f)))
         return a.value, bool(f.value)
 
+    def RowFilterStats(self):
+        """the level-0 row filter (coltt_hnsw_row_filter_stats): cumulative evaluations it rejected, f32 rows and shadow rows the filtered
+        launches read at level 0, filtered launches, and whether the index keeps the binary16 shadow of its rows"""
+        r, e, s, n, f = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
+        L.check(L.lib().coltt_hnsw_row_filter_stats(self.h, C.byref(r), C.byref(e), C.byref(s), C.byref(n), C.byref(f)))
+        return {"rejected": r.value, "f32_rows": e.value, "shadow_rows": s.value, "launches": n.value, "shadow": bool(f.value)}
+
     # -- product-quantised search (coltt_hnsw_pq_*; the reference's call shape: playground/hnswpq_verification.go:69-105)
     def PqAttach(self, pq):
         """snapshot the trained quantiser `pq` (a PQSpace) into the index and encode every stored row"""

@@ -287,6 +287,13 @@ int coltt_hnsw_reserve(coltt_handle_t h, uint64_t n_slots, uint64_t n_upper_rows
  * COLTT_EV8=0 (per call) searches the pair-owned rows.  This reports how many search launches the eight-lane core served and whether
  * the copy is complete. */
 int coltt_hnsw_rows8_searches(coltt_handle_t h, uint64_t* out_launches, int32_t* out_has_copy);
+/* The level-0 row filter of f32 cosine indexes (an internal of the search kernels: same ids, score bits and traversal counters with and without it).
+ * A line-transposed f32 cosine index with dim % 256 == 0 keeps a binary16 shadow of its rows (dim * 2 bytes per slot of device memory; none with
+ * COLTT_ROW_SHADOW=0 at create, or when its allocation failed); once a traversal's result set is full, a neighbour the shadow PROVES to be no
+ * closer than the set's worst member is rejected without reading its f32 row.  COLTT_ROW_FILTER = 0 / 1 forces it off / on per call, default: on for
+ * row arrays far larger than the caches at ef <= 128 (the ef > 128 kernels take it with COLTT_ROW_FILTER=1 only).  Cumulative per index over the filtered
+ * launches: evaluations the filter rejected, f32 rows read at level 0, shadow rows read (a neighbour the shadow cannot reject reads both), launches; *out_has_shadow = the index has its shadow.  Any out pointer may be NULL. */
+int coltt_hnsw_row_filter_stats(coltt_handle_t h, uint64_t* out_rejected, uint64_t* out_f32_rows, uint64_t* out_shadow_rows, uint64_t* out_launches, int32_t* out_has_shadow);
 /* graph export in the bulk_load layout (what Hnsw.Commit serialises, hnsw_commit.go:69-162).
  * Call with NULL arrays to get sizes.  With any array non-NULL, *n_slots / *n_rows / *n_edges are IN-OUT: on entry the
  * capacities of the caller's arrays (slots: ids, levels, deleted; rows + 1: row_offsets; edges: nbr, nbr_dist) — normally the
