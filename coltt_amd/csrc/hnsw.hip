@@ -148,6 +148,7 @@ __global__ __launch_bounds__(64) void hnsw_build_search_kernel(GraphView g, int3
       if ((uint32_t)lane < m) {
         row[rank] = myslot; drow[rank] = myd;
         if (l == 0 && g.adj0_n) g.adj0_n[(size_t)vi * g.mMax0 + rank] = g.norms[myslot];
+        if (l == 0 && g.adj0_m) g.adj0_m[(size_t)vi * g.mMax0 + rank] = g.rows_m[myslot];
         uint32_t rid = l == 0 ? myslot : (uint32_t)cap_slots + g.upper_off[myslot] + (uint32_t)(l - 1);
         uint32_t r = r0 + lane;
         uint32_t old = atomicExch(&head[rid], r);
@@ -217,6 +218,10 @@ __global__ void hnsw_link_kernel(GraphView g, uint64_t cap_slots, const BuildReq
   if (lvl0 && g.adj0_n) {
     float* nrow = g.adj0_n + (size_t)rid * g.mMax0;
     for (uint32_t i = 0; i < W; i++) nrow[i] = i < n ? g.norms[s[i]] : 0.f;
+  }
+  if (lvl0 && g.adj0_m) {
+    float2* mrow = g.adj0_m + (size_t)rid * g.mMax0;
+    for (uint32_t i = 0; i < W; i++) mrow[i] = i < n ? g.rows_m[s[i]] : float2{0.f, 0.f};
   }
 }
 
@@ -348,13 +353,16 @@ __global__ __launch_bounds__(64) void hnsw_link_diverse_kernel(GraphView g, uint
   }
   wave_sync();
   float* nrow = (lvl0 && g.adj0_n) ? g.adj0_n + (size_t)rid * g.mMax0 : nullptr;
+  float2* mrow = (lvl0 && g.adj0_m) ? g.adj0_m + (size_t)rid * g.mMax0 : nullptr;
   if ((uint32_t)lane < ns) {
     row[rank] = myslot; drow[rank] = __uint_as_float((uint32_t)(mine >> 32));
     if (nrow) nrow[rank] = g.norms[myslot];
+    if (mrow) mrow[rank] = g.rows_m[myslot];
   }
   if ((uint32_t)lane >= ns && (uint32_t)lane < W) {
     row[lane] = NBR_NONE; drow[lane] = 0.f;
     if (nrow) nrow[lane] = 0.f;
+    if (mrow) mrow[lane] = float2{0.f, 0.f};
   }
 }
 
@@ -370,13 +378,14 @@ __global__ void hnsw_link_count_kernel(const BuildReq* __restrict__ req, uint32_
   atomicMax(&stats[5], (unsigned long long)(c + (rid < cap_slots ? mMax0 : mMax)));
 }
 
-// adj0_n[slot][j] = norms[adj0[slot][j]] for the level-0 rows of slots [first, first + n): after a bulk install of the topology
+// adj0_n[slot][j] = norms[adj0[slot][j]] (and adj0_m[slot][j] = rows_m[adj0[slot][j]]) for the level-0 rows of slots [first, first + n): after a bulk install of the topology
 __global__ void adj_norms_kernel(GraphView g, uint64_t first, uint64_t n) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n * g.mMax0) return;
   const uint64_t i = first * g.mMax0 + t;
   const uint32_t nb = g.adj0[i];
   g.adj0_n[i] = nb != NBR_NONE ? g.norms[nb] : 0.f;
+  if (g.adj0_m) g.adj0_m[i] = nb != NBR_NONE ? g.rows_m[nb] : float2{0.f, 0.f};
 }
 
 __global__ void fill_u32_kernel(uint32_t* p, size_t n, uint32_t v) {
@@ -432,6 +441,18 @@ struct Hnsw : Object {
   // keeps one (decided at create: shape, COLTT_ROW_SHADOW; dropped for good when its allocation fails — the index then works without the filter).
   bool shadow = false;
   DevBuf rows_h;
+  // The 8-bit shadow (row_filter8.hpp, rows8.hpp): rows_b = one code byte per stored element, rows_m = (scale, error norm) per slot, adj0_m = rows_m of every
+  // level-0 edge's target, written wherever adj0_n is.  Derived data like rows_h: written and grown with `rows`, dropped for good when an allocation fails.
+  // Which of the two an index keeps is decided at create (COLTT_ROW_SHADOW_BITS; default: this one).
+  bool shadow8 = false;
+  DevBuf rows_b, rows_m, adj0_m;
+  void drop_shadow8() {
+    shadow8 = false;
+    for (DevBuf* b : {&rows_b, &rows_m, &adj0_m}) if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+    (void)hipGetLastError();
+  }
+  bool has_shadow8() const { return shadow8 && rows_b.p && rows_m.p && adj0_m.p; }
+  bool has_shadow16() const { return shadow && rows_h.p; }
   std::atomic<uint64_t> flt_launches{0}, flt_rejected{0}, flt_f32_rows{0}, flt_shadow_rows{0};   // filtered launches whose call completed; evaluations the filter rejected; f32 rows / shadow rows they read at level 0
   void drop_shadow() { shadow = false; if (rows_h.p) { (void)hipFree(rows_h.p); rows_h.p = nullptr; rows_h.cap = 0; } (void)hipGetLastError(); }
   // hnsw_pq.hpp: a snapshot of a trained product quantiser and one row-major code per slot (derived data, maintained like rows8:
@@ -474,6 +495,9 @@ struct Hnsw : Object {
     g.del_bits = any_deleted ? del_bits.as<uint32_t>() : nullptr;
     g.mMax = (uint32_t)cfg.m_max; g.mMax0 = (uint32_t)cfg.m_max0; g.dim = (int)dim;
     g.rows_h = shadow ? rows_h.as<uint8_t>() : nullptr;
+    g.rows_b = shadow8 ? rows_b.as<uint8_t>() : nullptr;
+    g.rows_m = shadow8 ? rows_m.as<float2>() : nullptr;
+    g.adj0_m = shadow8 ? adj0_m.as<float2>() : nullptr;
     return g;
   }
   int reserve(uint64_t slots, uint64_t upper_rows) {
@@ -481,6 +505,8 @@ struct Hnsw : Object {
       uint64_t nc = std::max<uint64_t>({slots, cap + cap / 2, 1024});
       COLTT_TRY(rows.reserve(nc * stride, true, stream));
       if (shadow && rows_h.reserve(nc * (size_t)dim * 2, true, stream) != COLTT_OK) drop_shadow();   // not an error: no shadow, no filter
+      if (shadow8 && (rows_b.reserve(nc * (size_t)dim, true, stream) != COLTT_OK || rows_m.reserve(nc * 8, true, stream) != COLTT_OK ||
+                      adj0_m.reserve(nc * cfg.m_max0 * 8, true, stream) != COLTT_OK)) drop_shadow8();
       COLTT_TRY(norms.reserve(nc * 4, true, stream));
       if (!dense) COLTT_TRY(ids.reserve(nc * 8, true, stream));
       COLTT_TRY(adj0.reserve(nc * cfg.m_max0 * 4, true, stream));
@@ -519,6 +545,11 @@ int prep_rows_any(Hnsw* x, const float* d_raw, uint64_t n, uint64_t slot_base, b
         const size_t hs = (size_t)x->dim * 2;
         if (x->rows_h.cap < (slot_base + n) * hs) x->drop_shadow();   // (reserve keeps it as large as `rows`: not reached)
         else rows_shadow_kernel<<<ceil_div(n * (x->dim / 8), 256), 256, 0, x->stream>>>(S, x->stride, x->rows_h.as<uint8_t>() + slot_base * hs, hs, (int)x->dim, n);
+      }
+      if (x->shadow8) {  // the 8-bit shadow and its (scale, error norm), from the same staging block
+        const size_t bs = (size_t)x->dim;
+        if (x->rows_b.cap < (slot_base + n) * bs || x->rows_m.cap < (slot_base + n) * 8) x->drop_shadow8();   // (not reached, as above)
+        else rows_b_kernel<<<ceil_div(n, 4), 256, 0, x->stream>>>(S, x->stride, x->rows_b.as<uint8_t>() + slot_base * bs, bs, x->rows_m.as<RowMeta8>() + slot_base, (int)x->dim, n);
       }
     } else {
       launch_prep_rows<Q_F16>(x->stream, d_raw, n, (int)x->dim, nrm, nullptr, 0, S, x->stride);
@@ -788,8 +819,17 @@ uint32_t resident_waves(const SearchGeom& sg, int quant) {
 // one process runs both kernels, tools/row_filter_ab.py); unset: on for the LDS-hash walk (ef <= 128, the measured instance: 10 M x 768, ef 128, 1.41 x in one
 // process, profiles/r07a_row_filter.md) where the row array is far larger than the caches: every row read is then an HBM read and the kernel sits at what the
 // memory system delivers, so bytes are time.
+// COLTT_ROW_FILTER_BITS = 8 / 16 picks the shadow a filtered launch reads (row_filter_bits); unset: the 8-bit one where the index keeps it.  An index keeps
+// what COLTT_ROW_SHADOW_BITS said when it was created; the kind it does not keep is served by the one it does.
+int row_filter_bits(const Hnsw* x) {
+  const bool h8 = x->has_shadow8(), h16 = x->has_shadow16();
+  if (!h8 && !h16) return 0;
+  const int want = policy().row_filter_bits;
+  if (want == 16) return h16 ? 16 : 8;
+  return h8 ? 8 : 16;
+}
 bool row_filter_on(const Hnsw* x, bool vis_hbm) {
-  if (!x->shadow || !x->rows_h.p) return false;
+  if (!x->has_shadow8() && !x->has_shadow16()) return false;
   const Policy p = policy();
   if (p.row_filter >= 0) return p.row_filter != 0;
   if (vis_hbm) return false;   // the ef > 128 twins (HBM visited map) have not been timed against their unfiltered partners: COLTT_ROW_FILTER=1 only
@@ -825,7 +865,11 @@ int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32
           else if (x->r8) kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 4, VIS_LDS, false, false, true>;   // the pair-owned core over the line-transposed rows
         }
         if constexpr (METRIC == M_COS && QUANT == Q_NONE) {   // the row-filter twin of the eight-lane instance just chosen
-          if (sg.ev8 && row_filter_on(x, false)) { kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false>; flt = true; }
+          if (sg.ev8 && row_filter_on(x, false)) {
+            if (row_filter_bits(x) == 8) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, 8>;
+            else kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false>;
+            flt = true;
+          }
         }
         break;   // (adjacency prefetch for f32 rows in small batches: measured, no gain — 1 M x 128, ef 20, one query 105 vs 111 us)
       default: break;
@@ -840,6 +884,10 @@ int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32
       if (sg.ev8 && row_filter_on(x, true) && (sg.w2 == 6 || sg.w2 == 7)) flt = true;
       if (flt && sg.w2 == 6) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false>;
       if (flt && sg.w2 == 7) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false>;
+      if (flt && row_filter_bits(x) == 8) {
+        if (sg.w2 == 6) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false, 8>;
+        if (sg.w2 == 7) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false, 8>;
+      }
     }
     if constexpr (QUANT != Q_F8) { if (!flt) {
       if (sg.ev8 && sg.w2 == 6) kern = nt ? hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 6, VIS_HBM, false, true, false, true> : hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 6, VIS_HBM, false, true>;
@@ -1039,12 +1087,12 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
   }
 #ifdef COLTT_PHASE_TIMING
   {
-    static const char* nm_w[8] = {"pop", "adjacency", "visited", "rows+dist", "merge", "prologue(upper levels)", "writeout", "-"};
+    static const char* nm_w[8] = {"pop", "adjacency", "visited", "rows+dist", "merge", "prologue(upper levels)", "writeout", "shadow rows (row filter, phase A)"};
     static const char* nm_l[8] = {"pop+publish", "adjacency", "visited+fetch+stage", "eval", "barrier2+admission", "-", "prologue(upper levels)", "-"};
     const char* const* nm = mw ? nm_l : nm_w;
-    double tot = 0; for (int i = 0; i < 7; i++) tot += (double)h_pt[i];
+    double tot = 0; for (int i = 0; i < 8; i++) tot += (double)h_pt[i];
     fprintf(stderr, "[phase] nq=%zu ef=%u visg=%d:", nq, sg.ef, (int)sg.visg);
-    for (int i = 0; i < 7; i++) fprintf(stderr, " %s %.1f%%", nm[i], 100.0 * (double)h_pt[i] / tot);
+    for (int i = 0; i < 8; i++) fprintf(stderr, " %s %.1f%%", nm[i], 100.0 * (double)h_pt[i] / tot);
     fprintf(stderr, "  | ticks/query %.0f\n", tot / (double)nq);
   }
 #endif
@@ -1297,12 +1345,13 @@ __global__ void hnsw_unlink_kernel(GraphView g, const uint32_t* __restrict__ nbs
   uint32_t* row = const_cast<uint32_t*>(adj_row(g, nbs[t], lvl[t], W));
   float* drow = lvl[t] == 0 ? g.adj0_d + (size_t)nbs[t] * g.mMax0 : g.adjU_d + ((size_t)g.upper_off[nbs[t]] + (uint32_t)(lvl[t] - 1)) * g.mMax;
   float* nrow = (lvl[t] == 0 && g.adj0_n) ? g.adj0_n + (size_t)nbs[t] * g.mMax0 : nullptr;
+  float2* mrow = (lvl[t] == 0 && g.adj0_m) ? g.adj0_m + (size_t)nbs[t] * g.mMax0 : nullptr;
   uint32_t m = 0;
   for (uint32_t i = 0; i < W && row[i] != NBR_NONE; i++) {
     uint32_t sl = row[i]; float dd = drow[i];
-    if (!is_deleted(g, sl)) { row[m] = sl; drow[m] = dd; if (nrow) nrow[m] = nrow[i]; m++; }
+    if (!is_deleted(g, sl)) { row[m] = sl; drow[m] = dd; if (nrow) nrow[m] = nrow[i]; if (mrow) mrow[m] = mrow[i]; m++; }
   }
-  for (; m < W; m++) { row[m] = NBR_NONE; drow[m] = 0.f; if (nrow) nrow[m] = 0.f; }
+  for (; m < W; m++) { row[m] = NBR_NONE; drow[m] = 0.f; if (nrow) nrow[m] = 0.f; if (mrow) mrow[m] = float2{0.f, 0.f}; }
 }
 
 int hnsw_undense(Hnsw* x) {
@@ -1415,6 +1464,7 @@ int insert_core(Hnsw* x, const uint64_t* ids, uint64_t first_id, const float* d_
     COLTT_HIP(hipMemsetAsync(x->adj0.as<uint32_t>() + base * x->cfg.m_max0, 0xff, (size_t)b * x->cfg.m_max0 * 4, x->stream));
     COLTT_HIP(hipMemsetAsync(x->adj0_d.as<float>() + base * x->cfg.m_max0, 0, (size_t)b * x->cfg.m_max0 * 4, x->stream));
     if (x->metric == COLTT_COSINE) COLTT_HIP(hipMemsetAsync(x->adj0_n.as<float>() + base * x->cfg.m_max0, 0, (size_t)b * x->cfg.m_max0 * 4, x->stream));
+    if (x->shadow8) COLTT_HIP(hipMemsetAsync(x->adj0_m.as<float2>() + base * x->cfg.m_max0, 0, (size_t)b * x->cfg.m_max0 * 8, x->stream));
     if (up) {
       COLTT_HIP(hipMemsetAsync(x->adjU.as<uint32_t>() + x->n_upper * x->cfg.m_max, 0xff, (size_t)up * x->cfg.m_max * 4, x->stream));
       COLTT_HIP(hipMemsetAsync(x->adjU_d.as<float>() + x->n_upper * x->cfg.m_max, 0, (size_t)up * x->cfg.m_max * 4, x->stream));
@@ -1631,7 +1681,9 @@ int coltt::hnsw_create_on(int device, uint32_t dim, int metric, int quant, const
   if (c.ef <= 0 || c.ef_construction <= 0) return fail(COLTT_E_INVALID, "hnsw_create: ef and efConstruction must be > 0");
   x->cfg = c;
   x->r8 = rows8_shape(dim, quant);
-  x->shadow = x->r8 && quant == COLTT_Q_NONE && metric == COLTT_COSINE && rows_h_shape((int)dim) && policy().row_shadow;
+  const bool shadow_ok = x->r8 && quant == COLTT_Q_NONE && metric == COLTT_COSINE && rows_h_shape((int)dim) && policy().row_shadow;
+  x->shadow = shadow_ok && (policy().row_shadow_bits & 16) != 0;
+  x->shadow8 = shadow_ok && (policy().row_shadow_bits & 8) != 0;
   COLTT_DEVICE(device); device = coltt_dev_scope_.device();
   x->device = device;
   COLTT_HIP(hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
@@ -2270,7 +2322,30 @@ int coltt_hnsw_row_filter_stats(coltt_handle_t h, uint64_t* out_rejected, uint64
   if (out_f32_rows) *out_f32_rows = x->flt_f32_rows.load();
   if (out_launches) *out_launches = x->flt_launches.load();
   if (out_shadow_rows) *out_shadow_rows = x->flt_shadow_rows.load();
-  if (out_has_shadow) *out_has_shadow = (x->shadow && x->rows_h.p) ? 1 : 0;
+  if (out_has_shadow) *out_has_shadow = (x->has_shadow16() ? 16 : 0) | (x->has_shadow8() ? 8 : 0);   // non-zero: some shadow is kept; bit 3 / bit 4: which
+  return COLTT_OK;
+}
+
+int coltt_hnsw_fetch_shadow8(coltt_handle_t h, uint64_t first_slot, uint64_t n, int8_t* out_codes, float* out_meta, float* out_adj_meta) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_fetch_shadow8: unknown handle");
+  ReadLock g(x->rw);
+  if (!x->has_shadow8()) return fail(COLTT_E_UNSUPPORTED, "hnsw_fetch_shadow8: the index keeps no 8-bit shadow");
+  if (first_slot > x->n || n > x->n - first_slot) return fail(COLTT_E_INVALID, "hnsw_fetch_shadow8: range outside [0,%llu)", (unsigned long long)x->n);
+  if (n == 0) return COLTT_OK;
+  COLTT_DEVICE(x->device);
+  const size_t dim = x->dim, w = x->cfg.m_max0;
+  if (out_codes) {   // rows8.hpp's layout -> natural element order, on the host (a read-back for tests and tools)
+    std::vector<uint8_t> raw(n * dim);
+    COLTT_HIP(hipMemcpy(raw.data(), x->rows_b.as<uint8_t>() + first_slot * dim, n * dim, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; i++)
+      for (size_t e = 0; e < dim; e++) {
+        const size_t r = e & 7, step = e >> 3, l = step >> 2, t_ = step & 3;
+        out_codes[i * dim + e] = (int8_t)raw[i * dim + ((l >> 2) * 8 + r) * 16 + (l & 3) * 4 + t_];
+      }
+  }
+  if (out_meta) COLTT_HIP(hipMemcpy(out_meta, x->rows_m.as<uint8_t>() + first_slot * 8, n * 8, hipMemcpyDeviceToHost));
+  if (out_adj_meta) COLTT_HIP(hipMemcpy(out_adj_meta, x->adj0_m.as<uint8_t>() + first_slot * w * 8, n * w * 8, hipMemcpyDeviceToHost));
   return COLTT_OK;
 }
 

@@ -41,6 +41,9 @@ struct GraphView {
   uint32_t mMax, mMax0;
   int dim;
   const uint8_t* rows_h;              // rows8.hpp: binary16 shadow of line-transposed f32 cosine rows (the level-0 row filter), or null
+  const uint8_t* rows_b;              // rows8.hpp: 8-bit shadow of the same rows (one code byte per element), or null
+  const float2* rows_m;               // [cap]          (scale, error norm) of every slot's 8-bit shadow row (rows8.hpp: RowMeta8), or null
+  float2* adj0_m;                     // [cap][mMax0]   rows_m[adj0[..]]: the neighbours' (scale, error norm) ride with the adjacency row like adj0_n, or null
 };
 
 struct WaveCtx {

@@ -244,7 +244,8 @@ void hnsw_search2_kernel(GraphView g, int32_t entry, int32_t entry_level,
 // above stay, instruction for instruction, what they were: the same prologue (query in rows8 order, entrypoint, upper levels through Group8Eval), then the
 // level-0 walk with Group8FilterEval (hnsw_walk2.hpp) — binary16 shadow rows first, f32 rows for what the shadow cannot reject.
 // stats[6] / stats[7] / stats[5]: evaluations the filter rejected / f32 rows read at level 0 / shadow rows read.
-template <int PROFILE, int OPT, int VISMODE, bool NT>
+// BITS: the shadow phase A reads (16: rows_h; 8: rows_b + adj0_m).  stats[5] counts the shadow rows of whichever kind.
+template <int PROFILE, int OPT, int VISMODE, bool NT, int BITS = 16>
 __global__ __launch_bounds__(64) void hnsw_search2_rowfilter_kernel(GraphView g, int32_t entry, int32_t entry_level,
                                                                    const float* __restrict__ q_eff, const float* __restrict__ qnorms,
                                                                    uint32_t nq, uint32_t k, uint32_t ef, uint32_t ef_pad, uint32_t bloom_words,
@@ -295,7 +296,7 @@ __global__ __launch_bounds__(64) void hnsw_search2_rowfilter_kernel(GraphView g,
     COLTT_PT(w, 5)
     w.n_dist += 1;  // searchLevel re-evaluates the entrypoint distance (hnsw.go:346)
     uint32_t len;
-    Group8FilterEval<M_COS, Q_NONE, true, NT> fev;
+    Group8FilterEval<M_COS, Q_NONE, true, NT, BITS> fev;
     search_level2<M_COS, Q_NONE, PROFILE, OPT, VISMODE, false>(g, w, cur, curd, ef, lane, len, fev);  // :258-259
     const uint32_t n = len < k ? len : k;  // selectNeighbors + pop (:261-277) == the k smallest, ascending
     for (uint32_t i = lane; i < n; i += 64) {

@@ -316,16 +316,21 @@ template <int METRIC, int QUANT, bool ADJN, bool HBM16 = false, bool NT = false>
 // needs its score: straight to the exact stream.  one() and the upper levels are Group8Eval's.
 // n_rej / n_f32 / n_h16: evaluations rejected by the filter / f32 rows read / shadow rows read, of this traversal at level 0 (wave-uniform).  A survivor of a
 // full-set chunk reads BOTH its shadow row and its f32 row: n_h16 - n_rej = the survivors, n_f32 - (n_h16 - n_rej) = rows read while the set was filling.
-template <int METRIC, int QUANT, bool ADJN, bool NT> struct Group8FilterEval {
+// BITS: which shadow phase A reads — 16: rows_h (row_filter.hpp), 8: rows_b with the neighbours' (scale, error norm) from the adjacency row
+// (GraphView::adj0_m; row_filter8.hpp).  No binary16 stage between the 8-bit shadow and the f32 row.
+// mt: the neighbour's (scale, error norm), set by search_level2 per chunk (BITS == 8 only; the binary16 twin never touches it).
+template <int METRIC, int QUANT, bool ADJN, bool NT, int BITS = 16> struct Group8FilterEval {
   static_assert(METRIC == M_COS && QUANT == Q_NONE && ADJN, "the row filter covers f32 cosine rows whose norms ride with the adjacency rows");
   typedef Group8Eval<METRIC, QUANT, ADJN, false, NT> base_t;
   static constexpr bool ROW_FILTER = true;
+  static constexpr bool ROW_META = BITS == 8;   // search_level2 reads adj0_m beside adj0_n
   static constexpr bool CHUNK_ADJ = false;
   static constexpr bool RADJ = false;
   static constexpr bool ROWPF = false;
   static constexpr bool EARLY = false;
   static constexpr bool BOUNDED = false;
   uint32_t n_rej = 0, n_f32 = 0, n_h16 = 0;
+  float2 mt = {0.f, 0.f};
   __device__ __forceinline__ uint32_t chunk_adj(int, int) const { return NBR_NONE; }
   __device__ __forceinline__ void prefetch(uint32_t, bool, int) const {}
   __device__ __forceinline__ float operator()(const GraphView& g, const WaveCtx& w, uint32_t nb, bool fresh, float nrm, int half, int lane) const {
@@ -344,19 +349,34 @@ template <int METRIC, int QUANT, bool ADJN, bool NT> struct Group8FilterEval {
     }
     const uint32_t rank = (uint32_t)__popcll(E & ((1ull << lane) - 1ull));
     uint32_t* const s_nb = w.scr; float* const s_nr = reinterpret_cast<float*>(w.scr + 32); float* const s_d = reinterpret_cast<float*>(w.scr + 64);
-    if (mine) { s_nb[rank] = nb; s_nr[rank] = nrm; }
+    if (mine) { s_nb[rank] = nb; if constexpr (BITS != 8) s_nr[rank] = nrm; }   // (the 8-bit bound is formed from registers: no norm in the scratch)
     wave_sync();
     const int grp = lane >> 3, rj = lane & 7;
-    const size_t hstride = (size_t)g.dim * 2;
-    // phase A: shadow rows.  Whole rows of 12 lines per burst where they divide (768-d: one row per step, as the exact stream), else bursts of 4.
-    if (nlh % 12 == 0) group8_stream_h<12, NT>(g.rows_h, hstride, s_nb, s_nr, s_d, nf, grp, rj, w.qp, nlh, w.qnorm, g.dim);
-    else group8_stream_h<4, NT>(g.rows_h, hstride, s_nb, s_nr, s_d, nf, grp, rj, w.qp, nlh, w.qnorm, g.dim);
-    wave_sync();
-    const float d_lo = mine ? s_d[rank] : 0.f;
+    [[maybe_unused]] const size_t hstride = (size_t)g.dim * 2;
+    // phase A: shadow rows.
+    float d_lo;
+    if constexpr (BITS == 8) {
+      // 8-bit codes.  Rows of 6 or 2 shadow lines (768-d, 256-d): the chunk's at most 32 rows in ONE burst (4 rows x 6 lines = 96 VGPRs per lane).  Every
+      // other width: a stream of bursts, two rows per lane group — whole rows of 6 lines per burst where they divide (1536-d ...), else bursts of 2
+      // (512-d, 1024-d ...).  The raw sums come back through the scratch; the bound is formed by the lane that holds (norm, s, e) in registers.
+      const int nlb = nl >> 2;
+      if (nlb == 6) group8_burst_b<6, NT>(g.rows_b, (size_t)g.dim, s_nb, s_d, nf, grp, rj, w.qp);
+      else if (nlb == 2) group8_burst_b<2, NT>(g.rows_b, (size_t)g.dim, s_nb, s_d, nf, grp, rj, w.qp);
+      else if (nlb % 6 == 0) group8_stream_b<6, 2, NT>(g.rows_b, (size_t)g.dim, s_nb, s_d, nf, grp, rj, w.qp, nlb);
+      else group8_stream_b<2, 2, NT>(g.rows_b, (size_t)g.dim, s_nb, s_d, nf, grp, rj, w.qp, nlb);
+      wave_sync();
+      d_lo = mine ? row_filter8_dlo(s_d[rank], mt.x, mt.y, g.dim, w.qnorm, nrm) : 0.f;
+    } else {   // binary16: whole rows of 12 lines per burst where they divide (768-d: one row per step, as the exact stream), else bursts of 4
+      if (nlh % 12 == 0) group8_stream_h<12, NT>(g.rows_h, hstride, s_nb, s_nr, s_d, nf, grp, rj, w.qp, nlh, w.qnorm, g.dim);
+      else group8_stream_h<4, NT>(g.rows_h, hstride, s_nb, s_nr, s_d, nf, grp, rj, w.qp, nlh, w.qnorm, g.dim);
+      wave_sync();
+      d_lo = mine ? s_d[rank] : 0.f;
+    }
     const bool surv = mine && !row_filter_rejects(d_lo, lower_bound);
     const unsigned long long S = __ballot(surv);
     const uint32_t ns = (uint32_t)__popcll(S);
     n_rej += nf - ns; n_f32 += ns; n_h16 += nf;
+    COLTT_PT(const_cast<WaveCtx&>(w), 7)  // phase A: shadow rows + bounds (diagnostic build only; slot 3 then holds phase B and the unfiltered chunks)
     float r = d_lo;
     wave_sync();   // every lane holds its bound before the scratch is rewritten
     if (ns) {      // phase B (wave-uniform): the survivors' f32 rows through the exact stream
@@ -377,6 +397,8 @@ template <int METRIC, int QUANT, bool ADJN, bool NT> struct Group8FilterEval {
 // does the evaluator take the pop's lowerBound (Group8FilterEval)?  Every other evaluator is called as before.
 template <class E, class = void> struct eval_row_filter : std::false_type {};
 template <class E> struct eval_row_filter<E, std::void_t<decltype(E::ROW_FILTER)>> : std::true_type {};
+template <class E, class = void> struct eval_row_meta : std::false_type {};
+template <class E> struct eval_row_meta<E, std::void_t<decltype(E::ROW_META)>> : std::integral_constant<bool, E::ROW_META> {};
 
 // greedyClosestNeighbor (hnsw.go:320-343) with the eight-lane core: hnsw_dev.hpp:greedy_level with the distances of a chunk coming
 // from Group8Eval (the upper rows carry no norms: the 4-byte gather serves the handful of evaluations up here)
@@ -536,6 +558,10 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
     wave_sync();
     const uint32_t* row = g.adj0 + (size_t)cslot * width;
     const float* nrow = ADJN ? g.adj0_n + (size_t)cslot * width : nullptr;
+    constexpr bool META = eval_row_meta<eval_t>::value;   // the 8-bit row filter: the neighbours' (scale, error norm) beside their norms
+    static_assert(!META || !PREF, "the 8-bit row filter has no adjacency prefetch: pre_nn would need the neighbours' (scale, error norm) too");
+    const float2* mrow = nullptr;
+    if constexpr (META) mrow = g.adj0_m + (size_t)cslot * width;
     const bool use_pre = pre_slot == cslot;
     const uint32_t pre_now = pre_nb; const float pre_nn_now = pre_nn;
     pre_slot = NBR_NONE;
@@ -560,6 +586,7 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
       const uint32_t nb = idx < width ? (pre_hit ? pre_now : row[idx]) : NBR_NONE;
       float nrm = 0.f;
       if constexpr (ADJN) nrm = idx < width ? (pre_hit ? pre_nn_now : nrow[idx]) : 0.f;
+      if constexpr (META) ev.mt = idx < width ? mrow[idx] : float2{0.f, 0.f};   // (no adjacency prefetch in the instances that carry it: see the static_assert above)
       const bool valid = nb != NBR_NONE && !is_deleted(g, nb);
       if constexpr (eval_t::ROWPF) { if (!pre_hit) ev.prefetch_at(cslot, idx, idx < width, half); }   // (requested with the adjacency row when that was prefetched)
       else ev.prefetch(nb, valid, half);   // evaluators whose per-neighbour input is small (hnsw_pq.hpp: a 32-128 byte code row) request it NOW, under the visited test

@@ -24,6 +24,7 @@
 #include <type_traits>
 #include "exact.hpp"
 #include "row_filter.hpp"
+#include "row_filter8.hpp"
 
 namespace coltt {
 namespace dev {
@@ -321,6 +322,179 @@ __device__ __forceinline__ void group8_stream_h(const uint8_t* __restrict__ rows
   if (total - t == 2u) { COLTT_G8H_STEP(A, B, 1) COLTT_G8H_STEP(B, A, 0) }
   else if (total - t == 1u) { COLTT_G8H_STEP(A, B, 0) }
 #undef COLTT_G8H_STEP
+}
+
+// ---- the 8-BIT SHADOW of line-transposed f32 cosine rows (rows_b + rows_m; row_filter8.hpp has the margin and its proof) ------------------------
+// One signed code byte per stored f32 element, dim bytes per slot, and per slot the pair (s, e): the row's scale and the norm of what the codes
+// miss (row_filter8.hpp).  Line-transposed like rows_h: shadow line L holds the elements of the f32 lines 4 L .. 4 L + 3, its 16-byte chunk r
+// residue r's 4 x 4 steps:
+//        rows_b byte (L * 8 + r) * 16 + (l & 3) * 4 + t   =   code of row element 8 * (4 * l + t) + r        l = f32 line, L = l >> 2
+// Lane r reads chunk r of a shadow line and the four f32x4 of the query it would read for the f32 lines 4 L .. 4 L + 3.  Same shapes as rows_h
+// (dim % 256 == 0: an even number of shadow lines per row).
+struct RowMeta8 { float s, e; };   // 8 bytes per slot (rows_m) and per level-0 edge (GraphView::adj0_m)
+
+// n natural-order f32 rows at `rows` (the ingest staging block) -> their codes at `rows_b` and (s, e) at `meta`.  One wave per row.
+__global__ __launch_bounds__(256) void rows_b_kernel(const uint8_t* __restrict__ rows, size_t stride, uint8_t* __restrict__ rows_b, size_t bstride,
+                                                     RowMeta8* __restrict__ meta, int dim, uint64_t n) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;   // (wave-uniform)
+  const float* src = reinterpret_cast<const float*>(rows + row * stride);
+  float mx = 0.f; bool bad = false;
+  for (int i = lane; i < dim; i += 64) { const float a = __builtin_fabsf(src[i]); bad = bad || !(a <= 3.4028234663852886e38f); mx = a > mx ? a : mx; }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) { const float o = __shfl_xor(mx, m, 64); mx = o > mx ? o : mx; }
+  bad = __ballot(bad) != 0ull;
+  const float s = bad ? 0.f : (float)((double)mx / 127.0);   // division rounded once (a f64 quotient of two f32 values rounds to f32 innocuously)
+  const bool none = !(s > 0.f);                              // zero row, not finite, or a scale that underflows: codes 0, e = +infinity
+  double err = 0.0;
+  const int chunks = dim >> 4;
+  for (int c = lane; c < chunks; c += 64) {
+    const int L = c >> 3, r = c & 7;
+    uint32_t wds[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      uint32_t wd = 0;
+#pragma unroll
+      for (int t = 0; t < 4; t++) {
+        const float x = src[8 * (4 * (4 * L + j) + t) + r];
+        int ci = 0;
+        if (!none) {
+          float f = __builtin_rintf((float)((double)x / (double)s));
+          f = f > 127.f ? 127.f : (f < -127.f ? -127.f : f);
+          ci = (int)f;
+          const double d = (double)x - (double)s * (double)ci;   // the product is exact in f64
+          err += d * d;
+        }
+        wd |= ((uint32_t)ci & 0xffu) << (8 * t);
+      }
+      wds[j] = wd;
+    }
+    *reinterpret_cast<u32x4e*>(rows_b + row * bstride + (size_t)c * 16) = u32x4e{wds[0], wds[1], wds[2], wds[3]};
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) err += __shfl_xor(err, m, 64);
+  if (lane == 0) {
+    RowMeta8 mt;
+    mt.s = none ? 0.f : s;
+    const double ev = __builtin_sqrt(err) * (1.0 + 9.5367431640625e-07);   // 1 + 2^-20, then towards +infinity:
+    float ef = (float)ev;                                                   // (ev >= 0: the next f32 up is the next bit pattern; an infinity stays)
+    if ((double)ef < ev) ef = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, ef) + 1u);
+    mt.e = none ? __builtin_inff() : ef;
+    meta[row] = mt;
+  }
+}
+
+// Phase A of the filter over the 8-bit shadow: group8_stream_h's stream of bursts over rows_b — the next burst always in flight in ping-pong
+// registers, no load under a branch, an idle group re-reads a live row.  A burst is R rows per lane group x U lines (R > 1 keeps as many bytes in
+// flight per wave as the binary16 stream does with rows half as long).  s_g[i] = the f32 sum of q_j * (float)c_j of neighbour i (8 partial sums of
+// dim / 8 fused products, the tree of group8_hsum); the caller turns it into the bound (row_filter8_dlo) with the row's (s, e) and norm, which
+// it holds in registers.  nlb = 128-byte shadow lines per row (dim / 128); requires nlb % U == 0, nlb >= U.
+template <int U, int R, bool NT>
+__device__ __forceinline__ void group8_stream_b(const uint8_t* __restrict__ rows_b, size_t bstride, const uint32_t* s_nb, float* s_g, uint32_t nf,
+                                                int grp, int rj, const float* __restrict__ qp, int nlb) {
+  const float* qb = qp + rj * 4;
+  const int nbur = nlb / U;
+  const uint32_t total = ((nf + (uint32_t)(8 * R - 1)) / (uint32_t)(8 * R)) * (uint32_t)nbur;
+  u32x4e A[R][U], B[R][U];
+  const uint8_t* rp[R];
+  auto row_of = [&](uint32_t pass, int i) -> const uint8_t* {
+    const uint32_t idx = (pass * (uint32_t)R + (uint32_t)i) * 8u + (uint32_t)grp;
+    return rows_b + (size_t)s_nb[idx < nf ? idx : 0u] * bstride + rj * 16;   // an idle group re-reads a live row
+  };
+#pragma unroll
+  for (int i = 0; i < R; i++) {
+    rp[i] = row_of(0, i);
+#pragma unroll
+    for (int u = 0; u < U; u++) A[i][u] = row_ld<NT>(reinterpret_cast<const u32x4e*>(rp[i] + (size_t)u * 128));
+  }
+  float acc[R];
+#pragma unroll
+  for (int i = 0; i < R; i++) acc[i] = 0.f;
+  uint32_t pass = 0; int b = 0;
+  // LOADNEXT is a literal, as in group8_stream: the step that has a successor issues its loads unconditionally
+#define COLTT_G8B_STEP(CUR, NXT, LOADNEXT)                                                                                   \
+  {                                                                                                                         \
+    int nb_ = b + 1; uint32_t np_ = pass;                                                                                   \
+    if (nb_ == nbur) { nb_ = 0; np_ = pass + 1u; }                                                                          \
+    if (LOADNEXT) {                                                                                                         \
+      _Pragma("unroll") for (int i = 0; i < R; i++) {                                                                       \
+        if (nb_ == 0) rp[i] = row_of(np_, i);                                                                               \
+        _Pragma("unroll") for (int u = 0; u < U; u++) NXT[i][u] = row_ld<NT>(reinterpret_cast<const u32x4e*>(rp[i] + (size_t)(nb_ * U + u) * 128)); \
+      }                                                                                                                     \
+    }                                                                                                                       \
+    _Pragma("unroll") for (int u = 0; u < U; u++) {                                                                         \
+      const int L = b * U + u;                                                                                              \
+      _Pragma("unroll") for (int j_ = 0; j_ < 4; j_++) {                                                                    \
+        const f32x4 q0 = *reinterpret_cast<const f32x4*>(qb + L * 128 + j_ * 32);                                           \
+        _Pragma("unroll") for (int i = 0; i < R; i++) {                                                                     \
+          const int wd = (int)CUR[i][u][j_];                                                                                \
+          acc[i] = __builtin_fmaf(q0[0], (float)((wd << 24) >> 24), acc[i]);                                                \
+          acc[i] = __builtin_fmaf(q0[1], (float)((wd << 16) >> 24), acc[i]);                                                \
+          acc[i] = __builtin_fmaf(q0[2], (float)((wd << 8) >> 24), acc[i]);                                                 \
+          acc[i] = __builtin_fmaf(q0[3], (float)(wd >> 24), acc[i]);                                                        \
+        }                                                                                                                   \
+      }                                                                                                                     \
+    }                                                                                                                       \
+    if (b == nbur - 1) {   /* wave-uniform: every group is at the same burst of its rows */                                  \
+      _Pragma("unroll") for (int i = 0; i < R; i++) {                                                                       \
+        const float sum = group8_hsum(acc[i]);                                                                              \
+        const uint32_t idx = (pass * (uint32_t)R + (uint32_t)i) * 8u + (uint32_t)grp;                                       \
+        if (rj == 0 && idx < nf) s_g[idx] = sum;                                                                            \
+        acc[i] = 0.f;                                                                                                       \
+      }                                                                                                                     \
+    }                                                                                                                       \
+    b = nb_; pass = np_;                                                                                                    \
+  }
+  uint32_t t = 0;
+  for (; t + 3u <= total; t += 2) {   // both steps have a successor
+    COLTT_G8B_STEP(A, B, 1)
+    COLTT_G8B_STEP(B, A, 1)
+  }
+  if (total - t == 2u) { COLTT_G8B_STEP(A, B, 1) COLTT_G8B_STEP(B, A, 0) }
+  else if (total - t == 1u) { COLTT_G8B_STEP(A, B, 0) }
+#undef COLTT_G8B_STEP
+}
+
+// The same sums for rows of exactly U shadow lines, the WHOLE chunk in one burst: a chunk has at most 32 fresh neighbours = 4 rows per lane group, and
+// 4 x U 16-byte loads per lane (768-d: 24, 96 VGPRs) are all requested before the first is consumed — one memory round trip for phase A, where the
+// stream above needs one per pass.  The walk is a chain of dependent round trips per wave (adjacency row, shadow rows, survivors' f32 rows), and with
+// rows this short that chain, not the bytes, is what a query waits for (profiles/r08a_row_filter8.md).  No load under a branch: an idle group
+// re-reads a live row.
+template <int U, bool NT>
+__device__ __forceinline__ void group8_burst_b(const uint8_t* __restrict__ rows_b, size_t bstride, const uint32_t* s_nb, float* s_g, uint32_t nf,
+                                               int grp, int rj, const float* __restrict__ qp) {
+  const float* qb = qp + rj * 4;
+  u32x4e A[4][U];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const uint32_t idx = (uint32_t)(i * 8 + grp);
+    const uint8_t* rp = rows_b + (size_t)s_nb[idx < nf ? idx : 0u] * bstride + rj * 16;
+#pragma unroll
+    for (int u = 0; u < U; u++) A[i][u] = row_ld<NT>(reinterpret_cast<const u32x4e*>(rp + (size_t)u * 128));
+  }
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const f32x4 q0 = *reinterpret_cast<const f32x4*>(qb + u * 128 + j * 32);
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int wd = (int)A[i][u][j];
+        acc[i] = __builtin_fmaf(q0[0], (float)((wd << 24) >> 24), acc[i]);
+        acc[i] = __builtin_fmaf(q0[1], (float)((wd << 16) >> 24), acc[i]);
+        acc[i] = __builtin_fmaf(q0[2], (float)((wd << 8) >> 24), acc[i]);
+        acc[i] = __builtin_fmaf(q0[3], (float)(wd >> 24), acc[i]);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const float sum = group8_hsum(acc[i]);
+    const uint32_t idx = (uint32_t)(i * 8 + grp);
+    if (rj == 0 && idx < nf) s_g[idx] = sum;
+  }
 }
 
 }  // namespace dev

@@ -252,10 +252,21 @@ class Hnsw:
 
     def RowFilterStats(self):
         """the level-0 row filter (coltt_hnsw_row_filter_stats): cumulative evaluations it rejected, f32 rows and shadow rows the filtered
-        launches read at level 0, filtered launches, and whether the index keeps the binary16 shadow of its rows"""
+        launches read at level 0, filtered launches, whether the index keeps a shadow of its rows and of which kinds (8 / 16 bits)"""
         r, e, s, n, f = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
         L.check(L.lib().coltt_hnsw_row_filter_stats(self.h, C.byref(r), C.byref(e), C.byref(s), C.byref(n), C.byref(f)))
-        return {"rejected": r.value, "f32_rows": e.value, "shadow_rows": s.value, "launches": n.value, "shadow": bool(f.value)}
+        return {"rejected": r.value, "f32_rows": e.value, "shadow_rows": s.value, "launches": n.value, "shadow": bool(f.value),
+                "shadow_bits": tuple(b for b in (8, 16) if f.value & b)}
+
+    def FetchShadow8(self, first=0, n=None):
+        """the 8-bit shadow of slots [first, first + n) (coltt_hnsw_fetch_shadow8): codes [n, dim] int8 in natural element order, (scale, error norm)
+        [n, 2], and the pairs riding with the level-0 adjacency rows [n, m_max0, 2]"""
+        ns = C.c_uint64(0)
+        L.check(L.lib().coltt_hnsw_export_raw(self.h, C.byref(ns), None, None, None, None, None, None))
+        n = ns.value - first if n is None else n
+        codes = np.empty((n, self.dim), np.int8); meta = np.empty((n, 2), np.float32); adj = np.empty((n, self.cfg.m_max0, 2), np.float32)
+        L.check(L.lib().coltt_hnsw_fetch_shadow8(self.h, C.c_uint64(first), C.c_uint64(n), L.vp(codes), L.vp(meta), L.vp(adj)))
+        return codes, meta, adj
 
     # -- product-quantised search (coltt_hnsw_pq_*; the reference's call shape: playground/hnswpq_verification.go:69-105)
     def PqAttach(self, pq):

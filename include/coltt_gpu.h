@@ -292,8 +292,18 @@ int coltt_hnsw_rows8_searches(coltt_handle_t h, uint64_t* out_launches, int32_t*
  * COLTT_ROW_SHADOW=0 at create, or when its allocation failed); once a traversal's result set is full, a neighbour the shadow PROVES to be no
  * closer than the set's worst member is rejected without reading its f32 row.  COLTT_ROW_FILTER = 0 / 1 forces it off / on per call, default: on for
  * row arrays far larger than the caches at ef <= 128 (the ef > 128 kernels take it with COLTT_ROW_FILTER=1 only).  Cumulative per index over the filtered
- * launches: evaluations the filter rejected, f32 rows read at level 0, shadow rows read (a neighbour the shadow cannot reject reads both), launches; *out_has_shadow = the index has its shadow.  Any out pointer may be NULL. */
+ * launches: evaluations the filter rejected, f32 rows read at level 0, shadow rows read (a neighbour the shadow cannot reject reads both), launches; *out_has_shadow = the index has its shadow.  Any out pointer may be NULL.
+ * Two kinds of shadow exist.  The 8-BIT one (the default): one signed code byte per element (dim bytes per slot) with a scale and the exact norm of
+ * what the codes miss per slot, the pair repeated per level-0 edge beside the neighbours' norms (8 bytes per slot + 8 bytes per edge); the bound charges
+ * that stored error norm (coltt_amd/csrc/row_filter8.hpp).  The BINARY16 one: dim * 2 bytes per slot (row_filter.hpp).
+ * COLTT_ROW_SHADOW_BITS = 8 / 16 / both (at create; default 8) says which an index keeps; COLTT_ROW_FILTER_BITS = 8 / 16 (per call) which a filtered launch
+ * reads — unset: 8 where the index keeps it, else 16; the kind an index does not keep is served by the one it does.  *out_has_shadow is non-zero when any
+ * shadow is kept: 8, 16 or 24 (both).  The shadow-row counter counts rows of whichever kind the launches read. */
 int coltt_hnsw_row_filter_stats(coltt_handle_t h, uint64_t* out_rejected, uint64_t* out_f32_rows, uint64_t* out_shadow_rows, uint64_t* out_launches, int32_t* out_has_shadow);
+/* Read-back of the 8-bit shadow for tests and tools: the codes of slots [first_slot, first_slot + n) in natural element order ([n][dim]), their
+ * (scale, error norm) pairs ([n][2] floats) and the pairs carried by their level-0 adjacency rows ([n][m_max0][2] floats, zeros at empty positions).
+ * Any out pointer may be NULL; COLTT_E_UNSUPPORTED when the index keeps no 8-bit shadow. */
+int coltt_hnsw_fetch_shadow8(coltt_handle_t h, uint64_t first_slot, uint64_t n, int8_t* out_codes, float* out_meta, float* out_adj_meta);
 /* graph export in the bulk_load layout (what Hnsw.Commit serialises, hnsw_commit.go:69-162).
  * Call with NULL arrays to get sizes.  With any array non-NULL, *n_slots / *n_rows / *n_edges are IN-OUT: on entry the
  * capacities of the caller's arrays (slots: ids, levels, deleted; rows + 1: row_offsets; edges: nbr, nbr_dist) — normally the

@@ -10,6 +10,8 @@
 //   U = 16-byte loads in flight per lane, W = resident waves per CU (64-thread workgroups), rows drawn by a hash (uniform, independent).
 //
 // build: hipcc --offload-arch=gfx950 -O3 -o gather tools/micro/gather.hip ; run: ./gather [GiB of table] > gather.jsonl
+//   ./gather <GiB> 3 [row bytes A] [row bytes B]: the row filter's question — the SAME number of rows (GiB / B of them) read as rows of A bytes
+//   (default 768: the 8-bit shadow of a 768-d row) and of B bytes (default 1536: the binary16 shadow), eight lanes per row, 4 and 8 waves per CU.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -79,8 +81,8 @@ void both(const uint8_t* table, uint64_t nrows, uint32_t row_bytes, int w, uint3
   const double a = run<G, U, false>(table, nrows, row_bytes, w, sink, 40.0);
   const double b = run<G, U, true>(table, nrows, row_bytes, w, sink, 40.0);
   printf("{\"table_GiB\": %.1f, \"row_bytes\": %u, \"lanes_per_row\": %d, \"loads_in_flight_per_lane\": %d, \"waves_per_cu\": %d, "
-         "\"KB_in_flight_per_cu\": %.0f, \"GBps\": %.0f, \"GBps_nontemporal\": %.0f, \"frac_of_8TBs\": %.3f}\n",
-         gib, row_bytes, G, U, w, (double)w * 64 * U * 16 / 1024.0, a, b, (a > b ? a : b) / 8000.0);
+         "\"KB_in_flight_per_cu\": %.0f, \"GBps\": %.0f, \"GBps_nontemporal\": %.0f, \"Grows_per_s\": %.3f, \"Grows_per_s_nontemporal\": %.3f, \"frac_of_8TBs\": %.3f}\n",
+         gib, row_bytes, G, U, w, (double)w * 64 * U * 16 / 1024.0, a, b, a / row_bytes, b / row_bytes, (a > b ? a : b) / 8000.0);
   fflush(stdout);
 }
 
@@ -112,7 +114,13 @@ template <int G> void chase(const uint8_t* table, uint64_t nrows, uint32_t rb, u
 
 // also callable from a process that already holds a HIP runtime (python -c "import torch, ctypes; ctypes.CDLL('./gather.so').gather_run(...)")
 extern "C" int gather_run(double gib, int quick);
-int main(int argc, char** argv) { return gather_run(argc > 1 ? atof(argv[1]) : 15.0, argc > 2 ? atoi(argv[2]) : 0); }
+static uint32_t g_rb_a = 768, g_rb_b = 1536;
+int main(int argc, char** argv) {
+  if (argc > 3) g_rb_a = (uint32_t)atoi(argv[3]);
+  if (argc > 4) g_rb_b = (uint32_t)atoi(argv[4]);
+  if (g_rb_a < 128 || g_rb_b < g_rb_a || g_rb_a % 128 || g_rb_b % 128) { fprintf(stderr, "row bytes: multiples of 128, A <= B\n"); return 2; }
+  return gather_run(argc > 1 ? atof(argv[1]) : 15.0, argc > 2 ? atoi(argv[2]) : 0);
+}
 
 extern "C" int gather_run(double gib, int quick) {
   const uint64_t bytes = (uint64_t)(gib * (1ull << 30));
@@ -123,6 +131,16 @@ extern "C" int gather_run(double gib, int quick) {
   const uint32_t rbs[2] = {1536, 3072};
   if (quick == 2) {   // latency probe only
     for (uint32_t rb : rbs) { chase<2>(table, bytes / rb, rb, sink, gib); chase<8>(table, bytes / rb, rb, sink, gib); chase<64>(table, bytes / rb, rb, sink, gib); }
+    CK(hipFree(table)); CK(hipFree(sink));
+    return 0;
+  }
+  if (quick == 3) {   // short rows against long rows, the same number of rows: what a shorter shadow row buys (rows/s), and what it costs (TB/s)
+    const uint64_t nrows = bytes / g_rb_b;
+    const uint32_t two[2] = {g_rb_a, g_rb_b};
+    for (uint32_t rb : two) {
+      const double g = (double)nrows * rb / (double)(1ull << 30);
+      for (int w : {4, 8}) { both<8, 6>(table, nrows, rb, w, sink, g); both<8, 12>(table, nrows, rb, w, sink, g); }
+    }
     CK(hipFree(table)); CK(hipFree(sink));
     return 0;
   }

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""A/B of the certified level-0 row filter (coltt_amd/csrc/row_filter.hpp) on ONE index in ONE process: COLTT_ROW_FILTER=0 against 1, calls
-alternating.  `python tools/row_filter_ab.py [n] [ef,ef,...] [rounds]` builds n x 768 f32 cosine with the batched builder (ROW_FILTER_AB_DIM for
-another dim), then per ef runs 10 000 queries `rounds` times per variant (kernel time from the hipEvent pair on the search stream; the first
-round of each variant is a warm-up), checks np.array_equal on ids, score bits, counts and the three traversal counters, and prints one JSON line:
-ms per launch for both, the filter's counters, and the bytes each variant really moves per query
-(shadow rows * dim * 2 + (n_dist - rejected) * dim * 4 + n_exp * 128 + n_dist * 4 against n_dist * dim * 4 + ...: a neighbour the shadow cannot
-reject reads its shadow row AND its f32 row).  COLTT_ROW_FILTER=1 also forces the ef > 128 twins, which the default leaves off."""
+"""A/B of the certified level-0 row filter on ONE index in ONE process, three sides: filter off, over the binary16 shadow (row_filter.hpp), over the 8-bit
+shadow (row_filter8.hpp).  The index is created with COLTT_ROW_SHADOW_BITS=both; per call COLTT_ROW_FILTER=0 / 1 and COLTT_ROW_FILTER_BITS=16 / 8 pick the
+side, calls alternating.  `python tools/row_filter_ab.py [n] [ef,ef,...] [rounds]` builds n x 768 f32 cosine with the batched builder (ROW_FILTER_AB_DIM for
+another dim), then per ef runs 10 000 queries `rounds` times per side (kernel time from the hipEvent pair on the search stream; the first round of each
+side is a warm-up), checks np.array_equal on ids, score bits, counts and the three traversal counters across the sides, and prints one JSON line: per side
+ms per launch (all values and the median), shadow rows / survivors / f32 rows per query, and the bytes the side REQUESTS per query
+    shadow rows x shadow row bytes + f32 rows x dim x 4 + n_exp x (128 + 128 + 256) + n_dist x 4
+(one adjacency row, its norms and its (scale, error norm) pairs per expansion — the same formula on every side, although only the 8-bit side reads the
+last 256 bytes: 0.5 % of the total; a neighbour the shadow cannot reject reads its shadow row AND its f32 row; f32 rows = every evaluation on the
+unfiltered side) as a fraction of the 8 TB/s peak.  Requested bytes
+from counters, not a FETCH_SIZE measurement.  COLTT_ROW_FILTER=1 also forces the ef > 128 twins, which the default leaves off."""
 import json
 import os
 import sys
@@ -14,8 +18,11 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+SIDES = (("off", "0", None), ("16", "1", "16"), ("8", "1", "8"))
+
 
 def main():
+    os.environ["COLTT_ROW_SHADOW_BITS"] = "both"
     import torch
     import coltt_amd as G
     import bench as B
@@ -32,42 +39,53 @@ def main():
     gen = torch.Generator(device=dev); gen.manual_seed(0x5EED5)
     q = ds.rows(nq, gen)
     out = B.Out(torch, dev, nq, k)
-    res = {"n": n, "dim": dim, "build_s": build_s, "shadow": h.RowFilterStats()["shadow"], "ef": {}}
+    st0 = h.RowFilterStats()
+    res = {"n": n, "dim": dim, "build_s": build_s, "shadow": st0["shadow"], "shadow_bits": list(st0["shadow_bits"]), "ef": {}}
+    assert tuple(st0["shadow_bits"]) == (8, 16), "the three-sided A/B needs an index that keeps both shadows"
     for ef in efs:
-        ms = {"0": [], "1": []}; keep = {}; flt = {}
+        ms = {s[0]: [] for s in SIDES}; keep = {}; flt = {}
         for r in range(rounds):
-            for v in ("0", "1"):   # alternating: drift of the box hits both variants alike
-                os.environ["COLTT_ROW_FILTER"] = v
+            for name, on, bits_ in SIDES:   # alternating: drift of the box hits every side alike
+                os.environ["COLTT_ROW_FILTER"] = on
+                if bits_:
+                    os.environ["COLTT_ROW_FILTER_BITS"] = bits_
+                else:
+                    os.environ.pop("COLTT_ROW_FILTER_BITS", None)
                 s0 = h.RowFilterStats()
                 st = h.SearchDevice(q.data_ptr(), nq, k, *out.ptrs(), ef=ef)
                 s1 = h.RowFilterStats()
                 if r:
-                    ms[v].append(h.last_kernel_ms())
+                    ms[name].append(h.last_kernel_ms())
                 got = (out.ids.cpu().numpy().copy(), out.sc.cpu().numpy().copy(), out.cnt.cpu().numpy().copy() if hasattr(out, "cnt") else None,
                        {kk: st[kk] for kk in ("n_dist", "n_exp", "n_hops")})
-                if v not in keep:
-                    keep[v] = got
-                else:   # every round of a variant answers alike
-                    assert np.array_equal(keep[v][0], got[0]) and np.array_equal(keep[v][1].view(np.uint32), got[1].view(np.uint32)) and keep[v][3] == got[3]
-                flt[v] = {kk: s1[kk] - s0[kk] for kk in ("rejected", "f32_rows", "shadow_rows", "launches")}
-        os.environ.pop("COLTT_ROW_FILTER", None)
-        a, b = keep["0"], keep["1"]
-        same = bool(np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)) and a[3] == b[3]
-                    and (a[2] is None or np.array_equal(a[2], b[2])))
+                if name not in keep:
+                    keep[name] = got
+                else:   # every round of a side answers alike
+                    assert np.array_equal(keep[name][0], got[0]) and np.array_equal(keep[name][1].view(np.uint32), got[1].view(np.uint32)) and keep[name][3] == got[3]
+                flt[name] = {kk: s1[kk] - s0[kk] for kk in ("rejected", "f32_rows", "shadow_rows", "launches")}
+        os.environ.pop("COLTT_ROW_FILTER", None); os.environ.pop("COLTT_ROW_FILTER_BITS", None)
+        a = keep["off"]
+        same = all(bool(np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)) and a[3] == b[3]
+                        and (a[2] is None or np.array_equal(a[2], b[2]))) for b in (keep["16"], keep["8"]))
         nd, ne = a[3]["n_dist"] / nq, a[3]["n_exp"] / nq
-        rej, f32, h16 = flt["1"]["rejected"] / nq, flt["1"]["f32_rows"] / nq, flt["1"]["shadow_rows"] / nq
-        row = {"identical": same, "per_query": {"n_dist": nd, "n_exp": ne, "rejected": rej, "f32_rows_level0": f32, "shadow_rows": h16, "survivors_reading_both": h16 - rej, "f32_rows_while_filling": f32 - (h16 - rej),
-                                                "f32_fraction_of_level0": f32 / max(rej + f32, 1e-9)}}
-        for v, name in (("0", "unfiltered"), ("1", "filtered")):
-            t = float(np.median(ms[v])) / 1e3
-            moved = (nd * dim * 4 if v == "0" else h16 * dim * 2 + (nd - rej) * dim * 4) + ne * 128 + nd * 4
-            row[name] = {"ms_per_launch": t * 1e3, "min_ms": float(min(ms[v])), "max_ms": float(max(ms[v])), "all_ms": [float(x) for x in ms[v]], "queries_per_s": nq / t,
-                         "bytes_moved_per_query": moved, "frac_of_hbm_peak_really_drawn": moved * nq / t / 8e12, "filter_counters_of_last_call": flt[v]}
-        row["speedup"] = row["unfiltered"]["ms_per_launch"] / row["filtered"]["ms_per_launch"]
-        row["bytes_ratio"] = row["filtered"]["bytes_moved_per_query"] / row["unfiltered"]["bytes_moved_per_query"]
+        row = {"identical": same, "per_query": {"n_dist": nd, "n_exp": ne}}
+        for name, on, bits_ in SIDES:
+            t = float(np.median(ms[name])) / 1e3
+            rej, f32, sh = flt[name]["rejected"] / nq, flt[name]["f32_rows"] / nq, flt[name]["shadow_rows"] / nq
+            # f32 rows: level 0 (the counter) + the upper levels' and the entrypoint's evaluations = every evaluation the filter did not reject
+            f32_all, sh_bytes = nd - rej, 0 if name == "off" else dim * (2 if name == "16" else 1)
+            moved = sh * sh_bytes + f32_all * dim * 4 + ne * (128 + 128 + 256) + nd * 4
+            row[name] = {"ms_per_launch": t * 1e3, "min_ms": float(min(ms[name])), "max_ms": float(max(ms[name])), "all_ms": [float(x) for x in ms[name]], "queries_per_s": nq / t,
+                         "shadow_rows": sh, "rejected": rej, "survivors_reading_both": sh - rej, "f32_rows_level0": f32, "f32_rows_while_filling": f32 - (sh - rej),
+                         "f32_fraction_of_level0": f32 / max(rej + f32, 1e-9) if name != "off" else 1.0,
+                         "bytes_requested_per_query": moved, "frac_of_hbm_peak_requested": moved * nq / t / 8e12, "filter_counters_of_last_call": flt[name]}
+        for name in ("16", "8"):
+            row[name]["speedup_over_off"] = row["off"]["ms_per_launch"] / row[name]["ms_per_launch"]
+            row[name]["bytes_ratio_to_off"] = row[name]["bytes_requested_per_query"] / row["off"]["bytes_requested_per_query"]
+        row["speedup_8_over_16"] = row["16"]["ms_per_launch"] / row["8"]["ms_per_launch"]
         res["ef"][str(ef)] = row
         print(json.dumps({str(ef): row}), file=sys.stderr, flush=True)
-        assert same, "the filtered and the unfiltered walk disagree"
+        assert same, "the sides disagree"
     print(json.dumps(res))
 
 
