@@ -8,6 +8,7 @@ COSINE, EUCLIDEAN = 0, 1
 Q_NONE, Q_F16, Q_F8, Q_BF16 = 0, 1, 2, 3
 SELECT_REFERENCE, SELECT_NEAREST = 0, 1
 MODE_EXACT, MODE_MFMA = 0, 1
+NBR_NONE = 0xFFFFFFFF   # "no neighbour at this position" in slot arrays (coltt_hnsw_row_filter_probe)
 
 _lib = None
 _env_seen = None

@@ -2349,6 +2349,48 @@ int coltt_hnsw_fetch_shadow8(coltt_handle_t h, uint64_t first_slot, uint64_t n, 
   return COLTT_OK;
 }
 
+int coltt_hnsw_row_filter_probe(coltt_handle_t h, const float* queries, size_t nq, const uint32_t* slots, const float* lower_bound, int bits, int nt,
+                                int full_at_pop, float* out_r, float* out_qnorm, float* out_rnorm, uint32_t* out_counts) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_row_filter_probe: unknown handle");
+  if (bits != 8 && bits != 16) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: bits must be 8 or 16");
+  if (nq && (!queries || !slots || !lower_bound || !out_r || !out_qnorm || !out_rnorm || !out_counts)) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: NULL buffer");
+  if (nq > 0x7fffffffu / 32) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: too many queries");
+  ReadLock g(x->rw);
+  if (!x->r8 || (bits == 8 ? !x->has_shadow8() : !x->has_shadow16())) return fail(COLTT_E_UNSUPPORTED, "hnsw_row_filter_probe: the index keeps no %d-bit shadow", bits);
+  if (nq == 0) return COLTT_OK;
+  for (size_t i = 0; i < nq * 32; i++)
+    if (slots[i] != NBR_NONE && slots[i] >= x->n) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: slot %u outside [0,%llu)", slots[i], (unsigned long long)x->n);
+  COLTT_DEVICE(x->device);
+  CtxLease<HCtx> ctx(x->pool);
+  if (!ctx.c) return COLTT_E_DEVICE;
+  HCtx* c = ctx.c;
+  const size_t dim = x->dim;
+  COLTT_TRY(c->w_qraw.reserve(nq * dim * 4));
+  COLTT_TRY(c->w_misc.reserve(256));
+  // one block of inputs and outputs: slots [nq][32] | lower_bound [nq] | out_r [nq][32] | out_rnorm [nq][32] | out_counts [nq][3]
+  COLTT_TRY(c->w_out_ids.reserve(nq * (32 * 3 + 1 + 3) * 4));
+  uint32_t* d_slots = c->w_out_ids.as<uint32_t>();
+  float* d_lb = reinterpret_cast<float*>(d_slots + nq * 32);
+  float* d_r = d_lb + nq; float* d_rn = d_r + nq * 32;
+  uint32_t* d_cnt = reinterpret_cast<uint32_t*>(d_rn + nq * 32);
+  COLTT_HIP(hipMemcpyAsync(c->w_qraw.p, queries, nq * dim * 4, hipMemcpyHostToDevice, c->stream));
+  COLTT_HIP(hipMemcpyAsync(d_slots, slots, nq * 32 * 4, hipMemcpyHostToDevice, c->stream));
+  COLTT_HIP(hipMemcpyAsync(d_lb, lower_bound, nq * 4, hipMemcpyHostToDevice, c->stream));
+  COLTT_TRY(prep_queries_any(x.get(), c, c->w_qraw.as<float>(), nq, c->w_misc.as<uint32_t>()));   // Normalize the queries as Search does
+  const size_t lds = ((dim * 4 + 15) & ~(size_t)15) + 96 * 4;
+  auto kern = bits == 8 ? (nt ? hnsw_row_filter_probe_kernel<true, 8> : hnsw_row_filter_probe_kernel<false, 8>)
+                        : (nt ? hnsw_row_filter_probe_kernel<true, 16> : hnsw_row_filter_probe_kernel<false, 16>);
+  kern<<<(uint32_t)nq, 64, lds, c->stream>>>(x->view(), c->w_qeff.as<float>(), c->w_qn.as<float>(), d_slots, d_lb, full_at_pop ? 1 : 0, d_r, d_rn, d_cnt);
+  COLTT_HIP(hipGetLastError());
+  COLTT_HIP(hipMemcpyAsync(out_r, d_r, nq * 32 * 4, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipMemcpyAsync(out_rnorm, d_rn, nq * 32 * 4, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipMemcpyAsync(out_counts, d_cnt, nq * 3 * 4, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipMemcpyAsync(out_qnorm, c->w_qn.p, nq * 4, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipStreamSynchronize(c->stream));
+  return COLTT_OK;
+}
+
 int coltt_last_kernel_ms(coltt_handle_t h, float* out_ms) {
   if (!out_ms) return fail(COLTT_E_INVALID, "last_kernel_ms: NULL out");
   if (auto x = lookup<Hnsw>(h)) { *out_ms = x->last_ms.load(); return COLTT_OK; }

@@ -323,6 +323,37 @@ __global__ __launch_bounds__(64) void hnsw_search2_rowfilter_kernel(GraphView g,
   if constexpr (VISMODE == VIS_HBM) { if (lane == 0) vis_epoch[blockIdx.x] = w.epoch; }
 }
 
+// The row filter's evaluator on CHOSEN (query, slot) pairs — a test-and-diagnostics kernel (coltt_hnsw_row_filter_probe), not a search.  One wave per
+// query, the LDS layout of the kernel above's prologue (query in rows8 order | 96 words of scratch); lane pair p holds slots[q][p] (NBR_NONE: not fresh)
+// with its norm and, for the 8-bit shadow, its (scale, error norm) from the per-slot arrays, and the wave makes ONE call of Group8FilterEval::filtered —
+// the dispatch, the streams and both phases are the walk's own code, nothing of them is restated here.  out_r: the value the even lane of every pair got
+// back; out_counts: (n_rej, n_f32, n_h16) of the call.  A chunk without a fresh pair makes no call, as in search_level2.
+template <bool NT, int BITS>
+__global__ __launch_bounds__(64) void hnsw_row_filter_probe_kernel(GraphView g, const float* __restrict__ q_eff, const float* __restrict__ qnorms,
+                                                                  const uint32_t* __restrict__ slots, const float* __restrict__ lower_bound, int full_at_pop,
+                                                                  float* __restrict__ out_r, float* __restrict__ out_rnorm, uint32_t* __restrict__ out_counts) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int lane = threadIdx.x;
+  const uint32_t qi = blockIdx.x;
+  WaveCtx w = {};
+  const size_t off = ((size_t)g.dim * 4 + 15) & ~(size_t)15;
+  w.qp = reinterpret_cast<float*>(smem);
+  w.scr = reinterpret_cast<uint32_t*>(smem + off);
+  for (int e = lane; e < g.dim; e += 64) w.qp[rows8_qindex<Q_NONE>(e)] = q_eff[(size_t)qi * g.dim + e];
+  w.qnorm = qnorms[qi];
+  wave_sync();
+  const int half = lane & 1, p = lane >> 1;
+  const uint32_t nb = slots[(size_t)qi * 32 + p];
+  const bool fresh = nb != NBR_NONE;
+  const float nrm = fresh ? g.norms[nb] : 0.f;
+  Group8FilterEval<M_COS, Q_NONE, true, NT, BITS> fev;
+  if constexpr (BITS == 8) fev.mt = fresh ? g.rows_m[nb] : float2{0.f, 0.f};
+  float r = 0.f;
+  if (__ballot(fresh)) r = fev.filtered(g, w, nb, fresh, nrm, half, lane, lower_bound[qi], full_at_pop != 0);   // (wave-uniform)
+  if (half == 0) { out_r[(size_t)qi * 32 + p] = r; out_rnorm[(size_t)qi * 32 + p] = nrm; }
+  if (lane == 0) { out_counts[(size_t)qi * 3] = fev.n_rej; out_counts[(size_t)qi * 3 + 1] = fev.n_f32; out_counts[(size_t)qi * 3 + 2] = fev.n_h16; }
+}
+
 
 // Hnsw.Search with a 256-thread workgroup per query (hnsw_lat.hpp): the latency path for small batches — the reference serves one
 // query per RPC (core/core.go:633-667).  One workgroup per CU, queries pulled from a global counter.  Same answers, score bits and

@@ -268,6 +268,18 @@ class Hnsw:
         L.check(L.lib().coltt_hnsw_fetch_shadow8(self.h, C.c_uint64(first), C.c_uint64(n), L.vp(codes), L.vp(meta), L.vp(adj)))
         return codes, meta, adj
 
+    def RowFilterProbe(self, queries, slots, lower_bound, bits=8, nt=0, full_at_pop=1):
+        """the level-0 walk's chunk evaluation on chosen pairs (coltt_hnsw_row_filter_probe): slots [nq, 32] uint32 (L.NBR_NONE = not fresh),
+        lower_bound a scalar or [nq].  Returns (r [nq, 32], qnorm [nq], rnorm [nq, 32], counts [nq, 3] = rejected, f32 rows, shadow rows)."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        s = np.ascontiguousarray(slots, np.uint32).reshape(nq, 32)
+        lb = np.ascontiguousarray(np.broadcast_to(np.asarray(lower_bound, np.float32), (nq,)))
+        r = np.zeros((nq, 32), np.float32); qn = np.zeros(nq, np.float32); rn = np.zeros((nq, 32), np.float32); cnt = np.zeros((nq, 3), np.uint32)
+        L.check(L.lib().coltt_hnsw_row_filter_probe(self.h, L.vp(q), C.c_size_t(nq), L.vp(s), L.vp(lb), C.c_int(int(bits)), C.c_int(int(nt)),
+                                                    C.c_int(int(full_at_pop)), L.vp(r), L.vp(qn), L.vp(rn), L.vp(cnt)))
+        return r, qn, rn, cnt
+
     # -- product-quantised search (coltt_hnsw_pq_*; the reference's call shape: playground/hnswpq_verification.go:69-105)
     def PqAttach(self, pq):
         """snapshot the trained quantiser `pq` (a PQSpace) into the index and encode every stored row"""

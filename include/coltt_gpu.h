@@ -304,6 +304,15 @@ int coltt_hnsw_row_filter_stats(coltt_handle_t h, uint64_t* out_rejected, uint64
  * (scale, error norm) pairs ([n][2] floats) and the pairs carried by their level-0 adjacency rows ([n][m_max0][2] floats, zeros at empty positions).
  * Any out pointer may be NULL; COLTT_E_UNSUPPORTED when the index keeps no 8-bit shadow. */
 int coltt_hnsw_fetch_shadow8(coltt_handle_t h, uint64_t first_slot, uint64_t n, int8_t* out_codes, float* out_meta, float* out_adj_meta);
+/* The row filter's evaluator on chosen pairs, for tests and tools: one wave per query makes ONE call of the level-0 walk's own chunk evaluation
+ * (hnsw_walk2.hpp: Group8FilterEval::filtered) on the up to 32 slots slots[q][0..32) (0xFFFFFFFF = no fresh neighbour at that position; a slot may
+ * repeat) with lower_bound[q] and full_at_pop (0 | 1), over the shadow of `bits` (8 | 16) bits, with non-temporal row loads or not (nt 1 | 0).
+ * The queries are prepared as coltt_hnsw_search prepares them.  out_r [nq][32]: what the walk would have been handed per position — the exact kernel's
+ * distance, or the certified lower bound of a rejected neighbour, 0 where not fresh; out_qnorm [nq] / out_rnorm [nq][32]: the squared norms the bound
+ * was formed from; out_counts [nq][3]: evaluations rejected, f32 rows read, shadow rows read.  lower_bound = +3e38 rejects nothing (every distance
+ * exact), -3e38 rejects every certified pair (every bound).  COLTT_E_UNSUPPORTED when the index does not keep the shadow asked for. */
+int coltt_hnsw_row_filter_probe(coltt_handle_t h, const float* queries, size_t nq, const uint32_t* slots, const float* lower_bound, int bits, int nt,
+                                int full_at_pop, float* out_r, float* out_qnorm, float* out_rnorm, uint32_t* out_counts);
 /* graph export in the bulk_load layout (what Hnsw.Commit serialises, hnsw_commit.go:69-162).
  * Call with NULL arrays to get sizes.  With any array non-NULL, *n_slots / *n_rows / *n_edges are IN-OUT: on entry the
  * capacities of the caller's arrays (slots: ids, levels, deleted; rows + 1: row_offsets; edges: nbr, nbr_dist) — normally the

@@ -52,8 +52,11 @@ def _sides(gh, Q, k, ef, monkeypatch, sides=("off", "8", "16")):
     return out
 
 
-def _check(gh, Q, efs, monkeypatch, k=10, del_bits=None, id_of=None, sides=("off", "8", "16"), want_survivors=False):
+def _check(gh, Q, efs, monkeypatch, k=10, del_bits=None, id_of=None, sides=("off", "8", "16"), want_survivors=False, gaussian=True):
+    """gaussian=False switches off the two expectations that were calibrated for Gaussian rows — that every ef rejects something and that the 8-bit
+    shadow rejects no more than the binary16 one — and nothing else.  Returns {(ef, side): counter deltas}."""
     d = gh.dim
+    seen = {}
     g = gh.ExportRaw(); rows = gh.FetchRows()
     for ef in efs:
         r = _sides(gh, Q, k, ef, monkeypatch, sides)
@@ -71,8 +74,10 @@ def _check(gh, Q, efs, monkeypatch, k=10, del_bits=None, id_of=None, sides=("off
             assert {k_: st1[k_] for k_ in ost} == ost, (ef, side, st1, ost)
             surv = f["shadow_rows"] - f["rejected"]   # full-set neighbours the shadow could not reject: phase B
             print(f"d{d} ef{ef} k{k} side {side}: shadow rows {f['shadow_rows']} rejected {f['rejected']} survivors {surv} f32 rows {f['f32_rows']} n_dist {st1['n_dist']}")
+            seen[(ef, side)] = f
             assert f["launches"] == 1
-            assert f["rejected"] > 0, f"ef{ef}: the filter over {side} bits rejected nothing"
+            if gaussian:
+                assert f["rejected"] > 0, f"ef{ef}: the filter over {side} bits rejected nothing"
             assert 0 <= surv <= f["f32_rows"]
             assert 0 < f["rejected"] + f["f32_rows"] <= st1["n_dist"]
             if want_survivors:
@@ -84,7 +89,9 @@ def _check(gh, Q, efs, monkeypatch, k=10, del_bits=None, id_of=None, sides=("off
             # The 8-bit margin (about 7e-3 of the norm product) contains the binary16 one (1e-3) several times over; a row the 8-bit bound proves and
             # the binary16 bound cannot needs the codes' error q . (x - s c) — spread about e / sqrt(dim) = 3e-4 .. 4e-4 of the norm product on these
             # rows — to fall more than ten of its standard deviations on the favourable side.  One per cent of the rows read is a generous slack.
-            assert f8["rejected"] <= f16["rejected"] + f16["shadow_rows"] // 100, (f8, f16)
+            if gaussian:
+                assert f8["rejected"] <= f16["rejected"] + f16["shadow_rows"] // 100, (f8, f16)
+    return seen
 
 
 def _check_arrays(gh):
@@ -108,10 +115,11 @@ def _check_arrays(gh):
 
 
 @pytest.mark.parametrize("nt", ["0", "1"], ids=["default-loads", "non-temporal-twins"])
-@pytest.mark.parametrize("d,n", [(256, 5000), (768, 3000), (512, 2000), (1536, 1500)])
+@pytest.mark.parametrize("d,n", [(256, 5000), (768, 3000), (512, 2000), (1536, 1500), (1024, 2000), (1280, 1500), (2304, 1000)])
 def test_three_sides_equal_the_oracle(gpu, monkeypatch, d, n, nt):
     """256-d and 768-d: rows of 2 / 6 shadow lines, the chunk in one burst; 512-d: 4 lines, the stream with two bursts of 2 per row; 1536-d: 12 lines,
-    the stream with two bursts of 6 per row.  ef 32 / 128 on the LDS-hash kernel, 256 on the HBM-visited one; growth without Reserve"""
+    the stream with two bursts of 6 per row; 1024-d: four bursts of 2; 1280-d: five bursts of 2 (an odd count: the other tail of the ping-pong loop);
+    2304-d: three bursts of 6 (and three of 12 binary16 lines).  ef 32 / 128 on the LDS-hash kernel, 256 on the HBM-visited one; growth without Reserve"""
     monkeypatch.setenv("COLTT_ROWS_NT", nt)
     X = O.fill_normal(8000 + d, (n, d)); lv = O.levels(8001 + d, n)
     gh = _gpu_build(gpu, X, lv, gpu.HnswCfg.default(ef_construction=60), batch=256)
@@ -121,6 +129,42 @@ def test_three_sides_equal_the_oracle(gpu, monkeypatch, d, n, nt):
     _check(gh, Q, (128,), monkeypatch, k=100)
     if nt == "0":
         _check_arrays(gh)
+
+
+def _clusters(seed, n, d, nq):
+    """20 tight clusters (centre + 1e-2 noise per element); queries: members plus noise"""
+    rng = np.random.default_rng(seed)
+    centres = O.fill_normal(seed, (20, d))
+    X = centres[rng.integers(0, 20, n)] + O.fill_normal(seed + 1, (n, d)) * np.float32(1e-2)
+    Q = X[rng.choice(n, nq, replace=False)] + O.fill_normal(seed + 2, (nq, d)) * np.float32(1e-2)
+    return np.ascontiguousarray(X, np.float32), np.ascontiguousarray(Q, np.float32)
+
+
+def _heavy_tails(seed, n, d, nq):
+    """Gaussian times lognormal, 90 % zeros: a few elements carry the row, the codes of the rest say little"""
+    rng = np.random.default_rng(seed)
+    def draw(s, m):
+        v = O.fill_normal(s, (m, d)) * rng.lognormal(0.0, 2.0, (m, d)).astype(np.float32)
+        v[rng.random((m, d)) < 0.9] = 0
+        v[np.arange(m), rng.integers(0, d, m)] += np.float32(1.0)   # (never a zero row)
+        return np.ascontiguousarray(v, np.float32)
+    return draw(seed, n), draw(seed + 1, nq)
+
+
+@pytest.mark.parametrize("make", [_clusters, _heavy_tails], ids=["clusters", "heavy-tails"])
+@pytest.mark.parametrize("d", [256, 1024])
+def test_three_sides_equal_the_oracle_on_rows_that_are_not_gaussian(gpu, monkeypatch, d, make):
+    """the collections the Gaussian tests say nothing about: rows that all look alike to the codes, and rows the codes say little about.  Parity with
+    the oracle and between the sides, counter equality and the counter identities; how MUCH such data lets the filter reject is printed, not asserted,
+    except that each collection rejects something at ef 128 (a filter that never fires proves nothing here)"""
+    n = 1500
+    X, Q = make(8500 + d, n, d, 32)
+    lv = O.levels(8501 + d, n)
+    gh = _gpu_build(gpu, X, lv, gpu.HnswCfg.default(ef_construction=60), batch=256)
+    assert gh.RowFilterStats()["shadow_bits"] == (8, 16)
+    seen = _check(gh, Q, (32, 128, 256), monkeypatch, gaussian=False)
+    for side in ("8", "16"):
+        assert seen[(128, side)]["rejected"] > 0, f"d{d} {make.__name__}: the filter over {side} bits rejected nothing at ef 128"
 
 
 def test_writers_keep_the_8_bit_arrays(gpu, monkeypatch):
