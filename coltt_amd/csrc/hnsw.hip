@@ -1161,10 +1161,12 @@ uint32_t pq_lut_shift(const Hnsw* x) { uint32_t sh = 4; while ((1u << sh) < x->p
 // (profiles/r05s_pq_ab.md): ef 1 024 410 -> 440 k queries/s, ef 1 408 277 -> 316 k.
 constexpr size_t PQ_WAVES_CAP = 12;
 struct PqGeom { uint32_t ef, ef_pad, vis_words; size_t lds; int variant; /* 0: LDS hash | 2: byte map + delta result set */ uint32_t per_cu; };
-bool pq_geom(Hnsw* x, uint32_t ef, bool force_hbm, PqGeom& out) {
+// filt_cap: the capacity of the allowed set R of a filtered walk (coltt_hnsw_pq_search_filtered), 0 = no filter
+bool pq_geom(Hnsw* x, uint32_t ef, bool force_hbm, PqGeom& out, uint32_t filt_cap = 0) {
   PqGeom s{};
   s.ef = ef; s.ef_pad = (ef + 63) & ~63u;
-  const size_t fixed = (size_t)s.ef_pad * 8 + ((size_t)pq_walk_table_rows(x->pq_row >> 4) << pq_lut_shift(x)) * 2;   // result set | binary16 table, pair-interleaved (the query stays in HBM: only the re-rank reads it)
+  const size_t fixed = (size_t)s.ef_pad * 8 + ((size_t)pq_walk_table_rows(x->pq_row >> 4) << pq_lut_shift(x)) * 2   // result set | binary16 table, pair-interleaved (the query stays in HBM: only the re-rank reads it)
+                     + (filt_cap ? (size_t)((filt_cap + 63u) & ~63u) * 8 : 0);                                         // | R
   if (fixed > 160 * 1024) return false;
   const bool hbm_ok = x->vis_stride != 0 && x->vis_regions > 0;
   // LDS hash: as search_geom sizes it; it must never need the reset path (err 8 -> the call is re-run over the byte map)
@@ -1185,16 +1187,18 @@ bool pq_geom(Hnsw* x, uint32_t ef, bool force_hbm, PqGeom& out) {
 }
 
 int launch_pq_walk(Hnsw* x, HCtx* c, const PqGeom& sg, bool nbr, uint32_t grid, uint32_t region_base, const unsigned short* lut, uint32_t nq, uint32_t k,
-                   uint32_t rerank, uint32_t* counter, uint32_t* surv, uint32_t* surv_cnt, unsigned long long* stats) {
+                   uint32_t rerank, uint32_t* counter, uint32_t* surv, uint32_t* surv_cnt, unsigned long long* stats, const FilterView* fv = nullptr, uint32_t fcap = 0) {
   const uint32_t sh = pq_lut_shift(x);
   // table row length x code-row pieces as compile-time constants for the common quantisers: 64 sub-vectors x 16 / 32 centroids (LS 4 / 5, 4 pieces),
   // 32 x 256 — the reference's shape, playground/hnswpq_verification.go:69-73 — (LS 8, 2 pieces), 96 x 256 (LS 8, 6 pieces); anything else runs the
   // forms that read the shape at run time.  Byte map (variant 2) with or without the neighbourhood blocks; the LDS-hash variant gathers.
   const uint32_t np = x->pq_row >> 4;
   typedef void (*pq_kern_t)(GraphView, int32_t, int32_t, const unsigned short*, const uint8_t*, const uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
-                            uint32_t*, uint32_t*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*);
+                            uint32_t*, uint32_t*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*, FilterView, uint32_t);
   pq_kern_t kern;
-#define COLTT_PQK(LS, NP) (sg.variant == 0 ? (pq_kern_t)hnsw_pq_search_kernel<0, VIS_LDS, LS, NP, false> : nbr ? (pq_kern_t)hnsw_pq_search_kernel<2, VIS_HBM, LS, NP, true> : (pq_kern_t)hnsw_pq_search_kernel<2, VIS_HBM, LS, NP, false>)
+  // fv (coltt_hnsw_pq_search_filtered): the same dispatch over the FILTER instances — one filter takes the same kernel form through either entry point
+#define COLTT_PQKF(LS, NP, F) (sg.variant == 0 ? (pq_kern_t)hnsw_pq_search_kernel<0, VIS_LDS, LS, NP, false, F> : nbr ? (pq_kern_t)hnsw_pq_search_kernel<2, VIS_HBM, LS, NP, true, F> : (pq_kern_t)hnsw_pq_search_kernel<2, VIS_HBM, LS, NP, false, F>)
+#define COLTT_PQK(LS, NP) (fv ? COLTT_PQKF(LS, NP, true) : COLTT_PQKF(LS, NP, false))
   if (sh == 5 && np == 4) kern = COLTT_PQK(5, 4);
   else if (sh == 4 && np == 4) kern = COLTT_PQK(4, 4);
   else if (sh == 8 && np == 2) kern = COLTT_PQK(8, 2);
@@ -1204,10 +1208,11 @@ int launch_pq_walk(Hnsw* x, HCtx* c, const PqGeom& sg, bool nbr, uint32_t grid, 
   else if (sh == 8) kern = COLTT_PQK(8, 0);
   else kern = COLTT_PQK(0, 0);
 #undef COLTT_PQK
+#undef COLTT_PQKF
   COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
   kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, lut, x->pq_codes.as<uint8_t>(), nbr ? x->pq_nbr.as<uint8_t>() : nullptr, x->pq_row, sh, nq, k, sg.ef, sg.ef_pad, rerank,
                                         sg.vis_words, counter, surv, surv_cnt, stats, x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride,
-                                        (size_t)x->vis_stride, x->w_vepoch.as<uint32_t>() + region_base);
+                                        (size_t)x->vis_stride, x->w_vepoch.as<uint32_t>() + region_base, fv ? *fv : FilterView{nullptr, 0u}, fcap);
   COLTT_HIP(hipGetLastError());
   return COLTT_OK;
 }
@@ -1227,8 +1232,10 @@ int launch_pq_rerank(Hnsw* x, HCtx* c, const PqGeom& sg, uint32_t q0, uint32_t n
 }
 
 // one attempt; *retry_hbm: the LDS hash would have needed its reset path — the caller runs the same call over the byte map
+// fv (coltt_hnsw_pq_search_filtered, WALK): the walk also keeps the allowed set R and the re-rank is over R; ef_override is then ef_walk (>= k)
 int pq_search_once(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t nq, uint32_t k, uint32_t ef_override, uint32_t rerank,
-                   uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_stats* stats, uint64_t* out_n_exact, bool force_hbm, bool* retry_hbm) {
+                   uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_stats* stats, uint64_t* out_n_exact, bool force_hbm, bool* retry_hbm,
+                   const FilterView* fv = nullptr) {
   *retry_hbm = false;
   if (stats) std::memset(stats, 0, sizeof(*stats));
   if (out_n_exact) *out_n_exact = 0;
@@ -1251,8 +1258,9 @@ int pq_search_once(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_
   if (ef > 4096) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search: ef=%u > 4096", ef);
   if (wants_visg(ef) || force_hbm) COLTT_TRY(ensure_visg(x));
   PqGeom sg;
-  bool have = pq_geom(x, ef, force_hbm, sg);
-  if (!have && !force_hbm) { COLTT_TRY(ensure_visg(x)); have = pq_geom(x, ef, true, sg); }   // no room for the LDS hash beside the table: the byte map
+  const uint32_t fcap = fv ? (rerank == 0 ? ef : std::min(std::max(rerank, k), ef)) : 0u;   // |R| <= cap: what the re-rank may read
+  bool have = pq_geom(x, ef, force_hbm, sg, fcap);
+  if (!have && !force_hbm) { COLTT_TRY(ensure_visg(x)); have = pq_geom(x, ef, true, sg, fcap); }   // no room for the LDS hash beside the table: the byte map
   if (!have) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search: dim %u / ef %u / %u sub-vectors need more than the CU's 160 KiB of LDS", x->dim, ef, x->pq_shape.m);
   uint32_t grid = (uint32_t)std::min<size_t>(nq, (size_t)256 * sg.per_cu);
   RegionLease lease;
@@ -1287,7 +1295,7 @@ int pq_search_once(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_
                              reinterpret_cast<uint32_t*>(c->w_pack.as<uint8_t>() + group * lut_q), c->w_pack.as<unsigned short>()));
     if (q0) COLTT_HIP(hipMemsetAsync(counter, 0, 4, c->stream));
     COLTT_TRY(launch_pq_walk(x, c, sg, nbr, (uint32_t)std::min<size_t>(grid, gn), lease.base, c->w_pack.as<unsigned short>(), (uint32_t)gn, k, rerank, counter, c->w_surv.as<uint32_t>(),
-                             c->w_scnt.as<uint32_t>(), d_stats));
+                             c->w_scnt.as<uint32_t>(), d_stats, fv, fcap));
     int rc;
 #define COLTT_LP_ARGS x, c, sg, (uint32_t)q0, (uint32_t)gn, k, c->w_surv.as<uint32_t>(), c->w_scnt.as<uint32_t>(), c->w_keys.as<unsigned long long>(), d_oi, d_os, d_oc
 #define COLTT_LP(Q) rc = x->metric == COLTT_COSINE ? launch_pq_rerank<M_COS, Q>(COLTT_LP_ARGS) : launch_pq_rerank<M_L2, Q>(COLTT_LP_ARGS)
@@ -1333,6 +1341,14 @@ int pq_search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, siz
   bool retry = false;
   COLTT_TRY(pq_search_once(x, c, queries, on_device, nq, k, ef_override, rerank, out_ids, out_scores, out_counts, stats, out_n_exact, false, &retry));
   if (retry) COLTT_TRY(pq_search_once(x, c, queries, on_device, nq, k, ef_override, rerank, out_ids, out_scores, out_counts, stats, out_n_exact, true, &retry));
+  return COLTT_OK;
+}
+// coltt_hnsw_pq_search_filtered, WALK: pq_search_common at ef_walk with the allowed set
+int pq_search_filtered_walk(Hnsw* x, HCtx* c, const FilterView& fv, const float* queries, size_t nq, uint32_t k, uint32_t ef_walk, uint32_t rerank,
+                            uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_stats* stats, uint64_t* out_n_exact) {
+  bool retry = false;
+  COLTT_TRY(pq_search_once(x, c, queries, false, nq, k, ef_walk, rerank, out_ids, out_scores, out_counts, stats, out_n_exact, false, &retry, &fv));
+  if (retry) COLTT_TRY(pq_search_once(x, c, queries, false, nq, k, ef_walk, rerank, out_ids, out_scores, out_counts, stats, out_n_exact, true, &retry, &fv));
   return COLTT_OK;
 }
 
@@ -2544,6 +2560,36 @@ int filter_search_common(Hnsw* x, HCtx* c, const HnswFilter* f, const float* que
 }
 
 
+// coltt_hnsw_pq_search_filtered (the entry point has checked that the index carries codes): the path is filter_path's, word for word; EXACT is filter_search_common's, WALK the walk over the quantiser's codes
+// at ef_walk (pq_search_once: the same grouping of queries, region lease, neighbourhood blocks and retry over the byte map) with the allowed set.
+int pq_filter_search_common(Hnsw* x, HCtx* c, const HnswFilter* f, const float* queries, size_t nq, uint32_t k, uint32_t ef_override, uint32_t rerank, int mode,
+                            uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_filter_stats* st) {
+  coltt_hnsw_filter_stats local{};
+  if (!st) st = &local;
+  std::memset(st, 0, sizeof(*st));
+  if (mode != COLTT_FILTER_AUTO && mode != COLTT_FILTER_WALK && mode != COLTT_FILTER_EXACT) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered: unknown mode %d", mode);
+  if (nq == 0) return COLTT_OK;
+  if (k == 0) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered: k must be >= 1");
+  if (nq > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search_filtered: more than 2^32-1 queries in one call");
+  const uint32_t ef = std::max<uint32_t>(ef_override ? ef_override : (uint32_t)x->cfg.ef, k);
+  if (ef > FILTER_EF_MAX) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search_filtered: ef=%u > %llu", ef, (unsigned long long)FILTER_EF_MAX);
+  uint32_t ef_walk = ef;
+  const int path = filter_path(f->allowed, x->live, ef, mode, ef_walk);
+  if (path == COLTT_FILTER_EXACT) return filter_search_common(x, c, f, queries, nq, k, ef_override, COLTT_FILTER_EXACT, out_ids, out_scores, out_counts, st);
+  st->path = COLTT_FILTER_WALK; st->ef_walk = ef_walk;
+  if (x->entry < 0 || f->allowed == 0) {   // empty index or empty filter: counts 0, not an error
+    std::memset(out_counts, 0, nq * 4);
+    return COLTT_OK;
+  }
+  coltt_hnsw_stats ws{};
+  uint64_t n_exact = 0;
+  const FilterView fv{f->bits.as<uint32_t>(), f->slots};
+  COLTT_TRY(pq_search_filtered_walk(x, c, fv, queries, nq, k, ef_walk, rerank, out_ids, out_scores, out_counts, &ws, &n_exact));
+  st->n_dist = ws.n_dist; st->n_exp = ws.n_exp; st->n_hops = ws.n_hops; st->n_visit_resets = 0; st->n_exact_rows = n_exact;
+  return COLTT_OK;
+}
+
+
 // ---- coltt_hnsw_search_filtered_batch: a filter per query.  Row i is the single-filter call on query i alone: its path from its own filter's
 // allowed count (filter_path), its walk at the geometry search_geom gives its ef_walk, its exact scan chunked by today's rules (the answer
 // is a pure top-k, so the chunking cannot change it).  One call launches at most two walks (LDS hash, HBM byte map), one scan, one select.
@@ -2799,6 +2845,26 @@ int coltt_hnsw_search_filtered(coltt_handle_t h, coltt_handle_t fh, const float*
   CtxLease<HCtx> ctx(x->pool);
   if (!ctx.c) return COLTT_E_DEVICE;
   return filter_search_common(x.get(), ctx.c, f.get(), queries, nq, k, ef_override, mode, out_ids, out_scores, out_counts, stats);
+}
+
+int coltt_hnsw_pq_search_filtered(coltt_handle_t h, coltt_handle_t fh, const float* queries, size_t nq, uint32_t k, uint32_t ef_override, uint32_t rerank, int mode,
+                                  uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_filter_stats* stats) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_pq_search_filtered: unknown index handle");
+  {   // no codes attached: checked first, for every mode
+    ReadLock g0(x->rw);
+    if (!x->pq_on) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered: the index carries no product-quantiser codes (coltt_hnsw_pq_attach)");
+  }
+  auto f = lookup<HnswFilter>(fh);   // held until the call returns: a concurrent destroy only unregisters it
+  if (!f) return fail(COLTT_E_NOT_FOUND, "hnsw_pq_search_filtered: unknown filter handle");
+  if (nq && (!queries || !out_ids || !out_scores || !out_counts)) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered: NULL buffer");
+  if (f->index != h) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered: the filter was built for another index");
+  ReadLock g(x->rw);
+  if (f->gen != x->gen) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered: the filter is stale (the index was loaded since it was built)");
+  COLTT_DEVICE(x->device);
+  CtxLease<HCtx> ctx(x->pool);
+  if (!ctx.c) return COLTT_E_DEVICE;
+  return pq_filter_search_common(x.get(), ctx.c, f.get(), queries, nq, k, ef_override, rerank, mode, out_ids, out_scores, out_counts, stats);
 }
 
 int coltt_hnsw_search_filtered_batch(coltt_handle_t h, const coltt_handle_t* filters, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,

@@ -467,18 +467,21 @@ __global__ __launch_bounds__(256) void hnsw_search_lat_kernel(GraphView g, int32
 // profiles/r05p_phase_breakdown.txt) and tied 24 instances of this kernel to the row format.
 // LS: the table's row length (log2) when it is one of the common ones (16, 32, 256 centroids), 0 = any; NP: 16-byte pieces per code row, 0 = any;
 // NBR: level-0 code rows come from the neighbourhood blocks, requested with the adjacency row (hnsw_pq.hpp: AdcEval<LS, NP, NBR>).
-template <int OPT, int VISMODE, int LS, int NP = 0, bool NBR = false>
+// FILTER (coltt_hnsw_pq_search_filtered, WALK): the same walk, plus the allowed set R (hnsw_dev.hpp: FiltSet; hnsw_walk2.hpp: search_level2<.., FILTER>) of
+// fcap entries, padded to 64, in LDS between the result set and the visited hash; the survivors handed to the re-rank are R's slots, nearest first, instead
+// of the result set's.  fv / fcap are read by the FILTER instances only.
+template <int OPT, int VISMODE, int LS, int NP = 0, bool NBR = false, bool FILTER = false>
 // amdgpu_waves_per_eu(3): <= 168 VGPRs, three waves per SIMD — the walk is latency-bound, resident traversals are its throughput
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void hnsw_pq_search_kernel(GraphView g, int32_t entry, int32_t entry_level, const unsigned short* __restrict__ lut_g,
                                                             const uint8_t* __restrict__ codes, const uint8_t* __restrict__ nbrc, uint32_t row_bytes, uint32_t lut_shift, uint32_t nq, uint32_t k,
                                                             uint32_t ef, uint32_t ef_pad, uint32_t rerank, uint32_t vis_words,
                                                             uint32_t* __restrict__ counter, uint32_t* __restrict__ surv, uint32_t* __restrict__ surv_cnt,
                                                             unsigned long long* __restrict__ stats, uint8_t* __restrict__ visg,
-                                                            size_t vis_stride, uint32_t* __restrict__ vis_epoch) {
+                                                            size_t vis_stride, uint32_t* __restrict__ vis_epoch, FilterView fv, uint32_t fcap) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x;
   WaveCtx w;
-  // LDS: [table | result set | visited hash or Bloom filter] — the table first: its lookups address it by immediate offsets (AdcEval<LS>).
+  // LDS: [table | result set | R (FILTER) | visited hash or Bloom filter] — the table first: its lookups address it by immediate offsets (AdcEval<LS>).
   // No copy of the query: the walk only needs its table.
   unsigned short* const lut = reinterpret_cast<unsigned short*>(smem);
   if constexpr (LS != 0) {   // AdcEval<LS> addresses the table by absolute LDS offsets: this kernel has no static LDS, so its dynamic LDS starts at 0
@@ -488,6 +491,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void hn
   w.qs = nullptr; w.qp = nullptr; w.scr = nullptr;
   w.res0 = reinterpret_cast<unsigned long long*>(smem + off); off += (size_t)ef_pad * 8;
   w.ef_pad = ef_pad;
+  FiltSet fs;
+  (void)fs;
+  if constexpr (FILTER) { fs.r = reinterpret_cast<unsigned long long*>(smem + off); off += (size_t)((fcap + 63u) & ~63u) * 8; fs.len = 0; fs.cap = fcap; fs.f = fv; }
   if constexpr (VISMODE == VIS_LDS) {
     w.vis = reinterpret_cast<uint32_t*>(smem + off); off += (size_t)vis_words * 4;
     w.hcap = vis_words; w.hcap_mask = vis_words - 1;
@@ -533,10 +539,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void hn
     w.n_dist += 1;  // searchLevel re-evaluates the entrypoint distance (hnsw.go:346)
     COLTT_PT(w, 5)  // table load + entry + upper levels
     uint32_t len;
-    search_level2<M_L2, Q_F16, PROF_SEARCH_HBM, OPT, VISMODE, true>(g, w, cur, curd, ef, lane, len, ev);  // :258-259 (M_L2: no norms ride along; Q_F16: the adjacency prefetch)
-    uint32_t r = rerank == 0 ? len : (rerank > k ? rerank : k);
-    r = r < len ? r : len;
-    for (uint32_t i = (uint32_t)lane; i < r; i += 64) surv[(size_t)qi * ef_pad + i] = (uint32_t)w.res0[i] >> 1;   // the r nearest by table distance, in that order
+    uint32_t r;
+    if constexpr (FILTER) {
+      search_level2<M_L2, Q_F16, PROF_SEARCH_HBM, OPT, VISMODE, true, AdcEval<LS, NP, NBR>&, true>(g, w, cur, curd, ef, lane, len, ev, &fs);
+      r = fs.len;   // <= fcap <= ef: the host folded `rerank` into fcap
+      for (uint32_t i = (uint32_t)lane; i < r; i += 64) surv[(size_t)qi * ef_pad + i] = (uint32_t)fs.r[i] >> 1;   // R, nearest first by table distance
+    } else {
+      search_level2<M_L2, Q_F16, PROF_SEARCH_HBM, OPT, VISMODE, true>(g, w, cur, curd, ef, lane, len, ev);  // :258-259 (M_L2: no norms ride along; Q_F16: the adjacency prefetch)
+      r = rerank == 0 ? len : (rerank > k ? rerank : k);
+      r = r < len ? r : len;
+      for (uint32_t i = (uint32_t)lane; i < r; i += 64) surv[(size_t)qi * ef_pad + i] = (uint32_t)w.res0[i] >> 1;   // the r nearest by table distance, in that order
+    }
     COLTT_PT(w, 6)  // final delta flush + survivors' write-out
     if (lane == 0) {
 #ifdef COLTT_PHASE_TIMING

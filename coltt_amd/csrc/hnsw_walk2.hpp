@@ -442,9 +442,15 @@ template <class T> __device__ __forceinline__ T vis_probe(const T* p) {
 enum { VIS_HBM = 0, VIS_LDS = 1 };   // visited set of search_level2: HBM byte map (behind the Bloom filter) | LDS hash that is never reset (err 8)
 
 // searchLevel (hnsw.go:345-389) on level 0.  On return res[0, len) holds the result set ascending by (d, slot).
-template <int METRIC, int QUANT, int PROFILE, int OPT, int VISMODE = VIS_HBM, bool ALWAYS_PREF = false, class EVAL = PairEval<METRIC, QUANT, PROFILE, (OPT & W2_ADJN) != 0 && METRIC == M_COS>>
+// FILTER (coltt_hnsw_pq_search_filtered, BOUNDED evaluators only): the same walk, plus the allowed set *fs (hnsw_dev.hpp: FiltSet) — the cap smallest keys
+// of the live allowed vertices among the entry point and every listed neighbour of every expanded vertex.  The table distance of a listed neighbour is on
+// hand whether or not it is fresh or under the bound, so the set depends only on WHICH vertices were expanded: every valid neighbour is offered where
+// its distance exists (EARLY: pre_d; set full at the pop: bounded_d), the fresh ones while the set is still filling (a non-fresh one was offered when
+// it was marked).  A vertex listed by many expanded vertices comes with the same key every time: sorted_offer's dedup keeps the set a set.
+template <int METRIC, int QUANT, int PROFILE, int OPT, int VISMODE = VIS_HBM, bool ALWAYS_PREF = false, class EVAL = PairEval<METRIC, QUANT, PROFILE, (OPT & W2_ADJN) != 0 && METRIC == M_COS>, bool FILTER = false>
 __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, uint32_t ep, float epd, uint32_t ef, int lane_in,
-                                              uint32_t& out_len, EVAL&& ev = EVAL()) {
+                                              uint32_t& out_len, EVAL&& ev = EVAL(), FiltSet* fs = nullptr) {
+  static_assert(!FILTER || std::remove_reference<EVAL>::type::BOUNDED, "the allowed set of a level-0 walk is defined for the walk over table distances");
   constexpr bool BLOOM = (OPT & W2_BLOOM) != 0 && VISMODE == VIS_HBM, DELTA = (OPT & W2_DELTA) != 0, ADJN = (OPT & W2_ADJN) != 0 && METRIC == M_COS;
 #ifdef COLTT_NO_ADJ_PREFETCH
   constexpr bool PREF = ALWAYS_PREF;
@@ -476,6 +482,11 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
       const uint32_t h = ep * 0x9E3779B1u;
       w.bloom[h >> w.bloom_shift] |= (1u << (h & 31u)) | (1u << ((h >> 5) & 31u));
     }
+  }
+  if constexpr (FILTER) {   // the level-0 entry point (the greedy descent only moves to live vertices; tested anyway)
+    fs->len = 0;
+    sorted_offer(fs->r, fs->len, fs->cap, lane == 0 && filter_allows(fs->f, ep) && !is_deleted(g, ep),
+                 ((unsigned long long)__float_as_uint(epd) << 32) | ((unsigned long long)ep << 1), lane, false);
   }
   uint32_t len = 1;
   uint32_t scan_lo = 0;   // every main-array member before this index is expanded (pop scans start at its 64-entry chunk)
@@ -595,6 +606,11 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
 #endif
       COLTT_PT(w, 1)  // adjacency row
       int fresh_i = 0;
+      // FILTER: the neighbour's allow-list word, requested beside the visited probe so that it flies under the same round trip.  Every lane loads (the
+      // others word 0 of the bitmap, which a filter that reaches a walk always has): see the probe below.
+      uint32_t fword = 0; bool fin = false;
+      (void)fword; (void)fin;
+      if constexpr (FILTER) { fin = valid && half == 0 && nb < fs->f.slots; fword = fs->f.bits[fin ? (nb >> 5) : 0u]; }
       if constexpr (eval_t::EARLY && VISMODE == VIS_HBM && !BLOOM) {
         // The probe of the byte map is ISSUED, the evaluator computes the distances of all listed neighbours out of inputs that are already on chip
         // (AdcEval<.., NBR>: the code rows came with the adjacency row), and only then is the probe's answer looked at: its round trip runs under
@@ -607,6 +623,7 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
         uint32_t vw = vis_probe(reinterpret_cast<const uint32_t*>(w.visg + (probe ? (nb & ~3u) : 0u)));
         ev.early(valid, half);
         ev.after_early(vw);   // the probe's value is not looked at (no s_waitcnt vmcnt for it) before the table sums are there
+        if constexpr (FILTER) ev.after_early(fword);
         const uint32_t v = (vw >> ((nb & 3u) * 8u)) & 0xffu;
         fresh_i = probe && v != (w.epoch & 0xffu) ? 1 : 0;
         if constexpr (eval_t::BOUNDED) { if (full_at_pop && !(ev.pre_d < lower_bound)) fresh_i = 0; }   // the bound: not marked, not counted
@@ -639,6 +656,14 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
       }
       fresh_i = __builtin_amdgcn_mov_dpp(fresh_i, 0xA0, 0xf, 0xf, true);  // even lane's verdict to its pair: quad_perm [0,0,2,2]
       const bool fresh = fresh_i != 0;
+      if constexpr (FILTER) {   // every valid neighbour whose table distance is on hand, fresh or not, under the bound or not
+        if (eval_t::EARLY || full_at_pop) {
+          float od;
+          if constexpr (eval_t::EARLY) od = ev.pre_d; else od = bounded_d;
+          sorted_offer(fs->r, fs->len, fs->cap, fin && ((fword >> (nb & 31u)) & 1u),
+                       ((unsigned long long)__float_as_uint(od) << 32) | ((unsigned long long)nb << 1), lane, true);
+        }
+      }
       const unsigned long long E = __ballot(fresh && half == 0);
       const uint32_t nfresh = __popcll(E);
       COLTT_PT(w, 2)  // visited test-and-set
@@ -649,6 +674,10 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
       if constexpr (eval_t::BOUNDED && !eval_t::EARLY) { if (full_at_pop) d = fresh ? bounded_d : 0.f; else d = ev(g, w, nb, fresh, nrm, half, lane); }
       else if constexpr (eval_row_filter<eval_t>::value) d = ev.filtered(g, w, nb, fresh, nrm, half, lane, lower_bound, full_at_pop);
       else d = ev(g, w, nb, fresh, nrm, half, lane);
+      if constexpr (FILTER && !eval_t::EARLY) {   // the set is still filling: the fresh ones (every non-fresh one was offered when it was marked)
+        if (!full_at_pop) sorted_offer(fs->r, fs->len, fs->cap, fresh && fin && ((fword >> (nb & 31u)) & 1u),
+                                       ((unsigned long long)__float_as_uint(d) << 32) | ((unsigned long long)nb << 1), lane, true);
+      }
       const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(E >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)E, 0u));   // fresh neighbours in front of this lane
       const bool adm = fresh && half == 0 && (rank < free_slots || d < lower_bound);
 #ifdef COLTT_PHASE_TIMING

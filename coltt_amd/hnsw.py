@@ -308,6 +308,19 @@ class Hnsw:
             return ids, sc, cnt, {"n_dist": st.n_dist, "n_exp": st.n_exp, "n_hops": st.n_hops, "n_exact": nx.value}
         return ids, sc, cnt
 
+    def PqSearchFiltered(self, queries, k, flt, ef=0, rerank=0, mode=FILTER_AUTO, with_stats=False):
+        """the k nearest among the ids of `flt` over the walk on the quantiser's codes (coltt_hnsw_pq_search_filtered); returns as SearchFiltered"""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        ids = np.zeros((nq, k), np.uint64); sc = np.zeros((nq, k), np.float32); cnt = np.zeros(nq, np.uint32)
+        st = HnswFilterStats()
+        L.check(L.lib().coltt_hnsw_pq_search_filtered(self.h, flt.h, L.vp(q), C.c_size_t(nq), C.c_uint32(k), C.c_uint32(ef), C.c_uint32(rerank),
+                                                      C.c_int(int(mode)), L.vp(ids), L.vp(sc), L.vp(cnt), C.byref(st)))
+        if with_stats:
+            return ids, sc, cnt, {"n_dist": st.n_dist, "n_exp": st.n_exp, "n_hops": st.n_hops, "n_visit_resets": st.n_visit_resets,
+                                  "ef_walk": st.ef_walk, "path": st.path, "n_exact_rows": st.n_exact_rows}
+        return ids, sc, cnt
+
     def PqSearchDevice(self, d_q, nq, k, d_ids, d_scores, d_counts, ef=0, rerank=0):
         st = HnswStats(); nx = C.c_uint64(0)
         L.check(L.lib().coltt_hnsw_pq_search_device(self.h, C.c_void_p(d_q), C.c_size_t(nq), C.c_uint32(k), C.c_uint32(ef), C.c_uint32(rerank),

@@ -146,3 +146,22 @@ func HnswPqSearch(h Handle, dim uint32, queries []float32, nq int, k, ef, rerank
 	})
 	return ids, sc, cnt, err
 }
+
+// HnswPqSearchFiltered: as HnswPqSearch, among the vertices filter f allows (coltt_hnsw_pq_search_filtered).  mode: FilterAuto / FilterWalk /
+// FilterExact, with the rule of HnswSearchFiltered: one filter takes the same path through either call.  One filter for the whole call.
+func HnswPqSearchFiltered(h, f Handle, dim uint32, queries []float32, nq int, k, ef, rerank uint32, mode int) ([]uint64, []float32, []uint32, error) {
+	if nq == 0 || k == 0 {
+		return nil, nil, make([]uint32, nq), nil
+	}
+	if err := checkDim(queries, dim, nq); err != nil {
+		return nil, nil, nil, err
+	}
+	ids := make([]uint64, nq*int(k))
+	sc := make([]float32, nq*int(k))
+	cnt := make([]uint32, nq)
+	err := call(func() C.int {
+		return C.coltt_hnsw_pq_search_filtered(h, f, fptr(queries), C.size_t(nq), C.uint32_t(k), C.uint32_t(ef), C.uint32_t(rerank), C.int(mode),
+			uptr(ids), fptr(sc), (*C.uint32_t)(unsafe.Pointer(&cnt[0])), nil)
+	})
+	return ids, sc, cnt, err
+}

@@ -430,6 +430,20 @@ func (xx *Hnsw) SearchFiltered(_ context.Context, query edge.Vector, k uint, f *
 	return xx.attach(ids, sc, int(cnt[0])), nil
 }
 
+// SearchFilteredPq(ctx, query, k, f, rerank) — SearchFiltered over the walk on product-quantiser codes, for an index that carries a quantiser
+// (colttgpu.HnswPqAttach(xx.Handle(), pq)); rerank as colttgpu.HnswPqSearch (0: every member of the allowed set is re-scored exactly).
+// The library's AUTO path, by the rule of SearchFiltered.
+func (xx *Hnsw) SearchFilteredPq(_ context.Context, query edge.Vector, k uint, f *HnswFilter, rerank uint) (SearchResult, error) {
+	if xx.err != nil {
+		return nil, xx.err
+	}
+	ids, sc, cnt, err := colttgpu.HnswPqSearchFiltered(xx.h, f.h, uint32(xx.dim), query, 1, uint32(k), 0, uint32(rerank), colttgpu.FilterAuto)
+	if err != nil {
+		return nil, err
+	}
+	return xx.attach(ids, sc, int(cnt[0])), nil
+}
+
 // SearchFilteredBatch(ctx, queries, k, filters) — a filter per query in one call: result i == SearchFiltered(ctx, queries[i], k, filters[i]).
 // One bad filter (closed, stale, of another index) fails the whole call; the micro-batcher's filtered mode (colttgpu.FilteredBatcher)
 // re-issues such a batch one query at a time.

@@ -245,7 +245,8 @@ int coltt_hnsw_search_device(coltt_handle_t h, const float* d_queries, size_t nq
  * 32 is the walk's row evaluations per unit of ef (n_dist / ef ~ 4 040 / 128 on the headline collection): below it the scan reads no
  * more rows than the walk would, and has no dependent chain (measured crossover: DESIGN.md, "Filtered search").
  *
- * An empty filter or an empty index gives counts of 0 and is not an error.  Not served: product-quantised walks, collection groups.
+ * An empty filter or an empty index gives counts of 0 and is not an error.  Not served: collection groups (the walk over product-quantiser codes
+ * takes one filter per call: coltt_hnsw_pq_search_filtered below).
  *
  * A FILTER PER QUERY (coltt_hnsw_search_filtered_batch).  filters[i] is query i's filter; row i equals
  * coltt_hnsw_search_filtered(hnsw, filters[i], query i, 1, k, ef_override, mode, ...) on the same index state: the same ids, the same
@@ -274,6 +275,26 @@ int coltt_hnsw_search_filtered(coltt_handle_t hnsw, coltt_handle_t filter, const
 int coltt_hnsw_search_filtered_batch(coltt_handle_t hnsw, const coltt_handle_t* filters /*[nq]*/, const float* queries, size_t nq,
                                      uint32_t k, uint32_t ef_override, int mode, uint64_t* out_ids, float* out_scores,
                                      uint32_t* out_counts, int32_t* out_paths /*[nq], may be NULL*/, coltt_hnsw_filter_stats* stats);
+
+/* FILTERED SEARCH OVER THE PRODUCT-QUANTISED WALK (coltt_hnsw_pq_search_filtered).  The filter object is the one above; one filter for the whole call.
+ *
+ * WALK.  With ef_walk as below, the walk is exactly coltt_hnsw_pq_search's walk at ef_walk (further down: table distance d = S_lo + S_hi, the canonical
+ * neighbour order, the stale lowerBound, bounded visiting, tombstoned neighbours skipped before anything else), so n_dist, n_exp and n_hops equal an
+ * unfiltered coltt_hnsw_pq_search at that ef on the same index state.  Let C be the set of LIVE ALLOWED vertices among the level-0 entry point and every
+ * listed neighbour of every vertex the level-0 walk expands — a listed neighbour counts whether or not it is fresh, under the bound, or admitted, so C
+ * depends only on which vertices were expanded.  R = the cap smallest members of C by (d bits, slot), cap = ef_walk when rerank == 0, else
+ * min(max(rerank, k), ef_walk).  Every member of R gets the index's exact distance (the re-rank of coltt_hnsw_pq_search); the answer is the k smallest by
+ * (exact score bits, slot), count = min(k, |R|).  Stats: path = WALK, ef_walk as chosen, n_exact_rows = the sum of |R| over the queries,
+ * n_visit_resets = 0.
+ * EXACT.  The exact path above, unchanged: the result of coltt_hnsw_search_filtered(..., COLTT_FILTER_EXACT).
+ * AUTO.  The rule above word for word (ef_need, ef_walk, EXACT when ef_need > 4096 or A <= 32 * ef_walk): one filter takes the same path through either
+ * entry point.
+ * Errors.  No codes attached: COLTT_E_INVALID as coltt_hnsw_pq_search, checked first for every mode; an unknown, foreign or stale filter: the codes of
+ * coltt_hnsw_search_filtered; ef > 4096 or an LDS need above 160 KiB: COLTT_E_UNSUPPORTED.  An empty filter or an empty index gives counts of 0 and
+ * no error; nq == 0 is not an error.  Host pointers only.  Not served: device pointers, a filter per query, collection groups. */
+int coltt_hnsw_pq_search_filtered(coltt_handle_t hnsw, coltt_handle_t filter, const float* queries, size_t nq, uint32_t k, uint32_t ef_override_or_0,
+                                  uint32_t rerank, int mode /* COLTT_FILTER_* */, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                  coltt_hnsw_filter_stats* stats);
 
 /* Capacity for n_slots vertices (and n_upper_rows upper-level adjacency rows; 0 = the expectation for this index's M) in ONE allocation per
  * array, before the inserts.  Optional — Insert grows the arrays by half their size when they are full — but an index whose final size is

@@ -191,6 +191,16 @@ class Hnsw {
     for (uint32_t i = 0; i < n; i++) r[i] = {ids[i], sc[i]};
     return r;
   }
+  // the same over the walk on product-quantiser codes (coltt_hnsw_pq_search_filtered; the index carries a quantiser: coltt_hnsw_pq_attach);
+  // rerank as coltt_hnsw_pq_search (0: every member of the allowed set is re-scored exactly)
+  SearchResult PqSearchFiltered(const Vector& query, unsigned k, const Filter& f, unsigned ef = 0, unsigned rerank = 0, int mode = COLTT_FILTER_AUTO,
+                                coltt_hnsw_filter_stats* stats = nullptr) const {
+    std::vector<uint64_t> ids(k); std::vector<float> sc(k); uint32_t n = 0;
+    check(coltt_hnsw_pq_search_filtered(h_, f.handle(), query.data(), 1, k, ef, rerank, mode, ids.data(), sc.data(), &n, stats));
+    SearchResult r(n);
+    for (uint32_t i = 0; i < n; i++) r[i] = {ids[i], sc[i]};
+    return r;
+  }
   // a filter per query (coltt_hnsw_search_filtered_batch): answer i == SearchFiltered(queries[i], k, *filters[i], ef, mode); paths (may be
   // null) receives the path each query took
   std::vector<SearchResult> SearchFilteredBatch(const std::vector<Vector>& queries, unsigned k, const std::vector<const Filter*>& filters,

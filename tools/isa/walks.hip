@@ -18,7 +18,7 @@ template __global__ void hnsw_search2_kernel<0, 1, 2, 7, 0, false, true, false>(
 #endif
 #if WALKS_SET & 4   // the walk over product-quantiser codes (64 x 32 quantiser: LS = 5, NP = 4; 32 x 256: LS = 8, NP = 2), gathered code rows | neighbourhood blocks
 #define PQK(LS, NP, NBR) template __global__ void hnsw_pq_search_kernel<2, 0, LS, NP, NBR>(GraphView, int32_t, int32_t, const unsigned short*, const uint8_t*, const uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, \
-    uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*);
+    uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*, FilterView, uint32_t);
 PQK(5, 0, false)
 PQK(5, 4, false)
 PQK(5, 4, true)
@@ -40,6 +40,22 @@ template __global__ void hnsw_search2_kernel<0, 0, 1, 4, 1, false, true, false, 
     uint32_t*, uint64_t*, float*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*);
 template __global__ void hnsw_search2_kernel<0, 1, 2, 7, 0, false, true, false, true>(GraphView, int32_t, int32_t, const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
     uint32_t*, uint64_t*, float*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*);
+#endif
+#if WALKS_SET & 96   // every shipped instance of the walk over product-quantiser codes — the (LS, NP) dispatch of launch_pq_walk x {LDS hash, byte map + gather,
+                     // byte map + neighbourhood blocks} — 32: unfiltered, 64: the FILTER instances (coltt_hnsw_pq_search_filtered)
+#define PQF(OPT, VIS, LS, NP, NBR, F) template __global__ void hnsw_pq_search_kernel<OPT, VIS, LS, NP, NBR, F>(GraphView, int32_t, int32_t, const unsigned short*, const uint8_t*, const uint8_t*, uint32_t, uint32_t, \
+    uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*, FilterView, uint32_t);
+#define PQF3(LS, NP, F) PQF(0, 1, LS, NP, false, F) PQF(2, 0, LS, NP, false, F) PQF(2, 0, LS, NP, true, F)
+#define PQF_ALL(F) PQF3(5, 4, F) PQF3(4, 4, F) PQF3(8, 2, F) PQF3(8, 6, F) PQF3(4, 0, F) PQF3(5, 0, F) PQF3(8, 0, F) PQF3(0, 0, F)
+#if WALKS_SET & 32
+PQF_ALL(false)
+#endif
+#if WALKS_SET & 64
+PQF_ALL(true)
+#endif
+#undef PQF_ALL
+#undef PQF3
+#undef PQF
 #endif
 }  // namespace kern
 }  // namespace coltt
