@@ -83,6 +83,7 @@ Policy read_policy_from_env() {
   v = num("COLTT_ROW_FILTER", set); p.row_filter = set ? (v > 0 ? 1 : 0) : -1;
   p.row_shadow = !off("COLTT_ROW_SHADOW");
   v = num("COLTT_ROW_FILTER_BITS", set); p.row_filter_bits = set && (v == 8 || v == 16) ? (int)v : 0;
+  { const char* e = getenv("COLTT_ROW_FILTER_BITS"); if (e && !strcmp(e, "8i")) p.row_filter_bits = 80; }   // row_filter8i.hpp: ROW_FILTER_8I
   { const char* e = getenv("COLTT_ROW_SHADOW_BITS"); p.row_shadow_bits = (!e || !*e) ? 8 : (!strcmp(e, "both") ? 24 : (atoi(e) == 16 ? 16 : 8)); }
   v = num("COLTT_ROWS_NT_MIN_MB", set); p.rows_nt_min_mb = set ? std::max<long long>(0, v) : 12288;
   v = num("COLTT_PQ_WAVES", set); p.pq_waves = set ? (int)std::max<long long>(1, std::min<long long>(16, v)) : 0;

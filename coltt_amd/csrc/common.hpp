@@ -112,7 +112,7 @@ struct Policy {
   int rows_nt = -1;            // COLTT_ROWS_NT: non-temporal row loads in the eight-lane walks: -1 = by the size of the row array (default), 0 never, 1 always
   int row_filter = -1;         // COLTT_ROW_FILTER: the certified level-0 row filter of the eight-lane f32 cosine walks (row_filter.hpp): -1 = where rows_nt holds (default), 0 never, 1 wherever the index has its shadow
   bool row_shadow = true;      // COLTT_ROW_SHADOW=0 (read at create): new f32 cosine indexes keep no binary16 shadow of their rows (dim * 2 bytes per slot), hence no filter
-  int row_filter_bits = 0;     // COLTT_ROW_FILTER_BITS = 8 / 16: the shadow a filtered launch reads (row_filter8.hpp / row_filter.hpp); 0 = unset: 8 where the index keeps it, else 16.  The other kind serves where the asked one is missing
+  int row_filter_bits = 0;     // COLTT_ROW_FILTER_BITS = 8 / 16 / 8i (= 80): the shadow a filtered launch reads (row_filter8.hpp / row_filter.hpp / row_filter8i.hpp: the 8-bit shadow against the quantised query); 0 = unset: 8i where the index keeps the 8-bit shadow, else 16.  The other kind serves where the asked one is missing
   int row_shadow_bits = 8;     // COLTT_ROW_SHADOW_BITS = 8 / 16 / both (read at create): which shadows a new f32 cosine index keeps — bit 3: the 8-bit codes (dim bytes per slot + 8 bytes per slot and per level-0 edge), bit 4: binary16 (dim * 2 bytes per slot)
   long long rows_nt_min_mb = 12288;  // COLTT_ROWS_NT_MIN_MB: ... row arrays of at least this many MiB (see exact.hpp: row_ld; measured crossover: profiles/r06ag_nt_rows_ab.md)
   int pq_waves = 0;            // COLTT_PQ_WAVES: resident traversals per CU of the product-quantised walk, 0 = the default cap

@@ -642,7 +642,7 @@ int prep_queries_any(Hnsw* x, HCtx* c, const float* d_qraw, size_t nq, uint32_t*
 
 uint32_t next_pow2(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
 
-struct SearchGeom { uint32_t ef, ef_pad, hcap; size_t lds; bool visg; uint32_t max_grid; int w2 = -1; uint32_t bloom_words = 0; bool w2_lds = false; bool ev8 = false; };  // w2: hnsw_walk2.hpp variant (OPT bits | 8 = deep profile), -1 = hnsw_dev.hpp:search_level
+struct SearchGeom { uint32_t ef, ef_pad, hcap; size_t lds; bool visg; uint32_t max_grid; int w2 = -1; uint32_t bloom_words = 0; bool w2_lds = false; bool ev8 = false; bool qd8i = false; };  // w2: hnsw_walk2.hpp variant (OPT bits | 8 = deep profile), -1 = hnsw_dev.hpp:search_level
 
 #ifndef COLTT_VISG_MIN_EF
 #define COLTT_VISG_MIN_EF 128
@@ -756,6 +756,9 @@ size_t waves_per_cu_cap(int quant);
 // COLTT_EV8=0: level-0 distances from the pair-owned rows even when the index carries the line-transposed copy (A/B and test knob)
 bool ev8_policy() { return policy().ev8; }
 
+int row_filter_bits(const Hnsw* x);
+bool row_filter_on(const Hnsw* x, bool vis_hbm);
+
 // filt_k > 0: the filtered walk's allowed set (k rounded up to 64 entries) sits beside the result set (hnsw_kernels.hpp: search_one_wave)
 SearchGeom search_geom(Hnsw* x, uint32_t ef, bool for_search = false, bool no_w2_lds = false, uint32_t filt_k = 0) {
   SearchGeom s;
@@ -767,7 +770,10 @@ SearchGeom search_geom(Hnsw* x, uint32_t ef, bool for_search = false, bool no_w2
   const bool vis_hbm = wants_visg(ef) && x->vis_stride != 0 && x->vis_regions > 0;
   const bool want8 = for_search && x->r8 && x->n > 0 && ev8_policy() && x->cfg.m_max0 <= 1024 &&
                      (vis_hbm ? (walk2_policy() == 6 || walk2_policy() == 7) : (!no_w2_lds && walk2_lds_policy() == 4));
-  const size_t fixed = qbytes + (want8 ? 96 * 4 : 0) + (size_t)s.ef_pad * 8 + (size_t)((filt_k + 63) & ~63u) * 8;   // query (+ the eight-lane core's scratch) + result set (merged in place) (+ the allowed set)
+  // the row filter over the quantised query (row_filter8i.hpp): two planes of dim signed bytes per wave behind the scratch (hnsw_kernels.hpp:
+  // hnsw_search2_rowfilter_kernel).  768-d, ef 128: 4 x (37 248 + 1 536) = 155 136 bytes per CU, four traversals still fit.
+  s.qd8i = want8 && filt_k == 0 && x->metric == COLTT_COSINE && x->quant == COLTT_Q_NONE && row_filter_on(x, vis_hbm) && row_filter_bits(x) == ROW_FILTER_8I;
+  const size_t fixed = qbytes + (want8 ? 96 * 4 : 0) + (s.qd8i ? (size_t)x->dim * 2 : 0) + (size_t)s.ef_pad * 8 + (size_t)((filt_k + 63) & ~63u) * 8;   // query (+ the eight-lane core's scratch) (+ the digit planes) + result set (merged in place) (+ the allowed set)
   // LDS visited set: sized so that a typical traversal (a few dozen evaluations per result slot) never resets
   s.hcap = std::min<uint32_t>(32768u, std::max<uint32_t>(8192u, next_pow2(ef * 48u)));
   // large ef x dim: shrink it until the wave's state fits the CU's 160 KiB (the reset-and-reseed path keeps results exact;
@@ -819,14 +825,21 @@ uint32_t resident_waves(const SearchGeom& sg, int quant) {
 // one process runs both kernels, tools/row_filter_ab.py); unset: on for the LDS-hash walk (ef <= 128, the measured instance: 10 M x 768, ef 128, 1.41 x in one
 // process, profiles/r07a_row_filter.md) where the row array is far larger than the caches: every row read is then an HBM read and the kernel sits at what the
 // memory system delivers, so bytes are time.
-// COLTT_ROW_FILTER_BITS = 8 / 16 picks the shadow a filtered launch reads (row_filter_bits); unset: the 8-bit one where the index keeps it.  An index keeps
-// what COLTT_ROW_SHADOW_BITS said when it was created; the kind it does not keep is served by the one it does.
+// COLTT_ROW_FILTER_BITS = 8 / 16 / 8i picks the shadow a filtered launch reads (row_filter_bits); unset: the 8-bit one where the index keeps it.  An index keeps
+// what COLTT_ROW_SHADOW_BITS said when it was created; the kind it does not keep is served by the one it does.  8i (ROW_FILTER_8I) reads the 8-bit shadow
+// against the query quantised once per traversal: phase A is an integer sum (row_filter8i.hpp); it is what an unset knob takes over the 8-bit shadow
+// (COLTT_ROW_FILTER8I_DEFAULT; the measurement behind it: profiles/r10a_row_filter8i.md).
+#ifndef COLTT_ROW_FILTER8I_DEFAULT
+#define COLTT_ROW_FILTER8I_DEFAULT 1
+#endif
 int row_filter_bits(const Hnsw* x) {
   const bool h8 = x->has_shadow8(), h16 = x->has_shadow16();
   if (!h8 && !h16) return 0;
   const int want = policy().row_filter_bits;
   if (want == 16) return h16 ? 16 : 8;
-  return h8 ? 8 : 16;
+  if (want == 8) return h8 ? 8 : 16;
+  if (want == ROW_FILTER_8I) return h8 ? ROW_FILTER_8I : 16;
+  return h8 ? (COLTT_ROW_FILTER8I_DEFAULT ? ROW_FILTER_8I : 8) : 16;
 }
 bool row_filter_on(const Hnsw* x, bool vis_hbm) {
   if (!x->has_shadow8() && !x->has_shadow16()) return false;
@@ -866,7 +879,9 @@ int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32
         }
         if constexpr (METRIC == M_COS && QUANT == Q_NONE) {   // the row-filter twin of the eight-lane instance just chosen
           if (sg.ev8 && row_filter_on(x, false)) {
-            if (row_filter_bits(x) == 8) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, 8>;
+            const int fb = row_filter_bits(x);
+            if (fb == ROW_FILTER_8I && sg.qd8i) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, ROW_FILTER_8I>;   // (sg.qd8i: search_geom made room for the digit planes)
+            else if (fb == 8 || fb == ROW_FILTER_8I) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, 8>;
             else kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false>;
             flt = true;
           }
@@ -884,7 +899,11 @@ int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32
       if (sg.ev8 && row_filter_on(x, true) && (sg.w2 == 6 || sg.w2 == 7)) flt = true;
       if (flt && sg.w2 == 6) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false>;
       if (flt && sg.w2 == 7) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false>;
-      if (flt && row_filter_bits(x) == 8) {
+      const int fb = flt ? row_filter_bits(x) : 0;
+      if (fb == ROW_FILTER_8I && sg.qd8i) {
+        if (sg.w2 == 6) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false, ROW_FILTER_8I>;
+        if (sg.w2 == 7) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false, ROW_FILTER_8I>;
+      } else if (fb == 8 || fb == ROW_FILTER_8I) {
         if (sg.w2 == 6) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false, 8>;
         if (sg.w2 == 7) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false, 8>;
       }
@@ -903,6 +922,12 @@ int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32
   if (sg.ev8) x->ev8_launches.fetch_add(1);
   c->flt_launch = flt;
   COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
+  static const bool dbg_occ = [] { const char* e = getenv("COLTT_DEBUG_OCCUPANCY"); return e && *e == '1'; }();   // diagnostics: the waves the runtime keeps resident per CU at this launch's LDS
+  if (dbg_occ) {
+    int per_cu = 0;
+    COLTT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64, sg.lds));
+    fprintf(stderr, "[occupancy] walk variant %d%s filter %d (8i planes %d): %zu B of LDS per wave, %d waves resident per CU, grid %u\n", sg.w2, sg.w2_lds ? " (LDS hash)" : "", flt ? 1 : 0, sg.qd8i ? 1 : 0, sg.lds, per_cu, grid);
+  }
   kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
                                         k, sg.ef, sg.ef_pad, sg.w2_lds ? sg.hcap : sg.bloom_words, counter, oi, os, oc, stats,
                                         x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
@@ -2367,13 +2392,20 @@ int coltt_hnsw_fetch_shadow8(coltt_handle_t h, uint64_t first_slot, uint64_t n, 
 
 int coltt_hnsw_row_filter_probe(coltt_handle_t h, const float* queries, size_t nq, const uint32_t* slots, const float* lower_bound, int bits, int nt,
                                 int full_at_pop, float* out_r, float* out_qnorm, float* out_rnorm, uint32_t* out_counts) {
+  if (bits != 8 && bits != 16) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: bits must be 8 or 16");
+  return coltt_hnsw_row_filter_probe_ex(h, queries, nq, slots, lower_bound, bits, nt, full_at_pop, out_r, out_qnorm, out_rnorm, out_counts, nullptr, nullptr);
+}
+
+int coltt_hnsw_row_filter_probe_ex(coltt_handle_t h, const float* queries, size_t nq, const uint32_t* slots, const float* lower_bound, int bits, int nt,
+                                   int full_at_pop, float* out_r, float* out_qnorm, float* out_rnorm, uint32_t* out_counts, int64_t* out_isum, float* out_qte) {
   auto x = lookup<Hnsw>(h);
   if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_row_filter_probe: unknown handle");
-  if (bits != 8 && bits != 16) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: bits must be 8 or 16");
+  if (bits != 8 && bits != 16 && bits != ROW_FILTER_8I) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: bits must be 8, 16 or 80 (8i)");
+  const bool k8i = bits == ROW_FILTER_8I;
   if (nq && (!queries || !slots || !lower_bound || !out_r || !out_qnorm || !out_rnorm || !out_counts)) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: NULL buffer");
   if (nq > 0x7fffffffu / 32) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: too many queries");
   ReadLock g(x->rw);
-  if (!x->r8 || (bits == 8 ? !x->has_shadow8() : !x->has_shadow16())) return fail(COLTT_E_UNSUPPORTED, "hnsw_row_filter_probe: the index keeps no %d-bit shadow", bits);
+  if (!x->r8 || (bits != 16 ? !x->has_shadow8() : !x->has_shadow16())) return fail(COLTT_E_UNSUPPORTED, "hnsw_row_filter_probe: the index keeps no %d-bit shadow", bits == 16 ? 16 : 8);
   if (nq == 0) return COLTT_OK;
   for (size_t i = 0; i < nq * 32; i++)
     if (slots[i] != NBR_NONE && slots[i] >= x->n) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: slot %u outside [0,%llu)", slots[i], (unsigned long long)x->n);
@@ -2385,7 +2417,8 @@ int coltt_hnsw_row_filter_probe(coltt_handle_t h, const float* queries, size_t n
   COLTT_TRY(c->w_qraw.reserve(nq * dim * 4));
   COLTT_TRY(c->w_misc.reserve(256));
   // one block of inputs and outputs: slots [nq][32] | lower_bound [nq] | out_r [nq][32] | out_rnorm [nq][32] | out_counts [nq][3]
-  COLTT_TRY(c->w_out_ids.reserve(nq * (32 * 3 + 1 + 3) * 4));
+  // (8i: | pad to 8 bytes | out_isum [nq][32] i64 | out_qte [nq][2])
+  COLTT_TRY(c->w_out_ids.reserve(nq * (32 * 3 + 1 + 3) * 4 + 8 + nq * (32 * 8 + 2 * 4)));
   uint32_t* d_slots = c->w_out_ids.as<uint32_t>();
   float* d_lb = reinterpret_cast<float*>(d_slots + nq * 32);
   float* d_r = d_lb + nq; float* d_rn = d_r + nq * 32;
@@ -2394,11 +2427,19 @@ int coltt_hnsw_row_filter_probe(coltt_handle_t h, const float* queries, size_t n
   COLTT_HIP(hipMemcpyAsync(d_slots, slots, nq * 32 * 4, hipMemcpyHostToDevice, c->stream));
   COLTT_HIP(hipMemcpyAsync(d_lb, lower_bound, nq * 4, hipMemcpyHostToDevice, c->stream));
   COLTT_TRY(prep_queries_any(x.get(), c, c->w_qraw.as<float>(), nq, c->w_misc.as<uint32_t>()));   // Normalize the queries as Search does
-  const size_t lds = ((dim * 4 + 15) & ~(size_t)15) + 96 * 4;
-  auto kern = bits == 8 ? (nt ? hnsw_row_filter_probe_kernel<true, 8> : hnsw_row_filter_probe_kernel<false, 8>)
+  long long* d_isum = reinterpret_cast<long long*>((reinterpret_cast<uintptr_t>(d_cnt + nq * 3) + 7) & ~(uintptr_t)7);
+  float* d_qte = reinterpret_cast<float*>(d_isum + nq * 32);
+  if (k8i) COLTT_HIP(hipMemsetAsync(d_isum, 0, nq * (32 * 8 + 2 * 4), c->stream));
+  const size_t lds = ((dim * 4 + 15) & ~(size_t)15) + 96 * 4 + (k8i ? dim * 2 : 0);   // 8i: the digit planes behind the scratch
+  auto kern = k8i ? (nt ? hnsw_row_filter_probe_kernel<true, ROW_FILTER_8I> : hnsw_row_filter_probe_kernel<false, ROW_FILTER_8I>)
+            : bits == 8 ? (nt ? hnsw_row_filter_probe_kernel<true, 8> : hnsw_row_filter_probe_kernel<false, 8>)
                         : (nt ? hnsw_row_filter_probe_kernel<true, 16> : hnsw_row_filter_probe_kernel<false, 16>);
-  kern<<<(uint32_t)nq, 64, lds, c->stream>>>(x->view(), c->w_qeff.as<float>(), c->w_qn.as<float>(), d_slots, d_lb, full_at_pop ? 1 : 0, d_r, d_rn, d_cnt);
+  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  kern<<<(uint32_t)nq, 64, lds, c->stream>>>(x->view(), c->w_qeff.as<float>(), c->w_qn.as<float>(), d_slots, d_lb, full_at_pop ? 1 : 0, d_r, d_rn, d_cnt,
+                                             k8i ? d_isum : nullptr, k8i ? d_qte : nullptr);
   COLTT_HIP(hipGetLastError());
+  if (k8i && out_isum) COLTT_HIP(hipMemcpyAsync(out_isum, d_isum, nq * 32 * 8, hipMemcpyDeviceToHost, c->stream));
+  if (k8i && out_qte) COLTT_HIP(hipMemcpyAsync(out_qte, d_qte, nq * 2 * 4, hipMemcpyDeviceToHost, c->stream));
   COLTT_HIP(hipMemcpyAsync(out_r, d_r, nq * 32 * 4, hipMemcpyDeviceToHost, c->stream));
   COLTT_HIP(hipMemcpyAsync(out_rnorm, d_rn, nq * 32 * 4, hipMemcpyDeviceToHost, c->stream));
   COLTT_HIP(hipMemcpyAsync(out_counts, d_cnt, nq * 3 * 4, hipMemcpyDeviceToHost, c->stream));

@@ -261,6 +261,8 @@ __global__ __launch_bounds__(64) void hnsw_search2_rowfilter_kernel(GraphView g,
   w.qp = reinterpret_cast<float*>(smem); w.qs = nullptr;   // [query in rows8 order | scratch | result set | visited hash or Bloom filter], as hnsw_search2_kernel<.., EV8>
   w.scr = reinterpret_cast<uint32_t*>(smem + off);
   off += 96 * 4;
+  [[maybe_unused]] uint8_t* qd = nullptr;   // BITS == ROW_FILTER_8I: the query's two digit planes between the scratch and the result set (search_geom: qd_bytes)
+  if constexpr (BITS == ROW_FILTER_8I) { qd = smem + off; off += (size_t)g.dim * 2; }
   w.res0 = reinterpret_cast<unsigned long long*>(smem + off);
   w.ef_pad = ef_pad;
   if constexpr (VISMODE == VIS_LDS) {
@@ -288,6 +290,12 @@ __global__ __launch_bounds__(64) void hnsw_search2_rowfilter_kernel(GraphView g,
     for (int e = lane; e < g.dim; e += 64) w.qp[rows8_qindex<Q_NONE>(e)] = q_eff[(size_t)qi * g.dim + e];
     w.qnorm = qnorms[qi];
     wave_sync();
+    Group8FilterEval<M_COS, Q_NONE, true, NT, BITS> fev;
+    if constexpr (BITS == ROW_FILTER_8I) {   // the query's digit planes, scale and error norm: once per traversal
+      fev.qd = qd;
+      query_digits8i(w.qp, qd, g.dim, lane, fev.qt, fev.qe);
+      wave_sync();
+    }
     uint32_t cur = (uint32_t)entry;
     float curd = Group8Eval<M_COS, Q_NONE, false, false, NT>().one(g, w, cur, lane);   // hnsw.go:253
     curd = __shfl(curd, 0, 64);
@@ -296,7 +304,6 @@ __global__ __launch_bounds__(64) void hnsw_search2_rowfilter_kernel(GraphView g,
     COLTT_PT(w, 5)
     w.n_dist += 1;  // searchLevel re-evaluates the entrypoint distance (hnsw.go:346)
     uint32_t len;
-    Group8FilterEval<M_COS, Q_NONE, true, NT, BITS> fev;
     search_level2<M_COS, Q_NONE, PROFILE, OPT, VISMODE, false>(g, w, cur, curd, ef, lane, len, fev);  // :258-259
     const uint32_t n = len < k ? len : k;  // selectNeighbors + pop (:261-277) == the k smallest, ascending
     for (uint32_t i = lane; i < n; i += 64) {
@@ -331,7 +338,8 @@ __global__ __launch_bounds__(64) void hnsw_search2_rowfilter_kernel(GraphView g,
 template <bool NT, int BITS>
 __global__ __launch_bounds__(64) void hnsw_row_filter_probe_kernel(GraphView g, const float* __restrict__ q_eff, const float* __restrict__ qnorms,
                                                                   const uint32_t* __restrict__ slots, const float* __restrict__ lower_bound, int full_at_pop,
-                                                                  float* __restrict__ out_r, float* __restrict__ out_rnorm, uint32_t* __restrict__ out_counts) {
+                                                                  float* __restrict__ out_r, float* __restrict__ out_rnorm, uint32_t* __restrict__ out_counts,
+                                                                  long long* __restrict__ out_isum, float* __restrict__ out_qte) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x;
   const uint32_t qi = blockIdx.x;
@@ -347,10 +355,20 @@ __global__ __launch_bounds__(64) void hnsw_row_filter_probe_kernel(GraphView g, 
   const bool fresh = nb != NBR_NONE;
   const float nrm = fresh ? g.norms[nb] : 0.f;
   Group8FilterEval<M_COS, Q_NONE, true, NT, BITS> fev;
-  if constexpr (BITS == 8) fev.mt = fresh ? g.rows_m[nb] : float2{0.f, 0.f};
+  if constexpr (BITS == 8 || BITS == ROW_FILTER_8I) fev.mt = fresh ? g.rows_m[nb] : float2{0.f, 0.f};
+  if constexpr (BITS == ROW_FILTER_8I) {   // the walk's own prologue step: the planes behind the scratch
+    uint8_t* const qd = smem + off + 96 * 4;
+    fev.qd = qd;
+    query_digits8i(w.qp, qd, g.dim, lane, fev.qt, fev.qe);
+    wave_sync();
+  }
   float r = 0.f;
   if (__ballot(fresh)) r = fev.filtered(g, w, nb, fresh, nrm, half, lane, lower_bound[qi], full_at_pop != 0);   // (wave-uniform)
   if (half == 0) { out_r[(size_t)qi * 32 + p] = r; out_rnorm[(size_t)qi * 32 + p] = nrm; }
+  if constexpr (BITS == ROW_FILTER_8I) {   // the integer sum of every fresh pair of a full-set call, and the query's (scale, error norm)
+    if (out_isum && half == 0) out_isum[(size_t)qi * 32 + p] = fev.isum;
+    if (out_qte && lane == 0) { out_qte[(size_t)qi * 2] = fev.qt; out_qte[(size_t)qi * 2 + 1] = fev.qe; }
+  }
   if (lane == 0) { out_counts[(size_t)qi * 3] = fev.n_rej; out_counts[(size_t)qi * 3 + 1] = fev.n_f32; out_counts[(size_t)qi * 3 + 2] = fev.n_h16; }
 }
 

@@ -318,12 +318,15 @@ template <int METRIC, int QUANT, bool ADJN, bool HBM16 = false, bool NT = false>
 // full-set chunk reads BOTH its shadow row and its f32 row: n_h16 - n_rej = the survivors, n_f32 - (n_h16 - n_rej) = rows read while the set was filling.
 // BITS: which shadow phase A reads — 16: rows_h (row_filter.hpp), 8: rows_b with the neighbours' (scale, error norm) from the adjacency row
 // (GraphView::adj0_m; row_filter8.hpp).  No binary16 stage between the 8-bit shadow and the f32 row.
-// mt: the neighbour's (scale, error norm), set by search_level2 per chunk (BITS == 8 only; the binary16 twin never touches it).
+// mt: the neighbour's (scale, error norm), set by search_level2 per chunk (the 8-bit kinds only; the binary16 twin never touches it).
+// BITS == ROW_FILTER_8I: the 8-bit shadow against the QUANTISED query — phase A is an exact integer sum (rows8.hpp: group8_burst_bi / group8_stream_bi;
+// row_filter8i.hpp has the bound).  qd / qt / qe: the query's digit planes in LDS, its scale and its error norm, set once per traversal by the kernel's
+// prologue (rows8.hpp: query_digits8i).  isum: the integer sum of this lane's neighbour in the last call (read by the probe kernel alone).
 template <int METRIC, int QUANT, bool ADJN, bool NT, int BITS = 16> struct Group8FilterEval {
   static_assert(METRIC == M_COS && QUANT == Q_NONE && ADJN, "the row filter covers f32 cosine rows whose norms ride with the adjacency rows");
   typedef Group8Eval<METRIC, QUANT, ADJN, false, NT> base_t;
   static constexpr bool ROW_FILTER = true;
-  static constexpr bool ROW_META = BITS == 8;   // search_level2 reads adj0_m beside adj0_n
+  static constexpr bool ROW_META = BITS == 8 || BITS == ROW_FILTER_8I;   // search_level2 reads adj0_m beside adj0_n
   static constexpr bool CHUNK_ADJ = false;
   static constexpr bool RADJ = false;
   static constexpr bool ROWPF = false;
@@ -331,6 +334,7 @@ template <int METRIC, int QUANT, bool ADJN, bool NT, int BITS = 16> struct Group
   static constexpr bool BOUNDED = false;
   uint32_t n_rej = 0, n_f32 = 0, n_h16 = 0;
   float2 mt = {0.f, 0.f};
+  const uint8_t* qd = nullptr; float qt = 0.f, qe = 0.f; long long isum = 0;
   __device__ __forceinline__ uint32_t chunk_adj(int, int) const { return NBR_NONE; }
   __device__ __forceinline__ void prefetch(uint32_t, bool, int) const {}
   __device__ __forceinline__ float operator()(const GraphView& g, const WaveCtx& w, uint32_t nb, bool fresh, float nrm, int half, int lane) const {
@@ -349,13 +353,25 @@ template <int METRIC, int QUANT, bool ADJN, bool NT, int BITS = 16> struct Group
     }
     const uint32_t rank = (uint32_t)__popcll(E & ((1ull << lane) - 1ull));
     uint32_t* const s_nb = w.scr; float* const s_nr = reinterpret_cast<float*>(w.scr + 32); float* const s_d = reinterpret_cast<float*>(w.scr + 64);
-    if (mine) { s_nb[rank] = nb; if constexpr (BITS != 8) s_nr[rank] = nrm; }   // (the 8-bit bound is formed from registers: no norm in the scratch)
+    if (mine) { s_nb[rank] = nb; if constexpr (!ROW_META) s_nr[rank] = nrm; }   // (the 8-bit bound is formed from registers: no norm in the scratch)
     wave_sync();
     const int grp = lane >> 3, rj = lane & 7;
     [[maybe_unused]] const size_t hstride = (size_t)g.dim * 2;
     // phase A: shadow rows.
     float d_lo;
-    if constexpr (BITS == 8) {
+    if constexpr (BITS == ROW_FILTER_8I) {
+      // 8-bit codes against the query's digit planes: the dispatch of the f32 sum below, integer sums.  H and L come back through the two halves of the
+      // scratch that phase A leaves free (the norms' and the distances'); I = 128 H + L in 64 bits.
+      const int nlb = nl >> 2;
+      int* const s_h = reinterpret_cast<int*>(w.scr + 64); int* const s_l = reinterpret_cast<int*>(w.scr + 32);
+      if (nlb == 6) group8_burst_bi<6, NT>(g.rows_b, (size_t)g.dim, s_nb, s_h, s_l, nf, grp, rj, qd);
+      else if (nlb == 2) group8_burst_bi<2, NT>(g.rows_b, (size_t)g.dim, s_nb, s_h, s_l, nf, grp, rj, qd);
+      else if (nlb % 6 == 0) group8_stream_bi<6, 2, NT>(g.rows_b, (size_t)g.dim, s_nb, s_h, s_l, nf, grp, rj, qd, g.dim, nlb);
+      else group8_stream_bi<2, 2, NT>(g.rows_b, (size_t)g.dim, s_nb, s_h, s_l, nf, grp, rj, qd, g.dim, nlb);
+      wave_sync();
+      isum = mine ? 128ll * (long long)s_h[rank] + (long long)s_l[rank] : 0ll;
+      d_lo = mine ? row_filter8i_dlo(isum, qt, qe, mt.x, mt.y, g.dim, w.qnorm, nrm) : 0.f;
+    } else if constexpr (BITS == 8) {
       // 8-bit codes.  Rows of 6 or 2 shadow lines (768-d, 256-d): the chunk's at most 32 rows in ONE burst (4 rows x 6 lines = 96 VGPRs per lane).  Every
       // other width: a stream of bursts, two rows per lane group — whole rows of 6 lines per burst where they divide (1536-d ...), else bursts of 2
       // (512-d, 1024-d ...).  The raw sums come back through the scratch; the bound is formed by the lane that holds (norm, s, e) in registers.

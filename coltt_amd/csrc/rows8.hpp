@@ -25,6 +25,7 @@
 #include "exact.hpp"
 #include "row_filter.hpp"
 #include "row_filter8.hpp"
+#include "row_filter8i.hpp"
 
 namespace coltt {
 namespace dev {
@@ -494,6 +495,159 @@ __device__ __forceinline__ void group8_burst_b(const uint8_t* __restrict__ rows_
     const float sum = group8_hsum(acc[i]);
     const uint32_t idx = (uint32_t)(i * 8 + grp);
     if (rj == 0 && idx < nf) s_g[idx] = sum;
+  }
+}
+
+// ---- INTEGER phase A over the 8-bit shadow: the query quantised once per traversal (row_filter8i.hpp has the quantiser, the margin and its proof) ----
+// Two planes of signed bytes, dim bytes each, h at qd and l at qd + dim (query level qh_i = 128 h_i + l_i), in the BYTE ORDER OF A SHADOW LINE:
+//        plane byte (L * 8 + r) * 16 + (l & 3) * 4 + t   =   digit of query element 8 * (4 * l + t) + r        l = f32 line, L = l >> 2
+// so lane r reads the 16 digits that face its 16 code bytes of shadow line L with ONE ds_read_b128 per plane, and a code dword meets its digit dword in
+// one v_dot4 per plane: no conversion, no f32 product.  The sums are exact integers, whatever the order.
+__device__ __forceinline__ int group8_hsum_i(int a) {   // group8_hsum's DPP steps on integers; every lane of the wave must be active
+  const int b = a + __builtin_amdgcn_mov_dpp(a, 0xB1, 0xf, 0xf, true);    // quad_perm [1,0,3,2]
+  const int c = b + __builtin_amdgcn_mov_dpp(b, 0x4E, 0xf, 0xf, true);    // quad_perm [2,3,0,1]
+  return c + __builtin_amdgcn_mov_dpp(c, 0x141, 0xf, 0xf, true);          // row_half_mirror: lane i <-> 7 - i
+}
+
+// The planes, the scale t and the error norm e_q of the query staged at qp (rows8 order).  One lane per plane dword: its four digits are one f32x4 of qp.
+// The caller orders LDS around the call (wave_sync before: qp is written; after: the planes are).  t_out = 0, e_q = +infinity: no certificate.
+__device__ __forceinline__ void query_digits8i(const float* __restrict__ qp, uint8_t* __restrict__ qd, int dim, int lane, float& t_out, float& eq_out) {
+  const int nw = dim >> 2;   // dwords per plane (dim % 256 == 0)
+  float mx = 0.f; bool bad = false;
+  for (int w = lane; w < nw; w += 64) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(qp + (size_t)w * 4);
+#pragma unroll
+    for (int s = 0; s < 4; s++) { const float a = __builtin_fabsf(v[s]); bad = bad || !(a <= 3.4028234663852886e38f); mx = a > mx ? a : mx; }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) { const float o = __shfl_xor(mx, m, 64); mx = o > mx ? o : mx; }
+  bad = __ballot(bad) != 0ull;
+  const float t = row_filter8i_scale(mx, bad);
+  double err = 0.0;
+  uint32_t* const ph = reinterpret_cast<uint32_t*>(qd); uint32_t* const pl = reinterpret_cast<uint32_t*>(qd + dim);
+  for (int w = lane; w < nw; w += 64) {
+    const int L = w >> 5, r = (w >> 2) & 7, j = w & 3;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(qp + (size_t)(((4 * L + j) * 8 + r) * 4));
+    uint32_t wh = 0, wl = 0;
+    if (t > 0.f) {
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        const int qh = row_filter8i_level(v[s], t);
+        int h, l;
+        row_filter8i_digits(qh, h, l);
+        const double d = (double)v[s] - (double)t * (double)qh;   // the product is exact in f64
+        err += d * d;
+        wh |= ((uint32_t)h & 0xffu) << (8 * s); wl |= ((uint32_t)l & 0xffu) << (8 * s);
+      }
+    }
+    ph[w] = wh; pl[w] = wl;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) err += __shfl_xor(err, m, 64);
+  t_out = t;
+  eq_out = t > 0.f ? row_filter8i_err(err) : __builtin_inff();
+}
+
+// group8_stream_b with integer sums: the same loads in the same order; s_h[i] / s_l[i] = sum h_j c_j / sum l_j c_j of neighbour i (exact; the caller forms
+// I = 128 H + L in 64 bits — at 2304-d saturated codes and digits put |128 H| beyond 2^31).  qd: the planes (query_digits8i).
+template <int U, int R, bool NT>
+__device__ __forceinline__ void group8_stream_bi(const uint8_t* __restrict__ rows_b, size_t bstride, const uint32_t* s_nb, int* s_h, int* s_l, uint32_t nf,
+                                                 int grp, int rj, const uint8_t* __restrict__ qd, int dim, int nlb) {
+  const u32x4e* const qh = reinterpret_cast<const u32x4e*>(qd + rj * 16);
+  const u32x4e* const ql = reinterpret_cast<const u32x4e*>(qd + dim + rj * 16);
+  const int nbur = nlb / U;
+  const uint32_t total = ((nf + (uint32_t)(8 * R - 1)) / (uint32_t)(8 * R)) * (uint32_t)nbur;
+  u32x4e A[R][U], B[R][U];
+  const uint8_t* rp[R];
+  auto row_of = [&](uint32_t pass, int i) -> const uint8_t* {
+    const uint32_t idx = (pass * (uint32_t)R + (uint32_t)i) * 8u + (uint32_t)grp;
+    return rows_b + (size_t)s_nb[idx < nf ? idx : 0u] * bstride + rj * 16;   // an idle group re-reads a live row
+  };
+#pragma unroll
+  for (int i = 0; i < R; i++) {
+    rp[i] = row_of(0, i);
+#pragma unroll
+    for (int u = 0; u < U; u++) A[i][u] = row_ld<NT>(reinterpret_cast<const u32x4e*>(rp[i] + (size_t)u * 128));
+  }
+  int ah[R], al[R];
+#pragma unroll
+  for (int i = 0; i < R; i++) { ah[i] = 0; al[i] = 0; }
+  uint32_t pass = 0; int b = 0;
+  // LOADNEXT is a literal, as in group8_stream: the step that has a successor issues its loads unconditionally
+#define COLTT_G8BI_STEP(CUR, NXT, LOADNEXT)                                                                                  \
+  {                                                                                                                         \
+    int nb_ = b + 1; uint32_t np_ = pass;                                                                                   \
+    if (nb_ == nbur) { nb_ = 0; np_ = pass + 1u; }                                                                          \
+    if (LOADNEXT) {                                                                                                         \
+      _Pragma("unroll") for (int i = 0; i < R; i++) {                                                                       \
+        if (nb_ == 0) rp[i] = row_of(np_, i);                                                                               \
+        _Pragma("unroll") for (int u = 0; u < U; u++) NXT[i][u] = row_ld<NT>(reinterpret_cast<const u32x4e*>(rp[i] + (size_t)(nb_ * U + u) * 128)); \
+      }                                                                                                                     \
+    }                                                                                                                       \
+    _Pragma("unroll") for (int u = 0; u < U; u++) {                                                                         \
+      const int L = b * U + u;                                                                                              \
+      const u32x4e h = qh[L * 8], l = ql[L * 8];                                                                            \
+      _Pragma("unroll") for (int j_ = 0; j_ < 4; j_++) {                                                                    \
+        _Pragma("unroll") for (int i = 0; i < R; i++) {                                                                     \
+          ah[i] = __builtin_amdgcn_sdot4((int)CUR[i][u][j_], (int)h[j_], ah[i], false);                                     \
+          al[i] = __builtin_amdgcn_sdot4((int)CUR[i][u][j_], (int)l[j_], al[i], false);                                     \
+        }                                                                                                                   \
+      }                                                                                                                     \
+    }                                                                                                                       \
+    if (b == nbur - 1) {   /* wave-uniform: every group is at the same burst of its rows */                                  \
+      _Pragma("unroll") for (int i = 0; i < R; i++) {                                                                       \
+        const int sh = group8_hsum_i(ah[i]), sl = group8_hsum_i(al[i]);                                                     \
+        const uint32_t idx = (pass * (uint32_t)R + (uint32_t)i) * 8u + (uint32_t)grp;                                       \
+        if (rj == 0 && idx < nf) { s_h[idx] = sh; s_l[idx] = sl; }                                                          \
+        ah[i] = 0; al[i] = 0;                                                                                               \
+      }                                                                                                                     \
+    }                                                                                                                       \
+    b = nb_; pass = np_;                                                                                                    \
+  }
+  uint32_t t = 0;
+  for (; t + 3u <= total; t += 2) {   // both steps have a successor
+    COLTT_G8BI_STEP(A, B, 1)
+    COLTT_G8BI_STEP(B, A, 1)
+  }
+  if (total - t == 2u) { COLTT_G8BI_STEP(A, B, 1) COLTT_G8BI_STEP(B, A, 0) }
+  else if (total - t == 1u) { COLTT_G8BI_STEP(A, B, 0) }
+#undef COLTT_G8BI_STEP
+}
+
+// group8_burst_b with integer sums: rows of exactly U shadow lines, the whole chunk in one burst.  Per line two ds_read_b128 (one per plane) and per code
+// dword two v_dot4, where the f32 sum reads four f32x4 of the query and issues four conversions and four fused multiply-adds.
+template <int U, bool NT>
+__device__ __forceinline__ void group8_burst_bi(const uint8_t* __restrict__ rows_b, size_t bstride, const uint32_t* s_nb, int* s_h, int* s_l, uint32_t nf,
+                                                int grp, int rj, const uint8_t* __restrict__ qd) {
+  constexpr int DIM = U * 128;
+  const u32x4e* const qh = reinterpret_cast<const u32x4e*>(qd + rj * 16);
+  const u32x4e* const ql = reinterpret_cast<const u32x4e*>(qd + DIM + rj * 16);
+  u32x4e A[4][U];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const uint32_t idx = (uint32_t)(i * 8 + grp);
+    const uint8_t* rp = rows_b + (size_t)s_nb[idx < nf ? idx : 0u] * bstride + rj * 16;
+#pragma unroll
+    for (int u = 0; u < U; u++) A[i][u] = row_ld<NT>(reinterpret_cast<const u32x4e*>(rp + (size_t)u * 128));
+  }
+  int ah[4] = {0, 0, 0, 0}, al[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    const u32x4e h = qh[u * 8], l = ql[u * 8];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        ah[i] = __builtin_amdgcn_sdot4((int)A[i][u][j], (int)h[j], ah[i], false);
+        al[i] = __builtin_amdgcn_sdot4((int)A[i][u][j], (int)l[j], al[i], false);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int sh = group8_hsum_i(ah[i]), sl = group8_hsum_i(al[i]);
+    const uint32_t idx = (uint32_t)(i * 8 + grp);
+    if (rj == 0 && idx < nf) { s_h[idx] = sh; s_l[idx] = sl; }
   }
 }
 

@@ -268,14 +268,23 @@ class Hnsw:
         L.check(L.lib().coltt_hnsw_fetch_shadow8(self.h, C.c_uint64(first), C.c_uint64(n), L.vp(codes), L.vp(meta), L.vp(adj)))
         return codes, meta, adj
 
-    def RowFilterProbe(self, queries, slots, lower_bound, bits=8, nt=0, full_at_pop=1):
+    def RowFilterProbe(self, queries, slots, lower_bound, bits=8, nt=0, full_at_pop=1, sums=False):
         """the level-0 walk's chunk evaluation on chosen pairs (coltt_hnsw_row_filter_probe): slots [nq, 32] uint32 (L.NBR_NONE = not fresh),
-        lower_bound a scalar or [nq].  Returns (r [nq, 32], qnorm [nq], rnorm [nq, 32], counts [nq, 3] = rejected, f32 rows, shadow rows)."""
+        lower_bound a scalar or [nq].  bits: 8, 16 or "8i" (the 8-bit shadow against the quantised query, row_filter8i.hpp).
+        Returns (r [nq, 32], qnorm [nq], rnorm [nq, 32], counts [nq, 3] = rejected, f32 rows, shadow rows); with sums=True ("8i" only) also
+        (isum [nq, 32] int64: the integer sums phase A formed, qte [nq, 2]: the queries' (scale, error norm))."""
         q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.dim)
         nq = q.shape[0]
         s = np.ascontiguousarray(slots, np.uint32).reshape(nq, 32)
         lb = np.ascontiguousarray(np.broadcast_to(np.asarray(lower_bound, np.float32), (nq,)))
         r = np.zeros((nq, 32), np.float32); qn = np.zeros(nq, np.float32); rn = np.zeros((nq, 32), np.float32); cnt = np.zeros((nq, 3), np.uint32)
+        if bits in ("8i", 80):
+            isum = np.zeros((nq, 32), np.int64); qte = np.zeros((nq, 2), np.float32)
+            L.check(L.lib().coltt_hnsw_row_filter_probe_ex(self.h, L.vp(q), C.c_size_t(nq), L.vp(s), L.vp(lb), C.c_int(80), C.c_int(int(nt)),
+                                                           C.c_int(int(full_at_pop)), L.vp(r), L.vp(qn), L.vp(rn), L.vp(cnt), L.vp(isum), L.vp(qte)))
+            return (r, qn, rn, cnt, isum, qte) if sums else (r, qn, rn, cnt)
+        if sums:
+            raise ValueError("RowFilterProbe: only the \"8i\" kind forms integer sums")
         L.check(L.lib().coltt_hnsw_row_filter_probe(self.h, L.vp(q), C.c_size_t(nq), L.vp(s), L.vp(lb), C.c_int(int(bits)), C.c_int(int(nt)),
                                                     C.c_int(int(full_at_pop)), L.vp(r), L.vp(qn), L.vp(rn), L.vp(cnt)))
         return r, qn, rn, cnt

@@ -317,8 +317,9 @@ int coltt_hnsw_rows8_searches(coltt_handle_t h, uint64_t* out_launches, int32_t*
  * Two kinds of shadow exist.  The 8-BIT one (the default): one signed code byte per element (dim bytes per slot) with a scale and the exact norm of
  * what the codes miss per slot, the pair repeated per level-0 edge beside the neighbours' norms (8 bytes per slot + 8 bytes per edge); the bound charges
  * that stored error norm (coltt_amd/csrc/row_filter8.hpp).  The BINARY16 one: dim * 2 bytes per slot (row_filter.hpp).
- * COLTT_ROW_SHADOW_BITS = 8 / 16 / both (at create; default 8) says which an index keeps; COLTT_ROW_FILTER_BITS = 8 / 16 (per call) which a filtered launch
- * reads — unset: 8 where the index keeps it, else 16; the kind an index does not keep is served by the one it does.  *out_has_shadow is non-zero when any
+ * COLTT_ROW_SHADOW_BITS = 8 / 16 / both (at create; default 8) says which an index keeps; COLTT_ROW_FILTER_BITS = 8 / 16 / 8i (per call) which a filtered
+ * launch reads — 8i: the 8-bit shadow against the query quantised once per traversal, phase A an exact integer sum (row_filter8i.hpp); unset: 8i where the
+ * index keeps the 8-bit shadow, else 16; the kind an index does not keep is served by the one it does.  *out_has_shadow is non-zero when any
  * shadow is kept: 8, 16 or 24 (both).  The shadow-row counter counts rows of whichever kind the launches read. */
 int coltt_hnsw_row_filter_stats(coltt_handle_t h, uint64_t* out_rejected, uint64_t* out_f32_rows, uint64_t* out_shadow_rows, uint64_t* out_launches, int32_t* out_has_shadow);
 /* Read-back of the 8-bit shadow for tests and tools: the codes of slots [first_slot, first_slot + n) in natural element order ([n][dim]), their
@@ -334,6 +335,11 @@ int coltt_hnsw_fetch_shadow8(coltt_handle_t h, uint64_t first_slot, uint64_t n, 
  * exact), -3e38 rejects every certified pair (every bound).  COLTT_E_UNSUPPORTED when the index does not keep the shadow asked for. */
 int coltt_hnsw_row_filter_probe(coltt_handle_t h, const float* queries, size_t nq, const uint32_t* slots, const float* lower_bound, int bits, int nt,
                                 int full_at_pop, float* out_r, float* out_qnorm, float* out_rnorm, uint32_t* out_counts);
+/* The same probe; bits may also be 80: the 8-bit shadow against the quantised query ("8i").  For that kind out_isum [nq][32] receives the integer sum
+ * sum qh_i c_i phase A formed for every fresh position of a full_at_pop call (0 elsewhere) and out_qte [nq][2] the query's (scale t, error norm e_q);
+ * both may be NULL and are left untouched by the other kinds. */
+int coltt_hnsw_row_filter_probe_ex(coltt_handle_t h, const float* queries, size_t nq, const uint32_t* slots, const float* lower_bound, int bits, int nt,
+                                   int full_at_pop, float* out_r, float* out_qnorm, float* out_rnorm, uint32_t* out_counts, int64_t* out_isum, float* out_qte);
 /* graph export in the bulk_load layout (what Hnsw.Commit serialises, hnsw_commit.go:69-162).
  * Call with NULL arrays to get sizes.  With any array non-NULL, *n_slots / *n_rows / *n_edges are IN-OUT: on entry the
  * capacities of the caller's arrays (slots: ids, levels, deleted; rows + 1: row_offsets; edges: nbr, nbr_dist) — normally the

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""A/B of the certified level-0 row filter on ONE index in ONE process, three sides: filter off, over the binary16 shadow (row_filter.hpp), over the 8-bit
-shadow (row_filter8.hpp).  The index is created with COLTT_ROW_SHADOW_BITS=both; per call COLTT_ROW_FILTER=0 / 1 and COLTT_ROW_FILTER_BITS=16 / 8 pick the
-side, calls alternating.  `python tools/row_filter_ab.py [n] [ef,ef,...] [rounds]` builds n x 768 f32 cosine with the batched builder (ROW_FILTER_AB_DIM for
+"""A/B of the certified level-0 row filter on ONE index in ONE process, four sides: filter off, over the binary16 shadow (row_filter.hpp), over the 8-bit
+shadow with the f32 query (row_filter8.hpp) and with the quantised query (row_filter8i.hpp: integer phase A).  The index is created with
+COLTT_ROW_SHADOW_BITS=both; per call COLTT_ROW_FILTER=0 / 1 and COLTT_ROW_FILTER_BITS=16 / 8 / 8i pick the side, calls alternating.  `python tools/row_filter_ab.py [n] [ef,ef,...] [rounds]` builds n x 768 f32 cosine with the batched builder (ROW_FILTER_AB_DIM for
 another dim), then per ef runs 10 000 queries `rounds` times per side (kernel time from the hipEvent pair on the search stream; the first round of each
 side is a warm-up), checks np.array_equal on ids, score bits, counts and the three traversal counters across the sides, and prints one JSON line: per side
 ms per launch (all values and the median), shadow rows / survivors / f32 rows per query, and the bytes the side REQUESTS per query
@@ -18,7 +18,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-SIDES = (("off", "0", None), ("16", "1", "16"), ("8", "1", "8"))
+SIDES = (("off", "0", None), ("16", "1", "16"), ("8", "1", "8"), ("8i", "1", "8i"))
 
 
 def main():
@@ -41,7 +41,7 @@ def main():
     out = B.Out(torch, dev, nq, k)
     st0 = h.RowFilterStats()
     res = {"n": n, "dim": dim, "build_s": build_s, "shadow": st0["shadow"], "shadow_bits": list(st0["shadow_bits"]), "ef": {}}
-    assert tuple(st0["shadow_bits"]) == (8, 16), "the three-sided A/B needs an index that keeps both shadows"
+    assert tuple(st0["shadow_bits"]) == (8, 16), "the four-sided A/B needs an index that keeps both shadows"
     for ef in efs:
         ms = {s[0]: [] for s in SIDES}; keep = {}; flt = {}
         for r in range(rounds):
@@ -66,7 +66,7 @@ def main():
         os.environ.pop("COLTT_ROW_FILTER", None); os.environ.pop("COLTT_ROW_FILTER_BITS", None)
         a = keep["off"]
         same = all(bool(np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)) and a[3] == b[3]
-                        and (a[2] is None or np.array_equal(a[2], b[2]))) for b in (keep["16"], keep["8"]))
+                        and (a[2] is None or np.array_equal(a[2], b[2]))) for b in (keep["16"], keep["8"], keep["8i"]))
         nd, ne = a[3]["n_dist"] / nq, a[3]["n_exp"] / nq
         row = {"identical": same, "per_query": {"n_dist": nd, "n_exp": ne}}
         for name, on, bits_ in SIDES:
@@ -79,10 +79,12 @@ def main():
                          "shadow_rows": sh, "rejected": rej, "survivors_reading_both": sh - rej, "f32_rows_level0": f32, "f32_rows_while_filling": f32 - (sh - rej),
                          "f32_fraction_of_level0": f32 / max(rej + f32, 1e-9) if name != "off" else 1.0,
                          "bytes_requested_per_query": moved, "frac_of_hbm_peak_requested": moved * nq / t / 8e12, "filter_counters_of_last_call": flt[name]}
-        for name in ("16", "8"):
+        for name in ("16", "8", "8i"):
             row[name]["speedup_over_off"] = row["off"]["ms_per_launch"] / row[name]["ms_per_launch"]
             row[name]["bytes_ratio_to_off"] = row[name]["bytes_requested_per_query"] / row["off"]["bytes_requested_per_query"]
         row["speedup_8_over_16"] = row["16"]["ms_per_launch"] / row["8"]["ms_per_launch"]
+        row["speedup_8i_over_8"] = row["8"]["ms_per_launch"] / row["8i"]["ms_per_launch"]
+        row["shadow_rows_equal_8_8i"] = flt["8"]["shadow_rows"] == flt["8i"]["shadow_rows"]
         res["ef"][str(ef)] = row
         print(json.dumps({str(ef): row}), file=sys.stderr, flush=True)
         assert same, "the sides disagree"
