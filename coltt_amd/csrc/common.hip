@@ -88,6 +88,7 @@ Policy read_policy_from_env() {
   v = num("COLTT_ROWS_NT_MIN_MB", set); p.rows_nt_min_mb = set ? std::max<long long>(0, v) : 12288;
   v = num("COLTT_PQ_WAVES", set); p.pq_waves = set ? (int)std::max<long long>(1, std::min<long long>(16, v)) : 0;
   p.pq_nbr = !off("COLTT_PQ_NBR");
+  p.pq_nbr_patch = !off("COLTT_PQ_NBR_PATCH");
   { const char* e = getenv("COLTT_LAT_SEQ"); p.lat_seq = e && *e == '1'; }
   v = num("COLTT_LAT_HELPERS", set); p.lat_helpers = set ? (int)std::max<long long>(0, std::min<long long>(3, v)) : 0;
   v = num("COLTT_LAT_MAX_NQ", set); if (!set) v = num("COLTT_MW_MAX_NQ", set);

@@ -117,6 +117,7 @@ struct Policy {
   long long rows_nt_min_mb = 12288;  // COLTT_ROWS_NT_MIN_MB: ... row arrays of at least this many MiB (see exact.hpp: row_ld; measured crossover: profiles/r06ag_nt_rows_ab.md)
   int pq_waves = 0;            // COLTT_PQ_WAVES: resident traversals per CU of the product-quantised walk, 0 = the default cap
   bool pq_nbr = true;          // COLTT_PQ_NBR=0: the product-quantised walk gathers its code rows by neighbour slot (round 5) instead of reading the neighbourhood blocks
+  bool pq_nbr_patch = true;    // COLTT_PQ_NBR_PATCH=0: Insert / Remove mark the neighbourhood blocks stale (the next product-quantised walk rebuilds all of them) instead of re-gathering the blocks of the rows they rewrote
   bool lat_seq = false;        // COLTT_LAT_SEQ=1
   int lat_helpers = 0;         // COLTT_LAT_HELPERS: cache-warming helper workgroups per walking workgroup of the latency kernel (batches <= 8 queries); 0 = none (default: measured 3-5 % SLOWER, profiles/r06f_latency_helpers_ab.md)
   bool lat_knob_set = false;   // COLTT_LAT_MAX_NQ / COLTT_MW_MAX_NQ present

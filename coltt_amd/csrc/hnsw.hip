@@ -178,8 +178,9 @@ __global__ __launch_bounds__(64) void hnsw_build_search_kernel(GraphView g, int3
 // the `width` nearest by (stored distance, slot) are kept (selectNeighbors, :391-397).  Rows stay sorted by slot.
 constexpr int LINK_W = 64;    // widest row the builder supports
 constexpr int LINK_CH = 64;   // requests merged per round
+// dirty (may be NULL): the owner of a LEVEL-0 row appends its slot — the rows whose neighbourhood blocks the host re-gathers afterwards (PqNbrPatch).
 __global__ void hnsw_link_kernel(GraphView g, uint64_t cap_slots, const BuildReq* __restrict__ req, uint32_t n_req,
-                                 uint32_t* __restrict__ head) {
+                                 uint32_t* __restrict__ head, uint32_t* __restrict__ dirty, uint32_t dirty_cap) {
   uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_req) return;
   if (req[r].next != NBR_NONE) return;
@@ -223,6 +224,7 @@ __global__ void hnsw_link_kernel(GraphView g, uint64_t cap_slots, const BuildReq
     float2* mrow = g.adj0_m + (size_t)rid * g.mMax0;
     for (uint32_t i = 0; i < W; i++) mrow[i] = i < n ? g.rows_m[s[i]] : float2{0.f, 0.f};
   }
+  if (lvl0 && dirty) { const uint32_t di = atomicAdd(&dirty[0], 1u); if (di < dirty_cap) dirty[2 + di] = rid; }
 }
 
 // Phase B of the diverse mode (algo 2 — NOT reference behaviour; definition: the oracle's select_diverse + the batch rule of
@@ -235,7 +237,7 @@ constexpr uint32_t LINKD_CAND = 1024;   // candidates per row (existing + the ba
 template <int METRIC, int QUANT, bool R8>
 __global__ __launch_bounds__(64) void hnsw_link_diverse_kernel(GraphView g, uint64_t cap_slots, const BuildReq* __restrict__ req, uint32_t n_req,
                                                               uint32_t* __restrict__ head, uint32_t keep_pruned,
-                                                              unsigned long long* __restrict__ stats) {
+                                                              unsigned long long* __restrict__ stats, uint32_t* __restrict__ dirty, uint32_t dirty_cap) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const uint32_t r = blockIdx.x;
   if (r >= n_req) return;
@@ -364,6 +366,7 @@ __global__ __launch_bounds__(64) void hnsw_link_diverse_kernel(GraphView g, uint
     if (nrow) nrow[lane] = 0.f;
     if (mrow) mrow[lane] = float2{0.f, 0.f};
   }
+  if (lvl0 && dirty && lane == 0) { const uint32_t di = atomicAdd(&dirty[0], 1u); if (di < dirty_cap) dirty[2 + di] = rid; }   // as hnsw_link_kernel
 }
 
 // Before the diverse link pass: the longest request chain of the batch (+ the widest row) -> stats[5].  A row that would receive more candidates than the link
@@ -460,9 +463,15 @@ struct Hnsw : Object {
   bool pq_on = false; PqShape pq_shape; uint32_t pq_row = 0 /* bytes per code row: m rounded up to 16 */; uint64_t pq_done = 0;
   DevBuf pq_cb, pq_codes, pq_stage;
   // Neighbourhood blocks of the product-quantised walk (hnsw_pq.hpp: AdcEval<.., NBR>): pq_nbr[slot][p][pq_row] = pq_codes[adj0[slot][p]] (zeros for an
-  // empty position) — derived from the level-0 rows and the codes, rebuilt LAZILY by the first product-quantised search after a mutation (writers only
-  // raise pq_nbr_stale under their exclusive lock; searches hold the lock shared and settle the rebuild among themselves under pq_nbr_mu).
+  // empty position) — derived from the level-0 rows and the codes.  Built whole by the first product-quantised search that finds them stale (searches hold
+  // the lock shared and settle the build among themselves under pq_nbr_mu), then MAINTAINED by the writers like adj0_n: Insert / InsertBatchDevice / Remove
+  // raise pq_nbr_stale before their first device write and, if the blocks were current, re-gather the blocks of exactly the level-0 rows they rewrote
+  // (PqNbrPatch below) and lower it again before they release the exclusive lock — a call that does not reach its end leaves them stale.  Load / BulkLoad /
+  // PqAttach (everything renumbered or re-coded) and a grown slot capacity leave them stale: the next walk that reads them rebuilds.
   DevBuf pq_nbr; bool pq_nbr_ok = false; std::atomic<bool> pq_nbr_stale{true}; std::mutex pq_nbr_mu;
+  bool pq_nbr_built = false;   // pq_nbr has held a whole build (a stale array is then state 2, not 0)
+  DevBuf pq_dirty;             // [0] = level-0 rows the link kernels of the mutation in flight rewrote, [2 ..] their slots (PqNbrPatch)
+  std::atomic<uint64_t> pq_nbr_builds{0}, pq_nbr_patches{0}, pq_nbr_patched_rows{0};
   bool dense = true; uint64_t dense_base = 0;
   std::unordered_map<uint64_t, uint32_t> id2slot;
   std::vector<uint64_t> h_ids;       // !dense
@@ -1171,8 +1180,73 @@ int ensure_pq_nbr(Hnsw* x, hipStream_t stream, bool* use) {
   }
   COLTT_HIP(hipGetLastError());
   COLTT_HIP(hipStreamSynchronize(stream));
-  x->pq_nbr_ok = true; x->pq_nbr_stale.store(false);
+  x->pq_nbr_ok = true; x->pq_nbr_built = true; x->pq_nbr_stale.store(false);
+  x->pq_nbr_builds.fetch_add(1);
   *use = true;
+  return COLTT_OK;
+}
+// ---- the writers' side of the neighbourhood blocks: re-gather the blocks of the level-0 rows a mutation rewrote -------------------------------------
+// the blocks of the listed slots, as pq_nbr_build_kernel writes them: one thread per 16-byte piece of nbr[slots[i]][p][row_bytes].  count (may be NULL: all
+// `cap` entries) = the device counter the link kernels appended under; a slot or a neighbour outside [0, n_slots) is skipped (never the case).
+__global__ void pq_nbr_patch_kernel(const uint32_t* __restrict__ adj0, const uint8_t* __restrict__ codes, uint8_t* __restrict__ nbr, const uint32_t* __restrict__ slots,
+                                    const uint32_t* __restrict__ count, uint32_t cap, uint32_t W, uint32_t row_bytes, uint32_t n_slots) {
+  const uint32_t pieces = row_bytes >> 4, per = W * pieces;
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t i = t / per;
+  uint32_t n = cap;
+  if (count) { const uint32_t c = *count; n = c < cap ? c : cap; }
+  if (i >= n) return;
+  const uint32_t slot = slots[i];
+  if (slot >= n_slots) return;
+  const uint32_t r = (uint32_t)(t - i * per);
+  const uint32_t p = r / pieces, pc = r - p * pieces;
+  const uint64_t e = (uint64_t)slot * W + p;
+  const uint32_t nb = adj0[e];
+  u32x4v v = {0u, 0u, 0u, 0u};
+  if (nb < n_slots) v = *reinterpret_cast<const u32x4v*>(codes + (size_t)nb * row_bytes + (size_t)pc * 16);   // (NBR_NONE is not below n_slots)
+  *reinterpret_cast<u32x4v*>(nbr + e * row_bytes + (size_t)pc * 16) = v;
+}
+// One mutation's bookkeeping.  begin: called under the exclusive lock once the call can no longer be refused and before its first device write — the blocks are
+// stale from here on; if they were current (and the knobs allow) the call tracks: d_dirty is the list its link kernels append to.  end: called when every
+// kernel of the mutation has been launched and the new slots' codes are written (sync_pq) — re-gathers the blocks of the new slots [first_new, first_new +
+// n_new), of the listed rows (the link kernels' list, or d_slots[n_slots_listed] the host put together: Remove) and only then calls the blocks current again.
+// A call that returns early never reaches end: the blocks stay stale and the next walk rebuilds them.
+constexpr uint64_t PQ_PATCH_MAX_LIST = 1ull << 20;   // entries (4 MiB): a call that could rewrite more rows than this leaves the blocks to the whole rebuild
+struct PqNbrPatch { bool on = false; uint32_t* d_dirty = nullptr; uint32_t cap = 0; };
+PqNbrPatch pq_nbr_patch_begin(Hnsw* x, uint64_t max_listed) {
+  PqNbrPatch t;
+  const bool current = !x->pq_nbr_stale.load() && x->pq_nbr_ok;
+  x->pq_nbr_stale.store(true);
+  if (!current || !x->pq_on || max_listed > PQ_PATCH_MAX_LIST) return t;   // an index that keeps no blocks pays this line and nothing else
+  const Policy pol = policy();
+  if (!pol.pq_nbr || !pol.pq_nbr_patch) return t;
+  if (max_listed) {
+    if (x->pq_dirty.reserve((2 + max_listed) * 4) != COLTT_OK) { (void)hipGetLastError(); return t; }
+    if (hipMemsetAsync(x->pq_dirty.p, 0, 8, x->stream) != hipSuccess) { (void)hipGetLastError(); return t; }
+    t.d_dirty = x->pq_dirty.as<uint32_t>(); t.cap = (uint32_t)max_listed;
+  }
+  t.on = true;
+  return t;
+}
+int pq_nbr_patch_end(Hnsw* x, const PqNbrPatch& t, uint64_t first_new, uint64_t n_new, const uint32_t* d_slots, uint32_t n_slots_listed) {
+  if (!t.on) return COLTT_OK;
+  const uint32_t W = (uint32_t)x->cfg.m_max0, pieces = x->pq_row >> 4;
+  if (x->pq_nbr.cap < (size_t)std::max<uint64_t>(x->cap, x->n) * W * x->pq_row || x->pq_done < x->n) return COLTT_OK;   // the slot capacity grew past the array: stale, rebuilt whole
+  const uint32_t* adj0 = x->adj0.as<uint32_t>(); const uint8_t* codes = x->pq_codes.as<uint8_t>(); uint8_t* nbr = x->pq_nbr.as<uint8_t>();
+  if (n_new) {   // a run of consecutive slots: the whole build's kernel over that run
+    const uint64_t total = n_new * W * pieces, e0 = first_new * W;
+    pq_nbr_build_kernel<<<(unsigned)ceil_div(total, 256), 256, 0, x->stream>>>(adj0 + e0, codes, nbr + e0 * x->pq_row, total, x->pq_row);
+  }
+  const uint32_t* list = t.d_dirty ? t.d_dirty + 2 : d_slots;
+  const uint32_t lcap = t.d_dirty ? t.cap : n_slots_listed;
+  if (lcap) pq_nbr_patch_kernel<<<(unsigned)ceil_div((uint64_t)lcap * W * pieces, 256), 256, 0, x->stream>>>(adj0, codes, nbr, list, t.d_dirty, lcap, W, x->pq_row, (uint32_t)x->n);
+  COLTT_HIP(hipGetLastError());
+  uint32_t listed = n_slots_listed;
+  if (t.d_dirty) COLTT_HIP(hipMemcpyAsync(&listed, t.d_dirty, 4, hipMemcpyDeviceToHost, x->stream));
+  COLTT_HIP(hipStreamSynchronize(x->stream));
+  if (listed > lcap) return COLTT_OK;   // (the list is sized by the request bound: not reached) rows were dropped — stale
+  x->pq_nbr_patches.fetch_add(1); x->pq_nbr_patched_rows.fetch_add(n_new + listed);
+  x->pq_nbr_stale.store(false);
   return COLTT_OK;
 }
 // log2 of a table row in LDS: the centroid count rounded up to a power of two, at least 16 (codes >= C never occur)
@@ -1431,12 +1505,12 @@ int launch_build(Hnsw* x, const SearchGeom& sg, uint32_t base, uint32_t count, c
 }
 
 template <int METRIC, int QUANT>
-int launch_link_diverse(Hnsw* x, const BuildReq* req, uint32_t n_req, uint32_t* head, unsigned long long* stats) {
+int launch_link_diverse(Hnsw* x, const BuildReq* req, uint32_t n_req, uint32_t* head, unsigned long long* stats, uint32_t* dirty, uint32_t dirty_cap) {
   auto kern = hnsw_link_diverse_kernel<METRIC, QUANT, false>;
   if constexpr (QUANT != Q_F8) { if (x->r8) kern = hnsw_link_diverse_kernel<METRIC, QUANT, true>; }
   const size_t lds = (((size_t)x->dim * 4 + 15) & ~(size_t)15) + (size_t)(2 * LINKD_CAND + 128) * 8;
   COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kern<<<n_req, 64, lds, x->stream>>>(x->view(), x->cap, req, n_req, head, (uint32_t)(x->cfg.keep_pruned ? 1 : 0), stats);
+  kern<<<n_req, 64, lds, x->stream>>>(x->view(), x->cap, req, n_req, head, (uint32_t)(x->cfg.keep_pruned ? 1 : 0), stats, dirty, dirty_cap);
   COLTT_HIP(hipGetLastError());
   return COLTT_OK;
 }
@@ -1460,6 +1534,10 @@ int insert_core(Hnsw* x, const uint64_t* ids, uint64_t first_id, const float* d_
       if (x->id2slot.count(id) || !seen.emplace(id, 1).second) return fail(COLTT_E_EXISTS, "Item already exists");
     }
   }
+  // The neighbourhood blocks are stale from here on; a call that found them current lists the level-0 rows its link kernels rewrite (every new vertex queues at
+  // most cfg.m level-0 requests, and a listed row is owned by one of them) and re-gathers their blocks at its end.
+  const uint64_t first_new = x->n;
+  const PqNbrPatch patch = pq_nbr_patch_begin(x, (uint64_t)n * (uint64_t)x->cfg.m);
   const uint32_t efc = (uint32_t)x->cfg.ef_construction;
   COLTT_TRY(x->w_misc.reserve(64));
   uint32_t* counter = x->w_misc.as<uint32_t>();
@@ -1560,7 +1638,7 @@ int insert_core(Hnsw* x, const uint64_t* ids, uint64_t first_id, const float* d_
         shrink = std::max(1u, b / 2);
         continue;
       }
-#define COLTT_LD_ARGS x, x->b_req.as<BuildReq>(), hm.n_req, x->b_head.as<uint32_t>(), d_stats
+#define COLTT_LD_ARGS x, x->b_req.as<BuildReq>(), hm.n_req, x->b_head.as<uint32_t>(), d_stats, patch.d_dirty, patch.cap
 #define COLTT_LD(Q) rc = x->metric == COLTT_COSINE ? launch_link_diverse<M_COS, Q>(COLTT_LD_ARGS) : launch_link_diverse<M_L2, Q>(COLTT_LD_ARGS)
       COLTT_DISPATCH_QUANT(x->quant, COLTT_LD)
 #undef COLTT_LD
@@ -1575,7 +1653,7 @@ int insert_core(Hnsw* x, const uint64_t* ids, uint64_t first_id, const float* d_
       }
       shrink = 0;
     } else if (hm.n_req) {
-      hnsw_link_kernel<<<ceil_div(hm.n_req, 64), 64, 0, x->stream>>>(x->view(), x->cap, x->b_req.as<BuildReq>(), hm.n_req, x->b_head.as<uint32_t>());
+      hnsw_link_kernel<<<ceil_div(hm.n_req, 64), 64, 0, x->stream>>>(x->view(), x->cap, x->b_req.as<BuildReq>(), hm.n_req, x->b_head.as<uint32_t>(), patch.d_dirty, patch.cap);
       COLTT_HIP(hipGetLastError());
     }
     commit_host();
@@ -1585,7 +1663,8 @@ int insert_core(Hnsw* x, const uint64_t* ids, uint64_t first_id, const float* d_
     x->n += b; x->live += b; x->n_upper += up; i += b;
   }
   COLTT_HIP(hipStreamSynchronize(x->stream));
-  return sync_pq(x);
+  COLTT_TRY(sync_pq(x));   // the new slots' codes: the blocks below gather them
+  return pq_nbr_patch_end(x, patch, first_new, x->n - first_new, nullptr, 0);
 }
 
 // the derived neighbour-norm rows of every slot (bulk installs; Insert / Remove maintain them incrementally in their kernels)
@@ -2041,7 +2120,6 @@ int coltt_hnsw_insert(coltt_handle_t h, uint64_t id, const float* vec, int32_t l
   if (!vec) return fail(COLTT_E_INVALID, "hnsw_insert: NULL vector");
   WriteLock g(x->rw);
   COLTT_DEVICE(x->device);
-  x->pq_nbr_stale.store(true);
   COLTT_TRY(x->w_raw.reserve((size_t)x->dim * 4));
   COLTT_HIP(hipMemcpyAsync(x->w_raw.p, vec, (size_t)x->dim * 4, hipMemcpyHostToDevice, x->stream));
   return insert_core(x.get(), &id, 0, x->w_raw.as<float>(), &level, 1, 1);
@@ -2054,7 +2132,6 @@ int coltt_hnsw_insert_batch_device(coltt_handle_t h, const uint64_t* ids, uint64
   if (n && (!d_vecs || !levels)) return fail(COLTT_E_INVALID, "hnsw_insert_batch_device: NULL input");
   WriteLock g(x->rw);
   COLTT_DEVICE(x->device);
-  x->pq_nbr_stale.store(true);
   return insert_core(x.get(), ids, first_id, d_vecs, levels, n, batch);
 }
 
@@ -2063,7 +2140,6 @@ int coltt_hnsw_remove(coltt_handle_t h, uint64_t id) {
   if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_remove: unknown handle");
   WriteLock g(x->rw);
   COLTT_DEVICE(x->device);
-  x->pq_nbr_stale.store(true);   // the neighbours' level-0 rows are about to be re-pruned
   uint32_t vi;
   if (x->dense) {
     if (id < x->dense_base || id >= x->dense_base + x->n) return fail(COLTT_E_NOT_FOUND, "Item not found");
@@ -2075,6 +2151,7 @@ int coltt_hnsw_remove(coltt_handle_t h, uint64_t id) {
     vi = it->second;
     x->id2slot.erase(it);
   }
+  const PqNbrPatch patch = pq_nbr_patch_begin(x.get(), 0);   // the neighbours' level-0 rows are about to be re-pruned: stale until their blocks are re-gathered below
   // removeVertex: delete from the map, set the deleted flag (hnsw.go:304-318)
   x->h_del[vi >> 5] |= 1u << (vi & 31);
   x->any_deleted = true; x->live--;
@@ -2118,7 +2195,10 @@ int coltt_hnsw_remove(coltt_handle_t h, uint64_t id) {
     COLTT_HIP(hipGetLastError());
   }
   COLTT_HIP(hipStreamSynchronize(x->stream));
-  return COLTT_OK;
+  // the rows the kernel compacted at level 0 are the removed vertex's level-0 neighbours: the tail of t_nb (levels descend), already on the device
+  uint32_t n_l0 = 0;
+  while (n_l0 < t_lv.size() && t_lv[t_lv.size() - 1 - n_l0] == 0) n_l0++;
+  return pq_nbr_patch_end(x.get(), patch, 0, 0, n_l0 ? x->b_req.as<uint32_t>() + (t_nb.size() - n_l0) : nullptr, n_l0);
 }
 
 int coltt_hnsw_export(coltt_handle_t h, uint64_t* n_slots, uint64_t* n_rows, uint64_t* n_edges, uint64_t* ids,
@@ -2320,6 +2400,43 @@ int coltt_hnsw_pq_fetch_codes(coltt_handle_t h, uint64_t first_slot, uint64_t n,
   if (n == 0) return COLTT_OK;
   if (!out_codes) return fail(COLTT_E_INVALID, "hnsw_pq_fetch_codes: NULL out");
   COLTT_HIP(hipMemcpy2D(out_codes, x->pq_shape.m, x->pq_codes.as<uint8_t>() + first_slot * x->pq_row, x->pq_row, x->pq_shape.m, n, hipMemcpyDeviceToHost));
+  return COLTT_OK;
+}
+
+namespace {
+// 0 = none (no quantiser, COLTT_PQ_NBR=0, never built, not affordable), 1 = current, 2 = built once and stale.  Caller holds pq_nbr_mu.
+int pq_nbr_state(const Hnsw* x) {
+  if (!policy().pq_nbr || !x->pq_on) return 0;
+  if (x->pq_nbr_stale.load()) return x->pq_nbr_built ? 2 : 0;
+  return x->pq_nbr_ok ? 1 : 0;
+}
+}  // namespace
+
+int coltt_hnsw_pq_nbr_stats(coltt_handle_t h, uint64_t* out_builds, uint64_t* out_patches, uint64_t* out_patched_rows, int32_t* out_state) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_pq_nbr_stats: unknown handle");
+  ReadLock g(x->rw);
+  std::lock_guard<std::mutex> gn(x->pq_nbr_mu);
+  if (out_builds) *out_builds = x->pq_nbr_builds.load();
+  if (out_patches) *out_patches = x->pq_nbr_patches.load();
+  if (out_patched_rows) *out_patched_rows = x->pq_nbr_patched_rows.load();
+  if (out_state) *out_state = pq_nbr_state(x.get());
+  return COLTT_OK;
+}
+
+int coltt_hnsw_pq_fetch_nbr(coltt_handle_t h, uint64_t first_slot, uint64_t n, uint8_t* out_blocks) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_pq_fetch_nbr: unknown handle");
+  ReadLock g(x->rw);
+  COLTT_DEVICE(x->device);
+  std::lock_guard<std::mutex> gn(x->pq_nbr_mu);   // (a search that finds the blocks stale rebuilds them under this)
+  const int st = pq_nbr_state(x.get());
+  if (st != 1) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_fetch_nbr: the neighbourhood blocks are %s", st == 2 ? "stale (the next product-quantised walk above ef 128 rebuilds them)" : "not kept");
+  if (first_slot > x->n || n > x->n - first_slot) return fail(COLTT_E_INVALID, "hnsw_pq_fetch_nbr: slots [%llu,%llu) outside [0,%llu)", (unsigned long long)first_slot, (unsigned long long)(first_slot + n), (unsigned long long)x->n);
+  if (n == 0) return COLTT_OK;
+  if (!out_blocks) return fail(COLTT_E_INVALID, "hnsw_pq_fetch_nbr: NULL out");
+  const size_t blk = (size_t)x->cfg.m_max0 * x->pq_row;
+  COLTT_HIP(hipMemcpy(out_blocks, x->pq_nbr.as<uint8_t>() + first_slot * blk, n * blk, hipMemcpyDeviceToHost));
   return COLTT_OK;
 }
 

@@ -45,7 +45,7 @@ namespace dev {
 // they are requested TOGETHER with the candidate's adjacency row at the end of the previous expansion (search_level2: ROWPF), one contiguous
 // mMax0 x row_bytes block (2 KiB for 32 x 64) instead of 32 gathers of 64 bytes (each a whole 128-byte line of HBM traffic) behind the adjacency row's
 // own round trip; the table sums of ALL listed neighbours then run under the visited probe's round trip (EARLY) instead of behind it.  One dependent
-// round trip per expansion (the probe) instead of three.  Derived data like adj0_n (hnsw.hip: sync_pq_nbr); the upper levels gather from `codes`.
+// round trip per expansion (the probe) instead of three.  Derived data maintained like adj0_n (hnsw.hip: ensure_pq_nbr builds them whole, pq_nbr_patch_end re-gathers what a writer rewrote); the upper levels gather from `codes`.
 // Round 6 — BOTH lanes of a pair work: the even lane owns the row's first PH = ceil(P / 2) pieces (table rows j < JS = 16 PH), the odd lane the rest; each sums its
 // half in j order from +0.0 and the pair adds the two partial sums (one DPP swap + one add: the definition above).  Half the issue slots per expansion for the
 // table sums, half the row registers.  So that ONE instruction stream serves both lanes, the table sits in LDS PAIR-INTERLEAVED — row j of the table at LDS row

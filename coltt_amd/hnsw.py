@@ -306,6 +306,23 @@ class Hnsw:
         L.check(L.lib().coltt_hnsw_pq_fetch_codes(self.h, C.c_uint64(first), C.c_uint64(n), L.vp(out)))
         return out
 
+    def PqNbrStats(self):
+        """the neighbourhood blocks of the product-quantised walk (coltt_hnsw_pq_nbr_stats): whole builds, mutating calls that patched, blocks they
+        rewrote, state 0 = none (never built / off / not affordable) / 1 = current / 2 = stale"""
+        b, p, r, s = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
+        L.check(L.lib().coltt_hnsw_pq_nbr_stats(self.h, C.byref(b), C.byref(p), C.byref(r), C.byref(s)))
+        return {"builds": b.value, "patches": p.value, "patched_rows": r.value, "state": s.value}
+
+    def PqFetchNbr(self, first=0, n=None):
+        """the blocks of slots [first, first + n) as the walk reads them (coltt_hnsw_pq_fetch_nbr): uint8 [n, m_max0, code row rounded up to 16];
+        raises unless the blocks are current (state 1)"""
+        ns = C.c_uint64(0)
+        L.check(L.lib().coltt_hnsw_export_raw(self.h, C.byref(ns), None, None, None, None, None, None))
+        n = ns.value - first if n is None else n
+        out = np.empty((n, self.cfg.m_max0, (self.PqInfo()["m"] + 15) & ~15), np.uint8)
+        L.check(L.lib().coltt_hnsw_pq_fetch_nbr(self.h, C.c_uint64(first), C.c_uint64(n), L.vp(out)))
+        return out
+
     def PqSearch(self, queries, k, ef=0, rerank=0, with_stats=False):
         q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.dim)
         nq = q.shape[0]

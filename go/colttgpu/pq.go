@@ -165,3 +165,31 @@ func HnswPqSearchFiltered(h, f Handle, dim uint32, queries []float32, nq int, k,
 	})
 	return ids, sc, cnt, err
 }
+
+// PqNbrStats: the neighbourhood blocks of the product-quantised walk (coltt_hnsw_pq_nbr_stats).  State: 0 = none (never built / off / not
+// affordable), 1 = current, 2 = stale (the next walk that reads them rebuilds).  Insert and Remove keep current blocks current: Patches counts the
+// calls that did, PatchedRows the blocks they rewrote, Builds the whole-array builds.
+type PqNbrStats struct {
+	Builds, Patches, PatchedRows uint64
+	State                        int
+}
+
+func HnswPqNbrStats(h Handle) (PqNbrStats, error) {
+	var b, p, r C.uint64_t
+	var st C.int32_t
+	err := call(func() C.int { return C.coltt_hnsw_pq_nbr_stats(h, &b, &p, &r, &st) })
+	return PqNbrStats{Builds: uint64(b), Patches: uint64(p), PatchedRows: uint64(r), State: int(st)}, err
+}
+
+// HnswPqFetchNbr: the blocks of slots [first, first + n) as the walk reads them, [n][mMax0][rowBytes] with rowBytes = the code row rounded up to 16
+// (coltt_hnsw_pq_fetch_nbr; an error unless State == 1).  Test / diagnostics.
+func HnswPqFetchNbr(h Handle, first, n uint64, mMax0, rowBytes uint32) ([]byte, error) {
+	out := make([]byte, n*uint64(mMax0)*uint64(rowBytes))
+	if len(out) == 0 {
+		return out, nil
+	}
+	err := call(func() C.int {
+		return C.coltt_hnsw_pq_fetch_nbr(h, C.uint64_t(first), C.uint64_t(n), bptr(out))
+	})
+	return out, err
+}

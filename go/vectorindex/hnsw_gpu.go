@@ -444,6 +444,28 @@ func (xx *Hnsw) SearchFilteredPq(_ context.Context, query edge.Vector, k uint, f
 	return xx.attach(ids, sc, int(cnt[0])), nil
 }
 
+// PqNbrStats — the neighbourhood blocks the product-quantised walk reads (colttgpu.HnswPqNbrStats): built whole by the first walk that needs them, kept
+// current by Insert and Remove afterwards (State 1); Load, a new quantiser or a grown capacity leave them stale (State 2) for the next walk to rebuild.
+func (xx *Hnsw) PqNbrStats() (colttgpu.PqNbrStats, error) {
+	if xx.err != nil {
+		return colttgpu.PqNbrStats{}, xx.err
+	}
+	return colttgpu.HnswPqNbrStats(xx.h)
+}
+
+// PqFetchNbr — the blocks of slots [first, first + n) as the walk reads them, [n][mMax0][rowBytes] (colttgpu.HnswPqFetchNbr; rowBytes = the quantiser's
+// sub-vector count rounded up to 16).  Test / diagnostics.
+func (xx *Hnsw) PqFetchNbr(first, n uint64, rowBytes uint32) ([]byte, error) {
+	if xx.err != nil {
+		return nil, xx.err
+	}
+	cfg, err := colttgpu.HnswGetCfg(xx.h)
+	if err != nil {
+		return nil, err
+	}
+	return colttgpu.HnswPqFetchNbr(xx.h, first, n, uint32(cfg.MMax0), rowBytes)
+}
+
 // SearchFilteredBatch(ctx, queries, k, filters) — a filter per query in one call: result i == SearchFiltered(ctx, queries[i], k, filters[i]).
 // One bad filter (closed, stale, of another index) fails the whole call; the micro-batcher's filtered mode (colttgpu.FilteredBatcher)
 // re-issues such a batch one query at a time.

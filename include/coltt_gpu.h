@@ -532,6 +532,15 @@ int coltt_hnsw_pq_attach(coltt_handle_t hnsw, coltt_handle_t pq);
 int coltt_hnsw_pq_info(coltt_handle_t hnsw, uint32_t* out_num_subvectors, uint32_t* out_num_centroids, int32_t* out_pq_metric, uint64_t* out_coded_slots);
 /* codes of slots [first_slot, first_slot + n): out_codes [n][num_subvectors] */
 int coltt_hnsw_pq_fetch_codes(coltt_handle_t hnsw, uint64_t first_slot, uint64_t n, uint8_t* out_codes);
+/* Neighbourhood blocks of the product-quantised walk: how often they were built whole, how often and how far patched.
+ * state: 0 = none (never built / off / not affordable), 1 = current, 2 = stale (the next walk that reads them rebuilds).
+ * builds = whole-array builds, patches = mutating calls (Insert / InsertBatchDevice / Remove) that re-gathered the blocks of the level-0 rows they
+ * rewrote instead of leaving the array stale, patched_rows = blocks those calls rewrote.  Outputs may be NULL. */
+int coltt_hnsw_pq_nbr_stats(coltt_handle_t hnsw, uint64_t* out_builds, uint64_t* out_patches,
+                            uint64_t* out_patched_rows, int32_t* out_state);
+/* The blocks of slots [first_slot, first_slot + n) as the walk reads them: [n][mMax0][row_bytes], row_bytes = the code
+ * row rounded up to 16 (padding and absent neighbours are zero).  COLTT_E_UNSUPPORTED unless state == 1.  Test / diagnostics. */
+int coltt_hnsw_pq_fetch_nbr(coltt_handle_t hnsw, uint64_t first_slot, uint64_t n, uint8_t* out_blocks);
 /* stats: n_dist = table-distance evaluations that counted (entrypoint, upper levels, every fresh neighbour while the set fills, afterwards the fresh
  * neighbours under the bound), n_exp / n_hops as Hnsw.Search; *out_n_exact (may be NULL) = exact re-rank evaluations */
 int coltt_hnsw_pq_search(coltt_handle_t hnsw, const float* queries, size_t nq, uint32_t k, uint32_t ef_override_or_0, uint32_t rerank,

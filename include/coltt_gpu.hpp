@@ -225,6 +225,22 @@ class Hnsw {
     if (paths) paths->assign(p.begin(), p.end());
     return out;
   }
+  // the neighbourhood blocks of the product-quantised walk (coltt_hnsw_pq_nbr_stats): State 0 = none, 1 = current, 2 = stale
+  struct PqNbrStatsResult { uint64_t Builds = 0, Patches = 0, PatchedRows = 0; int State = 0; };
+  PqNbrStatsResult PqNbrStats() const {
+    PqNbrStatsResult r; int32_t st = 0;
+    check(coltt_hnsw_pq_nbr_stats(h_, &r.Builds, &r.Patches, &r.PatchedRows, &st));
+    r.State = st;
+    return r;
+  }
+  // the blocks of slots [first, first + n) as the walk reads them (coltt_hnsw_pq_fetch_nbr): [n][mMax0][code row rounded up to 16]; test / diagnostics
+  std::vector<uint8_t> PqFetchNbr(uint64_t first, uint64_t n) const {
+    uint32_t m = 0;
+    check(coltt_hnsw_pq_info(h_, &m, nullptr, nullptr, nullptr));
+    std::vector<uint8_t> out((size_t)n * (size_t)RawConfig().m_max0 * ((m + 15u) & ~15u));
+    check(coltt_hnsw_pq_fetch_nbr(h_, first, n, out.data()));
+    return out;
+  }
   int Len() const { uint64_t n = 0; check(coltt_hnsw_len(h_, &n)); return (int)n; }
   // the collection's size is known (bulk import, Load): every array allocated once; never shrinks, never limits an Insert
   void Reserve(uint64_t vertices, uint64_t upper_rows = 0) { check(coltt_hnsw_reserve(h_, vertices, upper_rows)); }
