@@ -5,6 +5,8 @@ import numpy as np
 
 from . import _lib as L
 
+K_MAX = 2048   # largest topK the selection serves (csrc/select.hpp)
+
 
 class MultiVectorSpace:
     def __init__(self, dim, n_fields, distance=L.COSINE):
@@ -26,9 +28,10 @@ class MultiVectorSpace:
     # ChangedVertex (multi_vector_vertex.go:60-75)
     def ChangedVertex(self, ids, multi_vectors):
         ids = np.ascontiguousarray(ids, np.uint64).reshape(-1)
-        v = np.ascontiguousarray(multi_vectors, np.float32).reshape(len(ids), self.nf, -1)
-        if v.shape[2] != self.dim:
-            raise ValueError(f"index expect dimension: [{self.dim}], but got [{v.shape[2]}]")
+        v = np.ascontiguousarray(multi_vectors, np.float32)
+        if v.size != len(ids) * self.nf * self.dim:   # the library reads len(ids) x n_fields x dim floats, whatever it is handed
+            raise ValueError(f"expect {len(ids)} x {self.nf} vectors of dimension [{self.dim}] ({len(ids) * self.nf * self.dim} values), but got {v.size}")
+        v = v.reshape(len(ids), self.nf, self.dim)
         L.check(L.lib().coltt_cflat_upsert(self.h, L.vp(ids), L.vp(v), C.c_size_t(len(ids))))
 
     def RemoveVertex(self, ids):
@@ -42,6 +45,8 @@ class MultiVectorSpace:
     def MultiVertexSearch(self, topK, multi_vectors, ratios, include=None):
         q = np.ascontiguousarray(multi_vectors, np.float32).reshape(-1, self.nf, self.dim)
         r = np.ascontiguousarray(ratios, np.uint32); inc = np.ones(self.nf, np.uint8) if include is None else np.ascontiguousarray(include, np.uint8)
+        if r.size != self.nf or inc.size != self.nf:   # the library reads n_fields entries of each
+            raise ValueError(f"expect one ratio and one include flag per field ({self.nf}), but got {r.size} and {inc.size}")
         nq = q.shape[0]
         ids = np.zeros((nq, topK), np.uint64); sc = np.zeros((nq, topK), np.float32); cnt = np.zeros(nq, np.uint32)
         L.check(L.lib().coltt_cflat_search(self.h, L.vp(q), L.vp(r), L.vp(inc), C.c_size_t(nq), C.c_uint32(topK), L.vp(ids), L.vp(sc), L.vp(cnt)))

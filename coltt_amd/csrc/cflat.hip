@@ -207,30 +207,32 @@ int coltt_cflat_search(coltt_handle_t h, const float* queries, const uint32_t* r
     launch_prep_queries<Q_NONE>(c->stream, c->w_raw.as<float>(), c->nf, (int)c->dim, c->metric == COLTT_COSINE, c->w_q.as<float>());
     query_norms_kernel<<<1, 64, 0, c->stream>>>(c->w_q.as<float>(), c->nf, (int)c->dim, c->w_qn.as<float>());
     init_group_kernel<<<1, 256, 0, c->stream>>>(cnt, thr, ovf, 0);
-    auto scan = [&](uint64_t b, uint64_t e) {
+    auto scan = [&](uint64_t b, uint64_t e) -> int {
       if (e > b) {
         uint64_t groups = (e - b + 31) / 32;
         uint32_t grid = (uint32_t)std::min<uint64_t>((groups + 3) / 4, 2048);
         size_t lds = per * 4;
         if (c->metric == COLTT_COSINE) {
           auto kern = cflat_scan_kernel<M_COS>;
-          if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+          if (lds > 48 * 1024) COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
           kern<<<grid, 256, lds, c->stream>>>(F, c->stride, c->n, (int)c->nf, (int)c->dim, c->w_q.as<float>(), c->w_qn.as<float>(), d_w, thr,
                                               c->w_cand.as<unsigned long long>(), cnt, cap, b, e);
         } else {
           auto kern = cflat_scan_kernel<M_L2>;
-          if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+          if (lds > 48 * 1024) COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
           kern<<<grid, 256, lds, c->stream>>>(F, c->stride, c->n, (int)c->nf, (int)c->dim, c->w_q.as<float>(), c->w_qn.as<float>(), d_w, thr,
                                               c->w_cand.as<unsigned long long>(), cnt, cap, b, e);
         }
+        COLTT_HIP(hipGetLastError());  // a refused launch (LDS tile too large) must not read as an empty answer
       }
       flat_select_kernel<<<1, 256, 0, c->stream>>>(c->w_cand.as<unsigned long long>(), cnt, thr, cap, k, 0, c->ids.as<uint64_t>(), 0, ovf,
                                                    c->w_out_ids.as<uint64_t>(), c->w_out_sc.as<float>(), c->w_out_cnt.as<uint32_t>());
+      return COLTT_OK;
     };
     // segments of at most cap - k vertices can never overflow the candidate list
     const uint64_t seg = cap - std::min<uint32_t>(k, cap / 2);
-    if (c->n == 0) scan(0, 0);
-    for (uint64_t b = 0; b < c->n; b += seg) scan(b, std::min<uint64_t>(c->n, b + seg));
+    if (c->n == 0) COLTT_TRY(scan(0, 0));
+    for (uint64_t b = 0; b < c->n; b += seg) COLTT_TRY(scan(b, std::min<uint64_t>(c->n, b + seg)));
     uint32_t hc = 0;
     COLTT_HIP(hipMemcpyAsync(&hc, c->w_out_cnt.p, 4, hipMemcpyDeviceToHost, c->stream));
     COLTT_HIP(hipMemcpyAsync(hi.data(), c->w_out_ids.p, (size_t)k * 8, hipMemcpyDeviceToHost, c->stream));
