@@ -41,6 +41,12 @@ class MultiVectorSpace:
     def Len(self):
         n = C.c_uint64(0); L.check(L.lib().coltt_cflat_len(self.h, C.byref(n))); return n.value
 
+    def GetVertex(self, id_):
+        """the stored (for cosine: normalised) fields of one vertex, [n_fields][dim] f32; ColttError for an unknown id"""
+        o = np.zeros((self.nf, self.dim), np.float32)
+        L.check(L.lib().coltt_cflat_get(self.h, C.c_uint64(int(id_)), L.vp(o)))
+        return o
+
     # MultiVertexSearch (multi_vector_vertex.go:85-137)
     def MultiVertexSearch(self, topK, multi_vectors, ratios, include=None):
         q = np.ascontiguousarray(multi_vectors, np.float32).reshape(-1, self.nf, self.dim)
@@ -50,4 +56,17 @@ class MultiVectorSpace:
         nq = q.shape[0]
         ids = np.zeros((nq, topK), np.uint64); sc = np.zeros((nq, topK), np.float32); cnt = np.zeros(nq, np.uint32)
         L.check(L.lib().coltt_cflat_search(self.h, L.vp(q), L.vp(r), L.vp(inc), C.c_size_t(nq), C.c_uint32(topK), L.vp(ids), L.vp(sc), L.vp(cnt)))
+        return ids, sc, cnt
+
+    def MultiVertexSearchBatch(self, topK, multi_vectors, ratios, include=None):
+        """nq independent MultiVertexSearch requests in one call: ratios / include are [nq][n_fields] (include=None: every field of
+        every request).  Row i equals MultiVertexSearch(topK, multi_vectors[i], ratios[i], include[i]): same count, ids, order, score bits."""
+        q = np.ascontiguousarray(multi_vectors, np.float32).reshape(-1, self.nf, self.dim)
+        nq = q.shape[0]
+        r = np.ascontiguousarray(ratios, np.uint32); inc = np.ones((nq, self.nf), np.uint8) if include is None else np.ascontiguousarray(include, np.uint8)
+        want = (nq, self.nf)
+        if r.shape != want or inc.shape != want:   # the library reads nq x n_fields entries of each
+            raise ValueError(f"expect one ratio and one include flag per request and field {want}, but got {r.shape} and {inc.shape}")
+        ids = np.zeros((nq, topK), np.uint64); sc = np.zeros((nq, topK), np.float32); cnt = np.zeros(nq, np.uint32)
+        L.check(L.lib().coltt_cflat_search_batch(self.h, L.vp(q), L.vp(r), L.vp(inc), C.c_size_t(nq), C.c_uint32(topK), L.vp(ids), L.vp(sc), L.vp(cnt)))
         return ids, sc, cnt

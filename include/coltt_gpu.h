@@ -153,6 +153,13 @@ int coltt_cflat_upsert(coltt_handle_t h, const uint64_t* ids, const float* vecs,
 int coltt_cflat_remove(coltt_handle_t h, const uint64_t* ids, size_t n);
 int coltt_cflat_search(coltt_handle_t h, const float* queries, const uint32_t* ratios, const uint8_t* include, size_t nq,
                        uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_counts);
+/* MultiVertexSearch for nq independent requests: queries [nq][n_fields][dim], ratios [nq][n_fields], include [nq][n_fields].
+ * Row i of out_* equals coltt_cflat_search(h, query i, ratios i, include i, 1, k, ...) on the same store: same count, same ids,
+ * same order (descending by (score, id)), same f32 score bits. */
+int coltt_cflat_search_batch(coltt_handle_t h, const float* queries, const uint32_t* ratios, const uint8_t* include, size_t nq,
+                             uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_counts);
+/* the stored (for cosine: normalised) fields of one vertex, [n_fields][dim] f32; COLTT_E_NOT_FOUND for an unknown id */
+int coltt_cflat_get(coltt_handle_t h, uint64_t id, float* out_fields);
 
 /* ---- core HNSW: replaces *vectorindex.Hnsw (core/vectorindex/hnsw.go:43-54) --------------------- */
 typedef struct coltt_hnsw_cfg {       /* hnswConfig defaults: hnsw_config.go:135-162 */
