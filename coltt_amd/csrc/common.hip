@@ -86,6 +86,8 @@ Policy read_policy_from_env() {
   { const char* e = getenv("COLTT_ROW_FILTER_BITS"); if (e && !strcmp(e, "8i")) p.row_filter_bits = 80; }   // row_filter8i.hpp: ROW_FILTER_8I
   { const char* e = getenv("COLTT_ROW_SHADOW_BITS"); p.row_shadow_bits = (!e || !*e) ? 8 : (!strcmp(e, "both") ? 24 : (atoi(e) == 16 ? 16 : 8)); }
   v = num("COLTT_ROWS_NT_MIN_MB", set); p.rows_nt_min_mb = set ? std::max<long long>(0, v) : 12288;
+  p.vis16 = !off("COLTT_VIS16");
+  v = num("COLTT_VIS16_BUCKET_BITS", set); p.vis16_bucket_bits = set ? (int)std::max<long long>(1, std::min<long long>(10, v)) : 0;
   v = num("COLTT_PQ_WAVES", set); p.pq_waves = set ? (int)std::max<long long>(1, std::min<long long>(16, v)) : 0;
   p.pq_nbr = !off("COLTT_PQ_NBR");
   p.pq_nbr_patch = !off("COLTT_PQ_NBR_PATCH");

@@ -411,6 +411,8 @@ struct HCtx {
   DevBuf w_fdesc;                  // filtered batch: the walks' per-query descriptors, the exact path's queries and tiles
   PinnedBuf h_in, h_out;   // small calls: see PinnedBuf
   bool flt_launch = false;   // launch_search2 took the row-filter twin for the call in flight
+  bool v16_launch = false;   // ... and that twin walks over the 16-bit visited set (vis16.hpp)
+  const void* occ_kern = nullptr; size_t occ_lds = 0; int occ_per_cu = 0;   // the runtime's occupancy answer for the last (kernel, LDS) asked about
   int init() {  // the caller has selected the index's device
     COLTT_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     COLTT_HIP(hipEventCreate(&ev0));
@@ -457,6 +459,11 @@ struct Hnsw : Object {
   bool has_shadow8() const { return shadow8 && rows_b.p && rows_m.p && adj0_m.p; }
   bool has_shadow16() const { return shadow && rows_h.p; }
   std::atomic<uint64_t> flt_launches{0}, flt_rejected{0}, flt_f32_rows{0}, flt_shadow_rows{0};   // filtered launches whose call completed; evaluations the filter rejected; f32 rows / shadow rows they read at level 0
+  // the visited set of the last search launch (coltt_hnsw_visited_stats): 0 HBM byte map, 32 the LDS hash of 32-bit slots, 16 the 16-bit one (vis16.hpp); the
+  // traversals that launch kept resident per CU, its grid and, if it ran on the 16-bit table, the fullest stash and the most vertices one of its traversals
+  // visited; v16_launches: launches on the 16-bit table so far (one that overflowed and was re-run included)
+  std::atomic<int32_t> last_vis_kind{-1}; std::atomic<uint32_t> last_per_cu{0}, last_grid{0};
+  std::atomic<uint64_t> v16_launches{0}, last_stash_max{0}, last_visited_max{0};
   void drop_shadow() { shadow = false; if (rows_h.p) { (void)hipFree(rows_h.p); rows_h.p = nullptr; rows_h.cap = 0; } (void)hipGetLastError(); }
   // hnsw_pq.hpp: a snapshot of a trained product quantiser and one row-major code per slot (derived data, maintained like rows8:
   // writers encode the slots they added before they release the exclusive lock)
@@ -651,7 +658,8 @@ int prep_queries_any(Hnsw* x, HCtx* c, const float* d_qraw, size_t nq, uint32_t*
 
 uint32_t next_pow2(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
 
-struct SearchGeom { uint32_t ef, ef_pad, hcap; size_t lds; bool visg; uint32_t max_grid; int w2 = -1; uint32_t bloom_words = 0; bool w2_lds = false; bool ev8 = false; bool qd8i = false; };  // w2: hnsw_walk2.hpp variant (OPT bits | 8 = deep profile), -1 = hnsw_dev.hpp:search_level
+struct SearchGeom { uint32_t ef, ef_pad, hcap; size_t lds; bool visg; uint32_t max_grid; int w2 = -1; uint32_t bloom_words = 0; bool w2_lds = false; bool ev8 = false; bool qd8i = false;
+                    bool vis16 = false; uint32_t v16_bits = 0, v16_limit = 0; };   // vis16: the LDS visited set at 16 bits per entry (vis16.hpp): log2 of its bucket count, the capacity rule's limit  // w2: hnsw_walk2.hpp variant (OPT bits | 8 = deep profile), -1 = hnsw_dev.hpp:search_level
 
 #ifndef COLTT_VISG_MIN_EF
 #define COLTT_VISG_MIN_EF 128
@@ -811,6 +819,20 @@ SearchGeom search_geom(Hnsw* x, uint32_t ef, bool for_search = false, bool no_w2
     if (pol >= 0) { s.w2 = pol; s.w2_lds = true; }
   }
   s.ev8 = want8 && s.w2 >= 0;
+  // The headline walk (LDS variant 4, eight-lane core, row filter over the quantised query) keeps its visited set at 16 bits per entry (vis16.hpp) where every
+  // slot is representable: query + scratch + digit planes + result set + 16 KiB + the stash = 22 464 bytes at 768-d, ef 128 — SEVEN traversals per CU where the
+  // 32-bit table (38 784 bytes) held four.  The capacity rule is the 32-bit table's: 3/4 of 8 192 entries.  COLTT_VIS16=0 keeps the 32-bit table (per call).
+  // COLTT_VIS16_BUCKET_BITS (test knob) shrinks the table to 2^bits buckets and lifts the capacity rule, so that a small walk fills buckets, uses the stash and
+  // overflows it.
+  const Policy pol = policy();
+  if (s.ev8 && s.qd8i && s.w2_lds && s.w2 == 4 && !s.visg && pol.vis16 && ef <= 128) {
+    const uint32_t bits = pol.vis16_bucket_bits > 0 ? (uint32_t)pol.vis16_bucket_bits : VIS16_BUCKET_BITS;
+    if (x->n <= ((uint64_t)1 << (VIS16_TAG_BITS + bits))) {
+      s.vis16 = true; s.v16_bits = bits;
+      s.v16_limit = pol.vis16_bucket_bits > 0 ? 0xffffffu : ((8u << bits) >> 2) * 3;
+      s.lds = fixed + (size_t)vis16_table_words(bits) * 4 + VIS16_STASH * 4;
+    }
+  }
   return s;
 }
 
@@ -822,8 +844,12 @@ size_t waves_per_cu_cap(int quant) {
   return quant == Q_NONE ? 4 : 8;
 }
 
+// The walk over the 16-bit visited set is compiled for two waves per SIMD and its LDS fits seven times: all seven (COLTT_WAVES_PER_CU overrides here too).
+#ifndef COLTT_VIS16_WAVES_PER_CU
+#define COLTT_VIS16_WAVES_PER_CU 7
+#endif
 uint32_t resident_waves(const SearchGeom& sg, int quant) {
-  const size_t cap = (sg.w2 >= 0 && (sg.w2 & 8)) ? 4 : waves_per_cu_cap(quant);
+  const size_t cap = (sg.w2 >= 0 && (sg.w2 & 8)) ? 4 : (sg.vis16 && policy().waves_per_cu <= 0) ? (size_t)COLTT_VIS16_WAVES_PER_CU : waves_per_cu_cap(quant);
   return 256u * (uint32_t)std::max<size_t>(1, std::min<size_t>(cap, (160 * 1024) / sg.lds));
 }
 
@@ -877,6 +903,7 @@ int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32
   kern_t kern = nullptr;
   const bool nt = rows_nt(x);   // non-temporal row loads (eight-lane kernels): see exact.hpp: row_ld
   bool flt = false;             // the row-filter twin (row_filter_on)
+  bool v16 = false;             // ... over the 16-bit visited set (search_geom: vis16)
 #define COLTT_W2(V, PROF, OPT) case V: kern = hnsw_search2_kernel<METRIC, QUANT, PROF, OPT>; break;
   if (sg.w2_lds) {
     switch (sg.w2) {
@@ -889,7 +916,8 @@ int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32
         if constexpr (METRIC == M_COS && QUANT == Q_NONE) {   // the row-filter twin of the eight-lane instance just chosen
           if (sg.ev8 && row_filter_on(x, false)) {
             const int fb = row_filter_bits(x);
-            if (fb == ROW_FILTER_8I && sg.qd8i) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, ROW_FILTER_8I>;   // (sg.qd8i: search_geom made room for the digit planes)
+            if (fb == ROW_FILTER_8I && sg.qd8i && sg.vis16) { kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS16, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS16, false, ROW_FILTER_8I>; v16 = true; }
+            else if (fb == ROW_FILTER_8I && sg.qd8i) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, ROW_FILTER_8I>;   // (sg.qd8i: search_geom made room for the digit planes)
             else if (fb == 8 || fb == ROW_FILTER_8I) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, 8>;
             else kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false>;
             flt = true;
@@ -929,16 +957,21 @@ int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32
   if (x->r8 && !sg.ev8 && !(sg.w2_lds ? sg.w2 == 4 : (sg.w2 == 6 || sg.w2 == 7)))
     return fail(COLTT_E_UNSUPPORTED, "hnsw_search: walk variant %d has no instance for line-transposed rows (create the index with COLTT_ROWS8=0 for this experiment)", sg.w2);
   if (sg.ev8) x->ev8_launches.fetch_add(1);
-  c->flt_launch = flt;
+  if (sg.vis16 && !v16) return fail(COLTT_E_DEVICE, "hnsw_search: the launch's LDS was sized for the 16-bit visited set, but the walk chosen does not use it");
+  c->flt_launch = flt; c->v16_launch = v16;
   COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
   static const bool dbg_occ = [] { const char* e = getenv("COLTT_DEBUG_OCCUPANCY"); return e && *e == '1'; }();   // diagnostics: the waves the runtime keeps resident per CU at this launch's LDS
-  if (dbg_occ) {
-    int per_cu = 0;
-    COLTT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64, sg.lds));
-    fprintf(stderr, "[occupancy] walk variant %d%s filter %d (8i planes %d): %zu B of LDS per wave, %d waves resident per CU, grid %u\n", sg.w2, sg.w2_lds ? " (LDS hash)" : "", flt ? 1 : 0, sg.qd8i ? 1 : 0, sg.lds, per_cu, grid);
+  if (dbg_occ || v16) {   // (the 16-bit launches report it through coltt_hnsw_visited_stats: asked once per (kernel, LDS) and context)
+    if (c->occ_kern != reinterpret_cast<const void*>(kern) || c->occ_lds != sg.lds) {
+      int per_cu = 0;
+      COLTT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64, sg.lds));
+      c->occ_kern = reinterpret_cast<const void*>(kern); c->occ_lds = sg.lds; c->occ_per_cu = per_cu;
+    }
+    if (dbg_occ) fprintf(stderr, "[occupancy] walk variant %d%s filter %d (8i planes %d) visited set %s: %zu B of LDS per wave, %d waves resident per CU, grid %u\n", sg.w2, sg.w2_lds ? " (LDS hash)" : "", flt ? 1 : 0, sg.qd8i ? 1 : 0,
+                         v16 ? "16-bit LDS table" : (sg.w2_lds ? "32-bit LDS table" : "HBM byte map"), sg.lds, c->occ_per_cu, grid);
   }
   kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
-                                        k, sg.ef, sg.ef_pad, sg.w2_lds ? sg.hcap : sg.bloom_words, counter, oi, os, oc, stats,
+                                        k, sg.ef, sg.ef_pad, sg.w2_lds ? (v16 ? ((sg.v16_limit << 8) | sg.v16_bits) : sg.hcap) : sg.bloom_words, counter, oi, os, oc, stats,
                                         x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
                                         x->w_vepoch.as<uint32_t>() + region_base);
   COLTT_HIP(hipGetLastError());
@@ -1053,7 +1086,7 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
   // staging area (one workgroup per CU); if even that is too small for this ef the one-wave kernel serves the call.
   bool mw = nq <= lat_max_nq() && !force_single_wave;
   if (mw) {
-    SearchGeom m = sg; m.w2 = -1; m.w2_lds = false; m.bloom_words = 0; m.visg = false;
+    SearchGeom m = sg; m.w2 = -1; m.w2_lds = false; m.bloom_words = 0; m.visg = false; m.vis16 = false;
     // LDS: query + result set + exchange words + the staging area (32 padded rows) + the visited hash
     // (line-transposed rows are evaluated out of the registers they land in: no staging area — hnsw_lat.hpp: lat_eval_chunk, TP != 0)
     const bool lat_r8 = x->r8 && x->quant != COLTT_Q_F8;
@@ -1096,7 +1129,7 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
   COLTT_TRY(rc);
   COLTT_HIP(hipEventRecord(c->ev1, c->stream));
   if (x->dense && x->dense_base) add_base_kernel<<<ceil_div(nq * k, 256), 256, 0, c->stream>>>(d_oi, nq * k, x->dense_base);
-  unsigned long long h_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // [6], [7]: the row filter's counters (hnsw_kernels.hpp: hnsw_search2_rowfilter_kernel)
+  unsigned long long h_stats[18] = {0};   // [6], [7]: the row filter's counters; [16], [17]: the 16-bit visited set's maxima (hnsw_kernels.hpp: hnsw_search2_rowfilter_kernel; [8, 16) is the phase clock's)
   if (packed) COLTT_HIP(hipMemcpyAsync(c->h_out.p, c->w_pack.p, pack_bytes, hipMemcpyDeviceToHost, c->stream));
   else {
     if (!on_device) {
@@ -1104,17 +1137,17 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
       COLTT_HIP(hipMemcpyAsync(out_scores, d_os, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
       COLTT_HIP(hipMemcpyAsync(out_counts, d_oc, nq * 4, hipMemcpyDeviceToHost, c->stream));
     }
-    COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 64, hipMemcpyDeviceToHost, c->stream));
+    COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, c->stream));
   }
 #ifdef COLTT_PHASE_TIMING
   unsigned long long h_pt[8] = {0};
   COLTT_HIP(hipMemcpyAsync(h_pt, d_stats + 8, 64, hipMemcpyDeviceToHost, c->stream));
 #endif
   COLTT_HIP(hipStreamSynchronize(c->stream));  // the lease (destructor) outlives the kernel
-  if (!packed) std::memcpy(h_stats, c->h_out.p, 64);
+  if (!packed) std::memcpy(h_stats, c->h_out.p, sizeof(h_stats));
   if (packed) {
     const uint8_t* hb = c->h_out.as<uint8_t>();
-    std::memcpy(h_stats, hb + 16, 64);
+    std::memcpy(h_stats, hb + 16, sizeof(h_stats));
     std::memcpy(out_ids, hb + 256, nq * k * 8);
     std::memcpy(out_scores, hb + 256 + nq * k * 8, nq * k * 4);
     std::memcpy(out_counts, hb + 256 + nq * k * 12, nq * 4);
@@ -1133,6 +1166,14 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
   x->last_ms.store(ms);
+  {   // what this launch kept its visited set in, and how many traversals per CU it kept resident (the grid rule's figure; the 16-bit launches: the runtime's too)
+    const bool v16 = !mw && sg.w2 >= 0 && c->v16_launch;
+    uint32_t per_cu = mw ? 1u : resident_waves(sg, x->quant) / 256u;
+    if (v16 && c->occ_per_cu > 0) per_cu = std::min<uint32_t>(per_cu, (uint32_t)c->occ_per_cu);
+    x->last_vis_kind.store(sg.visg ? 0 : (v16 ? 16 : 32)); x->last_per_cu.store(per_cu); x->last_grid.store(grid);
+    x->last_stash_max.store(v16 ? h_stats[16] : 0); x->last_visited_max.store(v16 ? h_stats[17] : 0);
+    if (v16) x->v16_launches.fetch_add(1);
+  }
   if (mw && (h_stats[4] & 8ull))  // the multi-wave kernel's visited table would have needed a reset: same call on the single-wave kernel
     return search_common(x, c, queries, on_device, nq, k, ef_override, out_ids, out_scores, out_counts, stats, force | 1);
   if (sg.w2_lds && (h_stats[4] & 8ull))  // same for the walk2 kernel with the LDS hash: hnsw_dev.hpp:search_level has the reset-and-reseed path
@@ -2481,6 +2522,19 @@ int coltt_hnsw_row_filter_stats(coltt_handle_t h, uint64_t* out_rejected, uint64
   if (out_launches) *out_launches = x->flt_launches.load();
   if (out_shadow_rows) *out_shadow_rows = x->flt_shadow_rows.load();
   if (out_has_shadow) *out_has_shadow = (x->has_shadow16() ? 16 : 0) | (x->has_shadow8() ? 8 : 0);   // non-zero: some shadow is kept; bit 3 / bit 4: which
+  return COLTT_OK;
+}
+
+int coltt_hnsw_visited_stats(coltt_handle_t h, int32_t* out_kind, uint32_t* out_waves_per_cu, uint32_t* out_grid, uint64_t* out_launches16, uint64_t* out_stash_max, uint64_t* out_visited_max) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_visited_stats: unknown handle");
+  ReadLock g(x->rw);
+  if (out_kind) *out_kind = x->last_vis_kind.load();
+  if (out_waves_per_cu) *out_waves_per_cu = x->last_per_cu.load();
+  if (out_grid) *out_grid = x->last_grid.load();
+  if (out_launches16) *out_launches16 = x->v16_launches.load();
+  if (out_stash_max) *out_stash_max = x->last_stash_max.load();
+  if (out_visited_max) *out_visited_max = x->last_visited_max.load();
   return COLTT_OK;
 }
 

@@ -58,6 +58,7 @@ struct WaveCtx {
 #ifdef COLTT_PHASE_TIMING
   unsigned long long pt[8], t_last;  // shader-clock ticks per traversal phase (diagnostic build only)
 #endif
+  uint32_t v16_stash, v16_count;  // hnsw_walk2.hpp, VIS_LDS16: stash entries and visited vertices of the traversal just finished (diagnostics)
   uint32_t err;  // watchdog: 1 visited-set probe overflow, 2 expansion budget, 3 greedy hop budget (every loop is bounded)
 };
 

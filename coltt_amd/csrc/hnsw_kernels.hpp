@@ -245,8 +245,12 @@ void hnsw_search2_kernel(GraphView g, int32_t entry, int32_t entry_level,
 // level-0 walk with Group8FilterEval (hnsw_walk2.hpp) — binary16 shadow rows first, f32 rows for what the shadow cannot reject.
 // stats[6] / stats[7] / stats[5]: evaluations the filter rejected / f32 rows read at level 0 / shadow rows read.
 // BITS: the shadow phase A reads (16: rows_h; 8: rows_b + adj0_m).  stats[5] counts the shadow rows of whichever kind.
+// VISMODE == VIS_LDS16 (the headline instance alone: walk variant 4, BITS == ROW_FILTER_8I): the LDS visited set at 16 bits per entry (vis16.hpp), which is what
+// lets seven traversals share a CU's LDS; the instance leaves the register allocator room for two waves per SIMD.  bloom_words then carries
+// (capacity limit << 8) | log2(buckets); stats[16] / stats[17]: the largest stash count / visited count of a traversal (atomic maxima).
 template <int PROFILE, int OPT, int VISMODE, bool NT, int BITS = 16>
-__global__ __launch_bounds__(64) void hnsw_search2_rowfilter_kernel(GraphView g, int32_t entry, int32_t entry_level,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VISMODE == VIS_LDS16 ? 2 : 1)))
+void hnsw_search2_rowfilter_kernel(GraphView g, int32_t entry, int32_t entry_level,
                                                                    const float* __restrict__ q_eff, const float* __restrict__ qnorms,
                                                                    uint32_t nq, uint32_t k, uint32_t ef, uint32_t ef_pad, uint32_t bloom_words,
                                                                    uint32_t* __restrict__ counter, uint64_t* __restrict__ out_ids,
@@ -265,7 +269,13 @@ __global__ __launch_bounds__(64) void hnsw_search2_rowfilter_kernel(GraphView g,
   if constexpr (BITS == ROW_FILTER_8I) { qd = smem + off; off += (size_t)g.dim * 2; }
   w.res0 = reinterpret_cast<unsigned long long*>(smem + off);
   w.ef_pad = ef_pad;
-  if constexpr (VISMODE == VIS_LDS) {
+  if constexpr (VISMODE == VIS_LDS16) {
+    static_assert(BITS == ROW_FILTER_8I && OPT == 4, "the 16-bit visited set serves the headline instance");
+    w.vis = reinterpret_cast<uint32_t*>(w.res0 + (size_t)ef_pad);
+    w.hcap = bloom_words >> 8; w.hcap_mask = bloom_words & 0xffu;
+    w.bloom = nullptr; w.bloom_words = 0; w.bloom_shift = 0;
+    w.visg = nullptr; w.vis_bytes = 0; w.epoch = 0;
+  } else if constexpr (VISMODE == VIS_LDS) {
     w.vis = reinterpret_cast<uint32_t*>(w.res0 + (size_t)ef_pad);
     w.hcap = bloom_words; w.hcap_mask = bloom_words - 1;
     w.bloom = nullptr; w.bloom_words = 0; w.bloom_shift = 0;
@@ -282,6 +292,7 @@ __global__ __launch_bounds__(64) void hnsw_search2_rowfilter_kernel(GraphView g,
     const uint32_t qi = (uint32_t)__shfl((int)qt, 0, 64);
     if (qi >= nq) break;
     w.n_dist = w.n_exp = w.n_hops = w.n_resets = 0; w.err = 0;
+    if constexpr (VISMODE == VIS_LDS16) w.v16_stash = w.v16_count = 0;
 #ifdef COLTT_PHASE_TIMING
     for (int i_ = 0; i_ < 8; i_++) w.pt[i_] = 0;
     w.t_last = __builtin_amdgcn_s_memtime();
@@ -297,6 +308,9 @@ __global__ __launch_bounds__(64) void hnsw_search2_rowfilter_kernel(GraphView g,
       wave_sync();
     }
     uint32_t cur = (uint32_t)entry;
+    // (two waves per SIMD: the entry row's line addresses are the same for every query, and hoisted out of this loop they are 24 registers the instance has to
+    // spill and reload one by one in front of each line's load; re-derived per query they cost a dozen additions)
+    if constexpr (VISMODE == VIS_LDS16) asm volatile("" : "+s"(cur));
     float curd = Group8Eval<M_COS, Q_NONE, false, false, NT>().one(g, w, cur, lane);   // hnsw.go:253
     curd = __shfl(curd, 0, 64);
     w.n_dist += 1;
@@ -321,6 +335,7 @@ __global__ __launch_bounds__(64) void hnsw_search2_rowfilter_kernel(GraphView g,
       atomicAdd(&stats[6], (unsigned long long)fev.n_rej);
       atomicAdd(&stats[7], (unsigned long long)fev.n_f32);
       atomicAdd(&stats[5], (unsigned long long)fev.n_h16);
+      if constexpr (VISMODE == VIS_LDS16) { atomicMax(&stats[16], (unsigned long long)w.v16_stash); atomicMax(&stats[17], (unsigned long long)w.v16_count); }
 #ifdef COLTT_PHASE_TIMING
       COLTT_PT(w, 6)
       for (int i_ = 0; i_ < 8; i_++) atomicAdd(&stats[8 + i_], w.pt[i_]);

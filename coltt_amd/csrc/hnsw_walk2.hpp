@@ -23,6 +23,7 @@
 #include <type_traits>
 #include "hnsw_dev.hpp"
 #include "rows8.hpp"
+#include "vis16.hpp"
 
 namespace coltt {
 namespace dev {
@@ -455,7 +456,10 @@ __device__ __forceinline__ void greedy_level8(const GraphView& g, WaveCtx& w, ui
 template <class T> __device__ __forceinline__ T vis_probe(const T* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-enum { VIS_HBM = 0, VIS_LDS = 1 };   // visited set of search_level2: HBM byte map (behind the Bloom filter) | LDS hash that is never reset (err 8)
+// visited set of search_level2: HBM byte map (behind the Bloom filter) | LDS hash that is never reset (err 8) | the same, 16 bits per entry (vis16.hpp:
+// w.vis = the table, vis16_table_words(w.hcap_mask) words, then the stash of VIS16_STASH words; w.hcap_mask = log2 of the bucket count, w.hcap = the most
+// vertices the capacity rule lets in; a stash that overflows is err 8 too)
+enum { VIS_HBM = 0, VIS_LDS = 1, VIS_LDS16 = 2 };
 
 // searchLevel (hnsw.go:345-389) on level 0.  On return res[0, len) holds the result set ascending by (d, slot).
 // FILTER (coltt_hnsw_pq_search_filtered, BOUNDED evaluators only): the same walk, plus the allowed set *fs (hnsw_dev.hpp: FiltSet) — the cap smallest keys
@@ -485,7 +489,10 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
       __threadfence();
       w.epoch = 1;
     }
+  } else if constexpr (VISMODE == VIS_LDS16) {
+    for (uint32_t i = (uint32_t)lane * 4; i < vis16_table_words(w.hcap_mask); i += 256) *reinterpret_cast<u32x4v*>(w.vis + i) = u32x4v{0, 0, 0, 0};
   } else vis_clear(w, lane);
+  [[maybe_unused]] uint32_t stash_n = 0;   // VIS_LDS16: entries of the stash (wave-uniform)
   if constexpr (BLOOM) {
     for (uint32_t i = (uint32_t)lane * 4; i < w.bloom_words; i += 256) *reinterpret_cast<u32x4v*>(w.bloom + i) = u32x4v{0, 0, 0, 0};
   }
@@ -493,6 +500,7 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
   wave_sync();
   if (lane == 0) {
     if constexpr (VISMODE == VIS_HBM) __hip_atomic_store(w.visg + ep, (uint8_t)w.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if constexpr (VISMODE == VIS_LDS16) (void)vis16_test_and_set(w.vis, w.hcap_mask, ep);   // (an empty table: inserted)
     else vis_insert(w.vis, w.hcap_mask, ep);
     if constexpr (BLOOM) {
       const uint32_t h = ep * 0x9E3779B1u;
@@ -540,6 +548,9 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
     if (ci < 0 && dlane < 0) break;
     if constexpr (VISMODE == VIS_LDS) {
       if (vis_count + 64 > (w.hcap >> 2) * 3) { w.err |= 8u; break; }   // the table would need the reset path: give up, the host re-runs the call on the one-wave kernel
+    }
+    if constexpr (VISMODE == VIS_LDS16) {
+      if (vis_count + 64 > w.hcap || (w.err & 8u)) { w.err |= 8u; break; }   // the same rule (w.hcap: 3/4 of the entries), or the stash overflowed in the last expansion
     }
     const bool from_delta = key_lt(kd, kci);
     const unsigned long long ce = from_delta ? kd : kci;
@@ -650,7 +661,22 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
         if constexpr (eval_t::BOUNDED) {   // full set (see full_at_pop): the table sums of ALL listed neighbours, then the bound
           if (full_at_pop) { bounded_d = ev.eval_now(valid, half); want = want && bounded_d < lower_bound; }
         }
-        if (want) {
+        if constexpr (VISMODE == VIS_LDS16) {
+          // Test-and-set on the 16-bit table (vis16.hpp).  The stash is searched first, and only while it holds something; a lane whose two buckets are
+          // full appends its slot to the stash at its rank among such lanes (wave-uniform count), and a stash that cannot take them all is err 8.
+          uint32_t* const stash = w.vis + vis16_table_words(w.hcap_mask);
+          int r = VIS16_SEEN;
+          if (want && !(stash_n && vis16_stash_has(stash, stash_n, nb))) r = vis16_test_and_set(w.vis, w.hcap_mask, nb);
+          const unsigned long long F = __ballot(r == VIS16_FULL);
+          if (F) {   // (wave-uniform)
+            const uint32_t at = stash_n + (uint32_t)__popcll(F & ((1ull << lane) - 1ull));
+            if (r == VIS16_FULL && at < VIS16_STASH) stash[at] = nb;
+            stash_n += (uint32_t)__popcll(F);
+            if (stash_n > VIS16_STASH) { stash_n = VIS16_STASH; w.err |= 8u; }   // the pop gives up
+            wave_sync();
+          }
+          fresh_i = r != VIS16_SEEN ? 1 : 0;
+        } else if (want) {
           // Test-and-set.  No two lanes hold the same slot (a row lists a neighbour once), so load + store on the byte map is
           // race-free; agent-scope atomics are served by L2, never by a stale L1 line.
           bool maybe = true;
@@ -815,6 +841,7 @@ __device__ __forceinline__ void search_level2(const GraphView& g, WaveCtx& w, ui
   }
 #undef COLTT_PREFETCH_NEXT2
   if constexpr (DELTA) delta_flush(res, len, dl, scan_lo, lane);
+  if constexpr (VISMODE == VIS_LDS16) { w.v16_stash = stash_n; w.v16_count = vis_count; }
   out_len = len;
 }
 

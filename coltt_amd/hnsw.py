@@ -258,6 +258,15 @@ class Hnsw:
         return {"rejected": r.value, "f32_rows": e.value, "shadow_rows": s.value, "launches": n.value, "shadow": bool(f.value),
                 "shadow_bits": tuple(b for b in (8, 16) if f.value & b)}
 
+    def VisitedStats(self):
+        """the visited set of the last search launch (coltt_hnsw_visited_stats): its kind (0 HBM byte map, 32 LDS table of 32-bit slots, 16 the 16-bit LDS
+        table), the traversals that launch kept resident per CU and its grid, launches on the 16-bit table so far, and — if that last launch ran on the
+        16-bit table — the fullest stash and the most vertices one of its traversals visited"""
+        k, w, g = C.c_int32(0), C.c_uint32(0), C.c_uint32(0)
+        n, s, v = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.check(L.lib().coltt_hnsw_visited_stats(self.h, C.byref(k), C.byref(w), C.byref(g), C.byref(n), C.byref(s), C.byref(v)))
+        return {"kind": k.value, "waves_per_cu": w.value, "grid": g.value, "launches16": n.value, "stash_max": s.value, "visited_max": v.value}
+
     def FetchShadow8(self, first=0, n=None):
         """the 8-bit shadow of slots [first, first + n) (coltt_hnsw_fetch_shadow8): codes [n, dim] int8 in natural element order, (scale, error norm)
         [n, 2], and the pairs riding with the level-0 adjacency rows [n, m_max0, 2]"""

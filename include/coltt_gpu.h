@@ -329,6 +329,15 @@ int coltt_hnsw_rows8_searches(coltt_handle_t h, uint64_t* out_launches, int32_t*
  * index keeps the 8-bit shadow, else 16; the kind an index does not keep is served by the one it does.  *out_has_shadow is non-zero when any
  * shadow is kept: 8, 16 or 24 (both).  The shadow-row counter counts rows of whichever kind the launches read. */
 int coltt_hnsw_row_filter_stats(coltt_handle_t h, uint64_t* out_rejected, uint64_t* out_f32_rows, uint64_t* out_shadow_rows, uint64_t* out_launches, int32_t* out_has_shadow);
+/* The visited set of the level-0 walks (an internal of the search kernels: same answers and counters whichever serves).  Walks with ef <= 128 keep it in
+ * LDS: an open-addressed table of 32-bit slots (32 KiB, four traversals per CU with 768-d f32 rows), or — the row-filter walk over the quantised query on an
+ * index of at most 2^24 slots — an exact two-choice table of 16-bit entries with a 16-word stash (coltt_amd/csrc/vis16.hpp: 16 KiB, seven traversals per CU).
+ * COLTT_VIS16=0 (per call) keeps the 32-bit table.  A traversal that outgrows either re-runs the call on the kernel that resets and re-seeds its table.
+ * *out_kind: the visited set of the LAST search launch (0 HBM byte map, 32, 16; -1 before the first); *out_waves_per_cu / *out_grid: the traversals that launch
+ * kept resident per CU and its grid; *out_launches16: launches on the 16-bit table so far; *out_stash_max / *out_visited_max: the fullest stash and the most
+ * vertices one traversal of that last launch visited (0 unless it ran on the 16-bit table).
+ * Any out pointer may be NULL. */
+int coltt_hnsw_visited_stats(coltt_handle_t h, int32_t* out_kind, uint32_t* out_waves_per_cu, uint32_t* out_grid, uint64_t* out_launches16, uint64_t* out_stash_max, uint64_t* out_visited_max);
 /* Read-back of the 8-bit shadow for tests and tools: the codes of slots [first_slot, first_slot + n) in natural element order ([n][dim]), their
  * (scale, error norm) pairs ([n][2] floats) and the pairs carried by their level-0 adjacency rows ([n][m_max0][2] floats, zeros at empty positions).
  * Any out pointer may be NULL; COLTT_E_UNSUPPORTED when the index keeps no 8-bit shadow. */
