@@ -66,6 +66,12 @@ def lib():
         L = C.CDLL(p)
         L.coltt_last_error.restype = C.c_char_p
         L.coltt_version.restype = C.c_char_p
+        # coltt_hnsw_pq_search_filtered_batch(hnsw, filters[nq], queries, nq, k, ef, rerank, mode, out_ids, out_scores, out_counts, out_paths, stats);
+        # a library from before the entry point (COLTT_LIB: tools that measure against an older build) simply lacks it
+        if hasattr(L, "coltt_hnsw_pq_search_filtered_batch"):
+            L.coltt_hnsw_pq_search_filtered_batch.restype = C.c_int
+            L.coltt_hnsw_pq_search_filtered_batch.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
         _sync_policy()
     return _lib

@@ -1327,7 +1327,8 @@ bool pq_geom(Hnsw* x, uint32_t ef, bool force_hbm, PqGeom& out, uint32_t filt_ca
 }
 
 int launch_pq_walk(Hnsw* x, HCtx* c, const PqGeom& sg, bool nbr, uint32_t grid, uint32_t region_base, const unsigned short* lut, uint32_t nq, uint32_t k,
-                   uint32_t rerank, uint32_t* counter, uint32_t* surv, uint32_t* surv_cnt, unsigned long long* stats, const FilterView* fv = nullptr, uint32_t fcap = 0) {
+                   uint32_t rerank, uint32_t* counter, uint32_t* surv, uint32_t* surv_cnt, unsigned long long* stats, const FilterView* fv = nullptr, uint32_t fcap = 0,
+                   const PqFiltQuery* pd = nullptr) {
   const uint32_t sh = pq_lut_shift(x);
   // table row length x code-row pieces as compile-time constants for the common quantisers: 64 sub-vectors x 16 / 32 centroids (LS 4 / 5, 4 pieces),
   // 32 x 256 — the reference's shape, playground/hnswpq_verification.go:69-73 — (LS 8, 2 pieces), 96 x 256 (LS 8, 6 pieces); anything else runs the
@@ -1337,8 +1338,10 @@ int launch_pq_walk(Hnsw* x, HCtx* c, const PqGeom& sg, bool nbr, uint32_t grid, 
                             uint32_t*, uint32_t*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*, FilterView, uint32_t);
   pq_kern_t kern;
   // fv (coltt_hnsw_pq_search_filtered): the same dispatch over the FILTER instances — one filter takes the same kernel form through either entry point
-#define COLTT_PQKF(LS, NP, F) (sg.variant == 0 ? (pq_kern_t)hnsw_pq_search_kernel<0, VIS_LDS, LS, NP, false, F> : nbr ? (pq_kern_t)hnsw_pq_search_kernel<2, VIS_HBM, LS, NP, true, F> : (pq_kern_t)hnsw_pq_search_kernel<2, VIS_HBM, LS, NP, false, F>)
-#define COLTT_PQK(LS, NP) (fv ? COLTT_PQKF(LS, NP, true) : COLTT_PQKF(LS, NP, false))
+  // pd (coltt_hnsw_pq_search_filtered_batch): the same dispatch once more over the PERQ instances — nq descriptors, one per query of the launch; sg then
+  // carries the launch's variant, its largest query's LDS and the survivors' stride (ef_pad)
+#define COLTT_PQKF(LS, NP, F, P) (sg.variant == 0 ? (pq_kern_t)hnsw_pq_search_kernel<0, VIS_LDS, LS, NP, false, F, P> : nbr ? (pq_kern_t)hnsw_pq_search_kernel<2, VIS_HBM, LS, NP, true, F, P> : (pq_kern_t)hnsw_pq_search_kernel<2, VIS_HBM, LS, NP, false, F, P>)
+#define COLTT_PQK(LS, NP) (pd ? COLTT_PQKF(LS, NP, true, true) : fv ? COLTT_PQKF(LS, NP, true, false) : COLTT_PQKF(LS, NP, false, false))
   if (sh == 5 && np == 4) kern = COLTT_PQK(5, 4);
   else if (sh == 4 && np == 4) kern = COLTT_PQK(4, 4);
   else if (sh == 8 && np == 2) kern = COLTT_PQK(8, 2);
@@ -1352,24 +1355,38 @@ int launch_pq_walk(Hnsw* x, HCtx* c, const PqGeom& sg, bool nbr, uint32_t grid, 
   COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
   kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, lut, x->pq_codes.as<uint8_t>(), nbr ? x->pq_nbr.as<uint8_t>() : nullptr, x->pq_row, sh, nq, k, sg.ef, sg.ef_pad, rerank,
                                         sg.vis_words, counter, surv, surv_cnt, stats, x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride,
-                                        (size_t)x->vis_stride, x->w_vepoch.as<uint32_t>() + region_base, fv ? *fv : FilterView{nullptr, 0u}, fcap);
+                                        (size_t)x->vis_stride, x->w_vepoch.as<uint32_t>() + region_base,
+                                        pd ? FilterView{reinterpret_cast<const uint32_t*>(pd), 0u} : fv ? *fv : FilterView{nullptr, 0u}, fcap);
   COLTT_HIP(hipGetLastError());
   return COLTT_OK;
 }
 template <int METRIC, int QUANT>
 int launch_pq_rerank(Hnsw* x, HCtx* c, const PqGeom& sg, uint32_t q0, uint32_t nq, uint32_t k, const uint32_t* surv, const uint32_t* surv_cnt,
-                     unsigned long long* keys, uint64_t* oi, float* os, uint32_t* oc) {
+                     unsigned long long* keys, uint64_t* oi, float* os, uint32_t* oc, const PqFiltQuery* pd = nullptr, const float* pd_qe = nullptr,
+                     const float* pd_qn = nullptr) {
   const dim3 grid(ceil_div(sg.ef_pad, 32), nq);
   const GraphView g = x->view();
   const float* qe = c->w_qeff.as<float>() + (size_t)q0 * x->dim; const float* qn = c->w_qn.as<float>() + q0;
+  if (pd) { qe = pd_qe; qn = pd_qn; q0 = 0; }   // a compacted sub-batch (coltt_hnsw_pq_search_filtered_batch): its own queries; the select answers row pd[i].row
   if (x->r8) hnsw_pq_rerank_kernel<METRIC, QUANT, true><<<grid, 64, 0, c->stream>>>(g, qe, qn, surv, surv_cnt, sg.ef_pad, keys);
   else hnsw_pq_rerank_kernel<METRIC, QUANT, false><<<grid, 64, 0, c->stream>>>(g, qe, qn, surv, surv_cnt, sg.ef_pad, keys);
   const size_t lds = (size_t)sg.ef_pad * 8;
   COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_pq_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hnsw_pq_select_kernel<<<nq, 64, lds, c->stream>>>(keys, surv_cnt, sg.ef_pad, k, g.ids, oi + (size_t)q0 * k, os + (size_t)q0 * k, oc + q0);
+  hnsw_pq_select_kernel<<<nq, 64, lds, c->stream>>>(keys, surv_cnt, sg.ef_pad, k, g.ids, oi + (size_t)q0 * k, os + (size_t)q0 * k, oc + q0, pd);
   COLTT_HIP(hipGetLastError());
   return COLTT_OK;
 }
+
+// the geometry of one walk at ef, as every entry point decides it: the LDS hash unless the policy, the caller (force_hbm) or the table's size says the byte map
+int pq_walk_geom(Hnsw* x, uint32_t ef, bool force_hbm, uint32_t fcap, PqGeom& sg) {
+  if (wants_visg(ef) || force_hbm) COLTT_TRY(ensure_visg(x));
+  bool have = pq_geom(x, ef, force_hbm, sg, fcap);
+  if (!have && !force_hbm) { COLTT_TRY(ensure_visg(x)); have = pq_geom(x, ef, true, sg, fcap); }   // no room for the LDS hash beside the table: the byte map
+  if (!have) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search: dim %u / ef %u / %u sub-vectors need more than the CU's 160 KiB of LDS", x->dim, ef, x->pq_shape.m);
+  return COLTT_OK;
+}
+// the capacity of a filtered walk's allowed set R: what the re-rank may read
+inline uint32_t pq_filt_cap(uint32_t ef, uint32_t k, uint32_t rerank) { return rerank == 0 ? ef : std::min(std::max(rerank, k), ef); }
 
 // one attempt; *retry_hbm: the LDS hash would have needed its reset path — the caller runs the same call over the byte map
 // fv (coltt_hnsw_pq_search_filtered, WALK): the walk also keeps the allowed set R and the re-rank is over R; ef_override is then ef_walk (>= k)
@@ -1396,12 +1413,9 @@ int pq_search_once(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_
   }
   const uint32_t ef = std::max<uint32_t>(ef_override ? ef_override : (uint32_t)x->cfg.ef, k);  // gomath.MaxInt(ef, k), hnsw.go:258
   if (ef > 4096) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search: ef=%u > 4096", ef);
-  if (wants_visg(ef) || force_hbm) COLTT_TRY(ensure_visg(x));
   PqGeom sg;
-  const uint32_t fcap = fv ? (rerank == 0 ? ef : std::min(std::max(rerank, k), ef)) : 0u;   // |R| <= cap: what the re-rank may read
-  bool have = pq_geom(x, ef, force_hbm, sg, fcap);
-  if (!have && !force_hbm) { COLTT_TRY(ensure_visg(x)); have = pq_geom(x, ef, true, sg, fcap); }   // no room for the LDS hash beside the table: the byte map
-  if (!have) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search: dim %u / ef %u / %u sub-vectors need more than the CU's 160 KiB of LDS", x->dim, ef, x->pq_shape.m);
+  const uint32_t fcap = fv ? pq_filt_cap(ef, k, rerank) : 0u;   // |R| <= cap
+  COLTT_TRY(pq_walk_geom(x, ef, force_hbm, fcap, sg));
   uint32_t grid = (uint32_t)std::min<size_t>(nq, (size_t)256 * sg.per_cu);
   RegionLease lease;
   if (sg.variant != 0) { acquire_regions(x, grid, lease); grid = lease.count; }
@@ -2838,6 +2852,58 @@ int launch_filter_exact_batch(Hnsw* x, HCtx* c, uint32_t qg, uint32_t ntiles, ui
   return COLTT_OK;
 }
 
+// The exact path of a batch with a filter per query (coltt_hnsw_search_filtered_batch, coltt_hnsw_pq_search_filtered_batch): the rows of exact_q sorted
+// by filter, groups of <= qg sharing one, chunk lists as launch_filter_exact sizes them.  eq / tiles: what launch_filter_exact_batch reads.
+struct FiltExactPlan { uint32_t qg = 0; std::vector<FiltExactQ> eq; std::vector<FiltTile> tiles; uint64_t nlists = 0; };
+int plan_filter_exact_batch(Hnsw* x, const std::vector<HnswFilter*>& fl, std::vector<uint32_t>& exact_q, uint32_t k, const char* who, FiltExactPlan& out) {
+  const size_t qbytes = (((size_t)x->dim + 3) & ~(size_t)3) * 4, kbytes = (size_t)((k + 63) & ~63u) * 8;
+  uint32_t& qg = out.qg;
+  qg = FILT_QG;
+  while (qg > 1 && qg * (qbytes + kbytes) > 64 * 1024) qg--;
+  std::vector<FiltExactQ>& eq = out.eq;
+  std::vector<FiltTile>& tiles = out.tiles;
+  uint64_t& nlists = out.nlists;
+  eq.clear(); tiles.clear(); nlists = 0;
+  if (!exact_q.empty()) {
+    if (qg * (qbytes + kbytes) > 160 * 1024)
+      return fail(COLTT_E_UNSUPPORTED, "%s: dim %u / k %u need %zu B of LDS (> 160 KiB)", who, x->dim, k, qg * (qbytes + kbytes));
+    std::stable_sort(exact_q.begin(), exact_q.end(), [&](uint32_t a, uint32_t b) { return std::less<const HnswFilter*>()(fl[a], fl[b]); });
+    struct Run { size_t first, len; uint64_t nch, chunk; };
+    std::vector<Run> runs;
+    uint64_t groups = 0;
+    for (size_t a = 0; a < exact_q.size();) {
+      size_t b = a;
+      while (b < exact_q.size() && fl[exact_q[b]] == fl[exact_q[a]]) b++;
+      runs.push_back(Run{a, b - a, 0, 0});
+      groups += ceil_div(b - a, qg);
+      a = b;
+    }
+    for (Run& r : runs) r.nch = std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(4096, groups), ceil_div(fl[exact_q[r.first]]->allowed, 256)));
+    auto lists = [&] { uint64_t t = 0; for (const Run& r : runs) t += r.len * r.nch; return t; };
+    while (lists() * k * 8 > (256ull << 20)) {   // the chunk lists' workspace
+      bool any = false;
+      for (Run& r : runs) if (r.nch > 1) { r.nch = (r.nch + 1) / 2; any = true; }
+      if (!any) break;
+    }
+    for (Run& r : runs) {
+      const HnswFilter* f = fl[exact_q[r.first]];
+      const uint64_t A = f->allowed;
+      r.chunk = (((A + r.nch - 1) / r.nch) + 31) & ~31ull;
+      r.nch = (A + r.chunk - 1) / r.chunk;
+      for (size_t j = 0; j < r.len; j++) {
+        eq.push_back(FiltExactQ{exact_q[r.first + j], (uint32_t)nlists, (uint32_t)r.nch, 0u});
+        nlists += r.nch;
+      }
+      for (size_t g0 = 0; g0 < r.len; g0 += qg)
+        for (uint64_t ch = 0; ch < r.nch; ch++)
+          tiles.push_back(FiltTile{f->list.as<uint32_t>(), (uint32_t)(ch * r.chunk), (uint32_t)std::min<uint64_t>(A, (ch + 1) * r.chunk),
+                                   (uint32_t)(r.first + g0), (uint32_t)std::min<size_t>(qg, r.len - g0), (uint32_t)ch, 0u});
+    }
+    if (nlists > 0xffffffffull || tiles.size() > 0x7fffffffull) return fail(COLTT_E_UNSUPPORTED, "%s: too many exact-path chunk lists", who);
+  }
+  return COLTT_OK;
+}
+
 int filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,
                         int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, int32_t* out_paths, coltt_hnsw_filter_stats* st) {
   coltt_hnsw_filter_stats local{};
@@ -2883,49 +2949,12 @@ int filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, co
     if (wq[v].size() == 1 || sg.lds > wmax[v].lds) wmax[v] = sg;   // the launch's LDS: its largest query's
   }
   // the exact path: queries sorted by filter, groups of <= qg sharing one, chunk lists as launch_filter_exact sizes them
-  const size_t qbytes = (((size_t)x->dim + 3) & ~(size_t)3) * 4, kbytes = (size_t)((k + 63) & ~63u) * 8;
-  uint32_t qg = FILT_QG;
-  while (qg > 1 && qg * (qbytes + kbytes) > 64 * 1024) qg--;
-  std::vector<FiltExactQ> eq;
-  std::vector<FiltTile> tiles;
-  uint64_t nlists = 0;
-  if (!exact_q.empty()) {
-    if (qg * (qbytes + kbytes) > 160 * 1024)
-      return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered_batch: dim %u / k %u need %zu B of LDS (> 160 KiB)", x->dim, k, qg * (qbytes + kbytes));
-    std::stable_sort(exact_q.begin(), exact_q.end(), [&](uint32_t a, uint32_t b) { return std::less<const HnswFilter*>()(fl[a], fl[b]); });
-    struct Run { size_t first, len; uint64_t nch, chunk; };
-    std::vector<Run> runs;
-    uint64_t groups = 0;
-    for (size_t a = 0; a < exact_q.size();) {
-      size_t b = a;
-      while (b < exact_q.size() && fl[exact_q[b]] == fl[exact_q[a]]) b++;
-      runs.push_back(Run{a, b - a, 0, 0});
-      groups += ceil_div(b - a, qg);
-      a = b;
-    }
-    for (Run& r : runs) r.nch = std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(4096, groups), ceil_div(fl[exact_q[r.first]]->allowed, 256)));
-    auto lists = [&] { uint64_t t = 0; for (const Run& r : runs) t += r.len * r.nch; return t; };
-    while (lists() * k * 8 > (256ull << 20)) {   // the chunk lists' workspace
-      bool any = false;
-      for (Run& r : runs) if (r.nch > 1) { r.nch = (r.nch + 1) / 2; any = true; }
-      if (!any) break;
-    }
-    for (Run& r : runs) {
-      const HnswFilter* f = fl[exact_q[r.first]];
-      const uint64_t A = f->allowed;
-      r.chunk = (((A + r.nch - 1) / r.nch) + 31) & ~31ull;
-      r.nch = (A + r.chunk - 1) / r.chunk;
-      for (size_t j = 0; j < r.len; j++) {
-        eq.push_back(FiltExactQ{exact_q[r.first + j], (uint32_t)nlists, (uint32_t)r.nch, 0u});
-        nlists += r.nch;
-      }
-      for (size_t g0 = 0; g0 < r.len; g0 += qg)
-        for (uint64_t ch = 0; ch < r.nch; ch++)
-          tiles.push_back(FiltTile{f->list.as<uint32_t>(), (uint32_t)(ch * r.chunk), (uint32_t)std::min<uint64_t>(A, (ch + 1) * r.chunk),
-                                   (uint32_t)(r.first + g0), (uint32_t)std::min<size_t>(qg, r.len - g0), (uint32_t)ch, 0u});
-    }
-    if (nlists > 0xffffffffull || tiles.size() > 0x7fffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered_batch: too many exact-path chunk lists");
-  }
+  FiltExactPlan ep;
+  COLTT_TRY(plan_filter_exact_batch(x, fl, exact_q, k, "hnsw_search_filtered_batch", ep));
+  const uint32_t qg = ep.qg;
+  const std::vector<FiltExactQ>& eq = ep.eq;
+  const std::vector<FiltTile>& tiles = ep.tiles;
+  const uint64_t nlists = ep.nlists;
   // one upload of every table: [walks over the LDS hash][walks over the byte map][exact queries][tiles]
   const size_t o_w1 = wq[0].size() * sizeof(FiltQuery), o_eq = o_w1 + wq[1].size() * sizeof(FiltQuery);
   const size_t o_t = (o_eq + eq.size() * sizeof(FiltExactQ) + 31) & ~(size_t)31, o_end = o_t + tiles.size() * sizeof(FiltTile);
@@ -2990,6 +3019,205 @@ int filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, co
   x->last_ms.store(ms);
   if (h_stats[4]) return fail(COLTT_E_DEVICE, "hnsw_search_filtered_batch: traversal watchdog tripped (code %llu)", h_stats[4]);
   st->n_dist = h_stats[0]; st->n_exp = h_stats[1]; st->n_hops = h_stats[2]; st->n_visit_resets = h_stats[3]; st->n_exact_rows = h_stats[5];
+  return COLTT_OK;
+}
+
+// ---- coltt_hnsw_pq_search_filtered_batch: a filter per query over the walk on the quantiser's codes.  Row i is coltt_hnsw_pq_search_filtered on query i
+// alone: its path from its own filter (filter_path), its walk at ef_walk with the geometry and the capacity of R the single call gives it (pq_walk_geom,
+// pq_filt_cap), EXACT rows through the row batch's exact scan.  The walking queries are compacted (their prepared vectors gathered side by side: the
+// tables, survivors and keys are addressed by position in the launch) and run as at most two walk launches per group of queries — LDS hash, byte map — each
+// followed by the re-rank over its survivors; the select kernel answers the batch row of each.  A query whose LDS-hash walk reports the reset code runs
+// once more over the byte map, as the single call re-runs itself, and is counted once.
+__global__ void pq_gather_queries_kernel(const float* __restrict__ q_eff, const float* __restrict__ qnorms, const PqFiltQuery* __restrict__ pd, uint32_t dim,
+                                         float* __restrict__ out_q, float* __restrict__ out_n) {
+  const uint32_t j = blockIdx.x, row = pd[j].row;
+  for (uint32_t e = threadIdx.x; e < dim; e += blockDim.x) out_q[(size_t)j * dim + e] = q_eff[(size_t)row * dim + e];
+  if (threadIdx.x == 0) out_n[j] = qnorms[row];
+}
+
+int pq_filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,
+                           uint32_t rerank, int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, int32_t* out_paths,
+                           coltt_hnsw_filter_stats* st) {
+  coltt_hnsw_filter_stats local{};
+  if (!st) st = &local;
+  std::memset(st, 0, sizeof(*st));
+  if (mode != COLTT_FILTER_AUTO && mode != COLTT_FILTER_WALK && mode != COLTT_FILTER_EXACT) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: unknown mode %d", mode);
+  if (nq == 0) return COLTT_OK;
+  if (k == 0) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: k must be >= 1");
+  if (nq > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search_filtered_batch: more than 2^32-1 queries in one call");
+  const uint32_t ef = std::max<uint32_t>(ef_override ? ef_override : (uint32_t)x->cfg.ef, k);
+  if (ef > FILTER_EF_MAX) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search_filtered_batch: ef=%u > %llu", ef, (unsigned long long)FILTER_EF_MAX);
+  // each query's path, as its single-filter call would take it (n_live read once, under the caller's read lock)
+  const uint64_t n_live = x->live;
+  std::vector<uint32_t> efw(nq);
+  std::vector<uint32_t> walk_q, exact_q;   // the served queries (a non-empty filter on a non-empty index)
+  bool any_walk = false, any_exact = false;
+  for (size_t i = 0; i < nq; i++) {
+    const int path = filter_path(fl[i]->allowed, n_live, ef, mode, efw[i]);
+    if (out_paths) out_paths[i] = path;
+    if (path == COLTT_FILTER_WALK) { any_walk = true; st->ef_walk = std::max(st->ef_walk, efw[i]); }
+    else any_exact = true;
+    if (x->entry < 0 || fl[i]->allowed == 0) continue;
+    if (path == COLTT_FILTER_WALK) walk_q.push_back((uint32_t)i);
+    else exact_q.push_back((uint32_t)i);
+  }
+  st->path = any_walk && any_exact ? COLTT_FILTER_AUTO : any_walk ? COLTT_FILTER_WALK : COLTT_FILTER_EXACT;
+  if (walk_q.empty() && exact_q.empty()) {   // only empty filters, or an empty index: counts 0, not an error
+    std::memset(out_counts, 0, nq * 4);
+    return COLTT_OK;
+  }
+  if (!walk_q.empty() && x->pq_done != x->n)
+    return fail(COLTT_E_DEVICE, "hnsw_pq_search_filtered_batch: codes cover %llu of %llu slots", (unsigned long long)x->pq_done, (unsigned long long)x->n);
+  // the walks: each query's geometry is the single call's for its ef_walk; split by visited set.  A launch takes the LDS of its largest query, keeps
+  // as many traversals per CU as that one allows, and its survivors' rows are as long as its longest result set
+  struct Launch { std::vector<PqFiltQuery> q; size_t lds = 0; uint32_t ef_pad = 0, per_cu = 0; };
+  Launch wl[2];
+  auto add_walk = [&](Launch& l, const PqGeom& sg, uint32_t fcap, uint32_t i) {
+    l.q.push_back(PqFiltQuery{fl[i]->bits.as<uint32_t>(), fl[i]->slots, sg.ef, sg.ef_pad, sg.vis_words, fcap, i, 0u, 0u});
+    if (l.q.size() == 1 || sg.lds > l.lds) { l.lds = sg.lds; l.per_cu = sg.per_cu; }
+    l.ef_pad = std::max(l.ef_pad, sg.ef_pad);
+  };
+  {
+    std::map<uint32_t, PqGeom> geoms;
+    for (uint32_t i : walk_q) {
+      const uint32_t fcap = pq_filt_cap(efw[i], k, rerank);
+      auto it = geoms.find(efw[i]);
+      if (it == geoms.end()) {
+        PqGeom sg;
+        COLTT_TRY(pq_walk_geom(x, efw[i], false, fcap, sg));
+        it = geoms.emplace(efw[i], sg).first;
+      }
+      add_walk(wl[it->second.variant != 0 ? 1 : 0], it->second, fcap, i);
+    }
+  }
+  FiltExactPlan ep;
+  COLTT_TRY(plan_filter_exact_batch(x, fl, exact_q, k, "hnsw_pq_search_filtered_batch", ep));
+  // one upload of every table: [walks over the LDS hash][walks over the byte map][exact queries][tiles]
+  const size_t nw0 = wl[0].q.size(), nw1 = wl[1].q.size(), nw = nw0 + nw1;
+  const size_t o_eq = nw * sizeof(PqFiltQuery);
+  const size_t o_t = (o_eq + ep.eq.size() * sizeof(FiltExactQ) + 31) & ~(size_t)31, o_end = o_t + ep.tiles.size() * sizeof(FiltTile);
+  std::vector<uint8_t> blob(o_end);
+  if (nw0) std::memcpy(blob.data(), wl[0].q.data(), nw0 * sizeof(PqFiltQuery));
+  if (nw1) std::memcpy(blob.data() + nw0 * sizeof(PqFiltQuery), wl[1].q.data(), nw1 * sizeof(PqFiltQuery));
+  if (!ep.eq.empty()) std::memcpy(blob.data() + o_eq, ep.eq.data(), ep.eq.size() * sizeof(FiltExactQ));
+  if (!ep.tiles.empty()) std::memcpy(blob.data() + o_t, ep.tiles.data(), ep.tiles.size() * sizeof(FiltTile));
+  COLTT_TRY(c->w_fdesc.reserve(o_end));
+  uint8_t* d_desc = c->w_fdesc.as<uint8_t>();
+  PqFiltQuery* d_pd = reinterpret_cast<PqFiltQuery*>(d_desc);
+  COLTT_HIP(hipMemcpyAsync(d_desc, blob.data(), o_end, hipMemcpyHostToDevice, c->stream));
+  COLTT_TRY(c->w_out_ids.reserve(nq * k * 8));
+  COLTT_TRY(c->w_out_sc.reserve(nq * k * 4));
+  COLTT_TRY(c->w_out_cnt.reserve(nq * 4));
+  uint64_t* d_oi = c->w_out_ids.as<uint64_t>(); float* d_os = c->w_out_sc.as<float>(); uint32_t* d_oc = c->w_out_cnt.as<uint32_t>();
+  COLTT_HIP(hipMemsetAsync(d_oc, 0, nq * 4, c->stream));   // rows of empty filters stay at count 0
+  RegionLease lease;
+  bool nbr = false, nbr_known = false;
+  auto byte_map_ready = [&](uint32_t want) -> int {   // one lease and one look at the neighbourhood blocks per call
+    if (!lease.count) acquire_regions(x, want, lease);
+    if (!nbr_known) { COLTT_TRY(ensure_pq_nbr(x, c->stream, &nbr)); nbr_known = true; }
+    return COLTT_OK;
+  };
+  if (nw1) COLTT_TRY(byte_map_ready((uint32_t)std::min<size_t>(nw1, (size_t)256 * wl[1].per_cu)));
+  // the queries: all of them prepared as Search prepares them, the walking ones' then gathered into [nw][dim] | [nw] behind the raw batch
+  const size_t dim = x->dim;
+  COLTT_TRY(c->w_qraw.reserve(nq * dim * 4 + nw * dim * 4 + nw * 4));
+  COLTT_HIP(hipMemcpyAsync(c->w_qraw.p, queries, nq * dim * 4, hipMemcpyHostToDevice, c->stream));
+  COLTT_TRY(c->w_misc.reserve(256));
+  COLTT_TRY(c->h_out.reserve(256));
+  uint8_t* misc = c->w_misc.as<uint8_t>();
+  uint32_t* counter = reinterpret_cast<uint32_t*>(misc);
+  unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(misc + 16);
+  COLTT_TRY(prep_queries_any(x, c, c->w_qraw.as<float>(), nq, reinterpret_cast<uint32_t*>(misc)));   // as the single call; clears the counters
+  float* cq = c->w_qraw.as<float>() + nq * dim; float* cn = cq + nw * dim;
+  COLTT_HIP(hipEventRecord(c->ev0, c->stream));
+  const bool cos = x->metric == COLTT_COSINE;
+  const uint32_t lsh = pq_lut_shift(x);
+  const size_t lut_q = ((size_t)x->pq_row << lsh) * 2;
+  bool first_launch = true;
+  // the n walks whose descriptors are pd[0..n) (position j of the compacted queries = pd[j]): groups of queries under the workspaces' 256 MiB, as pq_search_once
+  auto run_walks = [&](const Launch& l, int variant, const PqFiltQuery* pd, size_t j0, size_t n) -> int {
+    pq_gather_queries_kernel<<<(uint32_t)n, 64, 0, c->stream>>>(c->w_qeff.as<float>(), c->w_qn.as<float>(), pd, (uint32_t)dim, cq + j0 * dim, cn + j0);
+    COLTT_HIP(hipGetLastError());
+    PqGeom sg{};
+    sg.variant = variant; sg.lds = l.lds; sg.ef_pad = l.ef_pad; sg.per_cu = l.per_cu;
+    uint32_t grid = (uint32_t)std::min<size_t>(n, (size_t)256 * l.per_cu);
+    if (variant != 0) grid = std::min(grid, lease.count);
+    const size_t group = std::max<size_t>(1, std::min<size_t>({n, (256ull << 20) / lut_q, (256ull << 20) / ((size_t)l.ef_pad * 12), (size_t)32768}));
+    COLTT_TRY(c->w_pack.reserve(group * lut_q + group * 4));
+    COLTT_TRY(c->w_surv.reserve(group * l.ef_pad * 4)); COLTT_TRY(c->w_scnt.reserve(group * 4)); COLTT_TRY(c->w_keys.reserve(group * l.ef_pad * 8));
+    for (size_t g0 = 0; g0 < n; g0 += group) {
+      const size_t gn = std::min(group, n - g0);
+      COLTT_TRY(pq_lut16_batch(c->stream, x->pq_cb.as<float>(), x->pq_shape, cq + (j0 + g0) * dim, gn, x->pq_row, lsh,
+                               reinterpret_cast<uint32_t*>(c->w_pack.as<uint8_t>() + group * lut_q), c->w_pack.as<unsigned short>()));
+      if (!first_launch) COLTT_HIP(hipMemsetAsync(counter, 0, 4, c->stream));
+      first_launch = false;
+      COLTT_TRY(launch_pq_walk(x, c, sg, nbr, (uint32_t)std::min<size_t>(grid, gn), lease.base, c->w_pack.as<unsigned short>(), (uint32_t)gn, k, rerank, counter,
+                               c->w_surv.as<uint32_t>(), c->w_scnt.as<uint32_t>(), d_stats, nullptr, 0u, pd + g0));
+      int rc;
+#define COLTT_LP_ARGS x, c, sg, 0u, (uint32_t)gn, k, c->w_surv.as<uint32_t>(), c->w_scnt.as<uint32_t>(), c->w_keys.as<unsigned long long>(), d_oi, d_os, d_oc, pd + g0, cq + (j0 + g0) * dim, cn + j0 + g0
+#define COLTT_LP(Q) rc = cos ? launch_pq_rerank<M_COS, Q>(COLTT_LP_ARGS) : launch_pq_rerank<M_L2, Q>(COLTT_LP_ARGS)
+      if (x->quant == COLTT_Q_NONE) { COLTT_LP(Q_NONE); } else { COLTT_LP(Q_F16); }
+#undef COLTT_LP
+#undef COLTT_LP_ARGS
+      COLTT_TRY(rc);
+    }
+    return COLTT_OK;
+  };
+  if (nw0) COLTT_TRY(run_walks(wl[0], 0, d_pd, 0, nw0));
+  if (nw1) COLTT_TRY(run_walks(wl[1], 2, d_pd + nw0, nw0, nw1));
+  if (!ep.eq.empty()) {
+    const FiltTile* d_tiles = reinterpret_cast<const FiltTile*>(d_desc + o_t);
+    const FiltExactQ* d_eq = reinterpret_cast<const FiltExactQ*>(d_desc + o_eq);
+    int rc = COLTT_OK;
+#define COLTT_FE(Q) rc = cos ? launch_filter_exact_batch<M_COS, Q>(x, c, ep.qg, (uint32_t)ep.tiles.size(), (uint32_t)ep.eq.size(), ep.nlists, d_tiles, d_eq, k, d_oi, d_os, d_oc, d_stats) \
+                         : launch_filter_exact_batch<M_L2, Q>(x, c, ep.qg, (uint32_t)ep.tiles.size(), (uint32_t)ep.eq.size(), ep.nlists, d_tiles, d_eq, k, d_oi, d_os, d_oc, d_stats)
+    COLTT_DISPATCH_QUANT(x->quant, COLTT_FE)
+#undef COLTT_FE
+    COLTT_TRY(rc);
+  }
+  unsigned long long h_stats[6];
+  COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 48, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipStreamSynchronize(c->stream));
+  std::memcpy(h_stats, c->h_out.p, 48);
+  if (nw0 && (h_stats[4] & 8ull) && !(h_stats[4] & ~8ull)) {   // some LDS-hash walks gave up (they added nothing to the sums): those queries over the byte map
+    std::vector<PqFiltQuery> back(nw0);
+    COLTT_HIP(hipMemcpy(back.data(), d_pd, nw0 * sizeof(PqFiltQuery), hipMemcpyDeviceToHost));
+    Launch rl;
+    std::map<uint32_t, PqGeom> geoms;
+    for (const PqFiltQuery& q : back) {
+      if (!(q.err & 8u)) continue;
+      auto it = geoms.find(q.ef);
+      if (it == geoms.end()) {
+        PqGeom sg;
+        COLTT_TRY(pq_walk_geom(x, q.ef, true, q.fcap, sg));
+        it = geoms.emplace(q.ef, sg).first;
+      }
+      add_walk(rl, it->second, q.fcap, q.row);
+    }
+    const size_t nr = rl.q.size();   // <= nw0: their descriptors and gathered queries take the places of the LDS-hash launch's
+    COLTT_TRY(byte_map_ready((uint32_t)std::min<size_t>(nr, (size_t)256 * rl.per_cu)));
+    COLTT_HIP(hipMemcpyAsync(d_pd, rl.q.data(), nr * sizeof(PqFiltQuery), hipMemcpyHostToDevice, c->stream));
+    COLTT_HIP(hipMemsetAsync(d_stats + 4, 0, 8, c->stream));
+    COLTT_TRY(run_walks(rl, 2, d_pd, 0, nr));
+    COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 48, hipMemcpyDeviceToHost, c->stream));
+    COLTT_HIP(hipStreamSynchronize(c->stream));
+    std::memcpy(h_stats, c->h_out.p, 48);
+  }
+  COLTT_HIP(hipEventRecord(c->ev1, c->stream));
+  if (h_stats[4]) {
+    COLTT_HIP(hipStreamSynchronize(c->stream));
+    return fail(COLTT_E_DEVICE, "hnsw_pq_search_filtered_batch: traversal watchdog tripped (code %llu)", h_stats[4]);
+  }
+  if (x->dense && x->dense_base) add_base_kernel<<<ceil_div(nq * k, 256), 256, 0, c->stream>>>(d_oi, nq * k, x->dense_base);
+  COLTT_HIP(hipMemcpyAsync(out_ids, d_oi, nq * k * 8, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipMemcpyAsync(out_scores, d_os, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipMemcpyAsync(out_counts, d_oc, nq * 4, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipStreamSynchronize(c->stream));   // the lease, the host tables and the callers' filters outlive the kernels
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+  x->last_ms.store(ms);
+  // [3]: the members of R the walks handed to the re-rank, [5]: the rows the exact scan read
+  st->n_dist = h_stats[0]; st->n_exp = h_stats[1]; st->n_hops = h_stats[2]; st->n_visit_resets = 0; st->n_exact_rows = h_stats[3] + h_stats[5];
   return COLTT_OK;
 }
 }  // namespace
@@ -3106,6 +3334,37 @@ int coltt_hnsw_search_filtered_batch(coltt_handle_t h, const coltt_handle_t* fil
   CtxLease<HCtx> ctx(x->pool);
   if (!ctx.c) return COLTT_E_DEVICE;
   return filter_batch_common(x.get(), ctx.c, fl, queries, nq, k, ef_override, mode, out_ids, out_scores, out_counts, out_paths, stats);
+}
+
+int coltt_hnsw_pq_search_filtered_batch(coltt_handle_t h, const coltt_handle_t* filters, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,
+                                        uint32_t rerank, int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, int32_t* out_paths,
+                                        coltt_hnsw_filter_stats* stats) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_pq_search_filtered_batch: unknown index handle");
+  ReadLock g(x->rw);
+  // no codes attached: checked first, for every mode
+  if (!x->pq_on) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: the index carries no product-quantiser codes (coltt_hnsw_pq_attach)");
+  if (nq && !filters) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: NULL filters");
+  if (nq && (!queries || !out_ids || !out_scores || !out_counts)) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: NULL buffer");
+  // every handle is checked before anything is launched; each distinct filter is held until the call returns (a concurrent destroy
+  // only unregisters it)
+  std::unordered_map<coltt_handle_t, std::shared_ptr<HnswFilter>> held;
+  std::vector<HnswFilter*> fl(nq);
+  for (size_t i = 0; i < nq; i++) {
+    auto it = held.find(filters[i]);
+    if (it == held.end()) {
+      auto f = lookup<HnswFilter>(filters[i]);
+      if (!f) return fail(COLTT_E_NOT_FOUND, "hnsw_pq_search_filtered_batch: unknown filter handle at position %zu", i);
+      if (f->index != h) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: the filter at position %zu was built for another index", i);
+      if (f->gen != x->gen) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: the filter at position %zu is stale (the index was loaded since it was built)", i);
+      it = held.emplace(filters[i], std::move(f)).first;
+    }
+    fl[i] = it->second.get();
+  }
+  COLTT_DEVICE(x->device);
+  CtxLease<HCtx> ctx(x->pool);
+  if (!ctx.c) return COLTT_E_DEVICE;
+  return pq_filter_batch_common(x.get(), ctx.c, fl, queries, nq, k, ef_override, rerank, mode, out_ids, out_scores, out_counts, out_paths, stats);
 }
 
 }  // extern "C"

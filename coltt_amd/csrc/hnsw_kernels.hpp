@@ -503,7 +503,12 @@ __global__ __launch_bounds__(256) void hnsw_search_lat_kernel(GraphView g, int32
 // FILTER (coltt_hnsw_pq_search_filtered, WALK): the same walk, plus the allowed set R (hnsw_dev.hpp: FiltSet; hnsw_walk2.hpp: search_level2<.., FILTER>) of
 // fcap entries, padded to 64, in LDS between the result set and the visited hash; the survivors handed to the re-rank are R's slots, nearest first, instead
 // of the result set's.  fv / fcap are read by the FILTER instances only.
-template <int OPT, int VISMODE, int LS, int NP = 0, bool NBR = false, bool FILTER = false>
+// PERQ (coltt_hnsw_pq_search_filtered_batch, with FILTER): the claimed index qi selects a descriptor (hnsw_dev.hpp: PqFiltQuery) that gives the query's
+// filter, ef, LDS geometry and capacity of R; the wave lays out [result set | R | visited hash] behind the table anew for every query it claims (the table
+// stays at 0).  The descriptors arrive in fv.bits (the kernel's parameter list is the one its other instances have); ef / rerank / vis_words / fcap are
+// then ignored, ef_pad is the stride of surv (the largest of the launch's queries'), and the dynamic LDS is the largest of the launch's queries'.  A
+// query whose LDS hash would have needed its reset path leaves err 8 in its descriptor, no survivors and nothing in the sums: the host runs it again.
+template <int OPT, int VISMODE, int LS, int NP = 0, bool NBR = false, bool FILTER = false, bool PERQ = false>
 // amdgpu_waves_per_eu(3): <= 168 VGPRs, three waves per SIMD — the walk is latency-bound, resident traversals are its throughput
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void hnsw_pq_search_kernel(GraphView g, int32_t entry, int32_t entry_level, const unsigned short* __restrict__ lut_g,
                                                             const uint8_t* __restrict__ codes, const uint8_t* __restrict__ nbrc, uint32_t row_bytes, uint32_t lut_shift, uint32_t nq, uint32_t k,
@@ -520,30 +525,44 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void hn
   if constexpr (LS != 0) {   // AdcEval<LS> addresses the table by absolute LDS offsets: this kernel has no static LDS, so its dynamic LDS starts at 0
     if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)smem != 0u) { if (lane == 0) atomicOr(&stats[4], 128ull); return; }
   }
-  size_t off = ((size_t)pq_walk_table_rows(row_bytes >> 4) << lut_shift) * 2;   // the pair-interleaved table (hnsw_pq.hpp); a multiple of 512
+  static_assert(!PERQ || FILTER, "a descriptor per query is the filtered batch's");
+  const size_t off_table = ((size_t)pq_walk_table_rows(row_bytes >> 4) << lut_shift) * 2;   // the pair-interleaved table (hnsw_pq.hpp); a multiple of 512
   w.qs = nullptr; w.qp = nullptr; w.scr = nullptr;
-  w.res0 = reinterpret_cast<unsigned long long*>(smem + off); off += (size_t)ef_pad * 8;
-  w.ef_pad = ef_pad;
   FiltSet fs;
   (void)fs;
-  if constexpr (FILTER) { fs.r = reinterpret_cast<unsigned long long*>(smem + off); off += (size_t)((fcap + 63u) & ~63u) * 8; fs.len = 0; fs.cap = fcap; fs.f = fv; }
-  if constexpr (VISMODE == VIS_LDS) {
-    w.vis = reinterpret_cast<uint32_t*>(smem + off); off += (size_t)vis_words * 4;
-    w.hcap = vis_words; w.hcap_mask = vis_words - 1;
-    w.bloom = nullptr; w.bloom_words = 0; w.bloom_shift = 0;
-    w.visg = nullptr; w.vis_bytes = 0; w.epoch = 0;
-  } else {
-    w.vis = nullptr; w.hcap = 0; w.hcap_mask = 0;
-    w.bloom = reinterpret_cast<uint32_t*>(smem + off); off += (size_t)vis_words * 4;
-    w.bloom_words = vis_words; w.bloom_shift = 32u - (uint32_t)__builtin_ctz(vis_words | 0x80000000u);
-    w.visg = visg + (size_t)blockIdx.x * vis_stride; w.vis_bytes = vis_stride; w.epoch = vis_epoch[blockIdx.x];
-  }
+  if constexpr (FILTER) { fs.len = 0; fs.f = fv; }
+  // what lies behind the table, for one geometry: once per launch, or (PERQ) once per claimed query
+  auto lay_out = [&](uint32_t ef_pad_q, uint32_t fcap_q, uint32_t vis_words_q) {
+    size_t off = off_table;
+    w.res0 = reinterpret_cast<unsigned long long*>(smem + off); off += (size_t)ef_pad_q * 8;
+    w.ef_pad = ef_pad_q;
+    if constexpr (FILTER) { fs.r = reinterpret_cast<unsigned long long*>(smem + off); off += (size_t)((fcap_q + 63u) & ~63u) * 8; fs.cap = fcap_q; }
+    if constexpr (VISMODE == VIS_LDS) {
+      w.vis = reinterpret_cast<uint32_t*>(smem + off); off += (size_t)vis_words_q * 4;
+      w.hcap = vis_words_q; w.hcap_mask = vis_words_q - 1;
+      w.bloom = nullptr; w.bloom_words = 0; w.bloom_shift = 0;
+    } else {
+      w.vis = nullptr; w.hcap = 0; w.hcap_mask = 0;
+      w.bloom = reinterpret_cast<uint32_t*>(smem + off); off += (size_t)vis_words_q * 4;
+      w.bloom_words = vis_words_q; w.bloom_shift = 32u - (uint32_t)__builtin_ctz(vis_words_q | 0x80000000u);
+    }
+  };
+  if constexpr (!PERQ) lay_out(ef_pad, fcap, vis_words);
+  if constexpr (VISMODE == VIS_LDS) { w.visg = nullptr; w.vis_bytes = 0; w.epoch = 0; }
+  else { w.visg = visg + (size_t)blockIdx.x * vis_stride; w.vis_bytes = vis_stride; w.epoch = vis_epoch[blockIdx.x]; }
   AdcEval<LS, NP, NBR> ev; ev.codes = codes; ev.row_bytes = row_bytes; ev.lut = lut; ev.lut_shift = lut_shift; ev.nbrc = nbrc; ev.nbr_stride = g.mMax0 * row_bytes;
   ev.hsel = (uint32_t)lane & 1u;
   for (;;) {
     const uint32_t qt = atomicAdd(counter, lane == 0 ? 1u : 0u);  // branch-free work fetch, see hnsw_search_kernel
     const uint32_t qi = (uint32_t)__shfl((int)qt, 0, 64);
     if (qi >= nq) break;
+    if constexpr (PERQ) {   // the descriptor is wave-uniform: its words go to scalar registers
+      const uint32_t* dw = reinterpret_cast<const uint32_t*>(reinterpret_cast<const PqFiltQuery*>(fv.bits) + qi);
+      auto rf = [&](int i) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)dw[i]); };
+      fs.f = FilterView{reinterpret_cast<const uint32_t*>(((uint64_t)rf(1) << 32) | rf(0)), rf(2)};
+      ef = rf(3);
+      lay_out(rf(4), rf(6), rf(5));
+    }
     w.n_dist = w.n_exp = w.n_hops = w.n_resets = 0; w.err = 0;
 #ifdef COLTT_PHASE_TIMING
     for (int i_ = 0; i_ < 8; i_++) w.pt[i_] = 0;
@@ -576,6 +595,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void hn
     if constexpr (FILTER) {
       search_level2<M_L2, Q_F16, PROF_SEARCH_HBM, OPT, VISMODE, true, AdcEval<LS, NP, NBR>&, true>(g, w, cur, curd, ef, lane, len, ev, &fs);
       r = fs.len;   // <= fcap <= ef: the host folded `rerank` into fcap
+      if constexpr (PERQ) {
+        const uint32_t qerr = (uint32_t)__shfl((int)w.err, 0, 64);
+        if (qerr) {   // reported per query; it hands nothing to the re-rank and stays out of the sums
+          if (lane == 0) { const_cast<PqFiltQuery*>(reinterpret_cast<const PqFiltQuery*>(fv.bits))[qi].err = qerr; surv_cnt[qi] = 0u; atomicOr(&stats[4], (unsigned long long)qerr); }
+          continue;
+        }
+      }
       for (uint32_t i = (uint32_t)lane; i < r; i += 64) surv[(size_t)qi * ef_pad + i] = (uint32_t)fs.r[i] >> 1;   // R, nearest first by table distance
     } else {
       search_level2<M_L2, Q_F16, PROF_SEARCH_HBM, OPT, VISMODE, true>(g, w, cur, curd, ef, lane, len, ev);  // :258-259 (M_L2: no norms ride along; Q_F16: the adjacency prefetch)
@@ -618,10 +644,11 @@ __global__ __launch_bounds__(64) void hnsw_pq_rerank_kernel(GraphView g, const f
 // step 2: the k smallest keys of a query — (exact score bits, slot) order — by k rounds of a wave minimum over the keys staged in LDS
 __global__ __launch_bounds__(64) void hnsw_pq_select_kernel(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ surv_cnt, uint32_t ef_pad, uint32_t k,
                                                             const uint64_t* __restrict__ ids, uint64_t* __restrict__ out_ids, float* __restrict__ out_scores,
-                                                            uint32_t* __restrict__ out_counts) {
+                                                            uint32_t* __restrict__ out_counts, const PqFiltQuery* __restrict__ pd = nullptr) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   unsigned long long* const res = reinterpret_cast<unsigned long long*>(smem);
   const uint32_t qi = blockIdx.x, r = surv_cnt[qi];
+  const uint32_t row = pd ? pd[qi].row : qi;   // pd (coltt_hnsw_pq_search_filtered_batch): query qi of the launch answers batch row pd[qi].row
   const int lane_in = threadIdx.x;
   for (uint32_t i = (uint32_t)lane_in; i < r; i += 64) res[i] = keys[(size_t)qi * ef_pad + i];
   wave_sync();
@@ -633,13 +660,13 @@ __global__ __launch_bounds__(64) void hnsw_pq_select_kernel(const unsigned long 
     const unsigned long long km = wave_min_u64(best);
     if (best == km && km != ~0ull) {   // keys are distinct (a slot appears once): exactly one lane
       const uint32_t slot = (uint32_t)km >> 1;
-      out_ids[(size_t)qi * k + t] = ids ? ids[slot] : (uint64_t)slot;
-      out_scores[(size_t)qi * k + t] = __uint_as_float((uint32_t)(km >> 32));
+      out_ids[(size_t)row * k + t] = ids ? ids[slot] : (uint64_t)slot;
+      out_scores[(size_t)row * k + t] = __uint_as_float((uint32_t)(km >> 32));
       res[bi] = ~0ull;
     }
     wave_sync();
   }
-  if (lane_in == 0) out_counts[qi] = n;
+  if (lane_in == 0) out_counts[row] = n;
 }
 
 // coltt_hnsw_search_filtered, EXACT: the k nearest live allowed vertices by (score bits, slot), over the filter's compacted slot list.

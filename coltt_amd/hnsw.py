@@ -356,6 +356,25 @@ class Hnsw:
                                   "ef_walk": st.ef_walk, "path": st.path, "n_exact_rows": st.n_exact_rows}
         return ids, sc, cnt
 
+    def PqSearchFilteredBatch(self, queries, k, filters, ef=0, rerank=0, mode=FILTER_AUTO, with_stats=False):
+        """a filter per query over the walk on the quantiser's codes (coltt_hnsw_pq_search_filtered_batch): row i ==
+        PqSearchFiltered(queries[i], k, filters[i], ef, rerank, mode).  `filters`: one HnswFilter per query row (repeats allowed).
+        Returns as SearchFilteredBatch: ids, scores, counts, paths (+ stats)."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        if len(filters) != nq:
+            raise ValueError(f"PqSearchFilteredBatch: {len(filters)} filters for {nq} queries")
+        fh = np.array([0 if f.h is None else f.h.value for f in filters], np.uint64)
+        ids = np.zeros((nq, k), np.uint64); sc = np.zeros((nq, k), np.float32); cnt = np.zeros(nq, np.uint32)
+        paths = np.zeros(nq, np.int32)
+        st = HnswFilterStats()
+        L.check(L.lib().coltt_hnsw_pq_search_filtered_batch(self.h, L.vp(fh), L.vp(q), C.c_size_t(nq), C.c_uint32(k), C.c_uint32(ef), C.c_uint32(rerank),
+                                                            C.c_int(int(mode)), L.vp(ids), L.vp(sc), L.vp(cnt), L.vp(paths), C.byref(st)))
+        if with_stats:
+            return ids, sc, cnt, paths, {"n_dist": st.n_dist, "n_exp": st.n_exp, "n_hops": st.n_hops, "n_visit_resets": st.n_visit_resets,
+                                         "ef_walk": st.ef_walk, "path": st.path, "n_exact_rows": st.n_exact_rows}
+        return ids, sc, cnt, paths
+
     def PqSearchDevice(self, d_q, nq, k, d_ids, d_scores, d_counts, ef=0, rerank=0):
         st = HnswStats(); nx = C.c_uint64(0)
         L.check(L.lib().coltt_hnsw_pq_search_device(self.h, C.c_void_p(d_q), C.c_size_t(nq), C.c_uint32(k), C.c_uint32(ef), C.c_uint32(rerank),

@@ -86,6 +86,15 @@ func HnswFilteredBackend(h Handle, dim uint32, ef uint32) FilteredBackend {
 	}
 }
 
+// HnswPqFilteredBackend: the filtered mode over the walk on product-quantiser codes (coltt_hnsw_pq_search_filtered_batch) for an index that
+// carries a quantiser; every caller gets the answer of its own HnswPqSearchFiltered call at this rerank.
+func HnswPqFilteredBackend(h Handle, dim uint32, ef, rerank uint32) FilteredBackend {
+	return func(f []Handle, q []float32, nq int, k uint32) ([]uint64, []float32, []uint32, error) {
+		ids, sc, cnt, _, err := HnswPqSearchFilteredBatch(h, f, dim, q, nq, k, ef, rerank, FilterAuto)
+		return ids, sc, cnt, err
+	}
+}
+
 func NewFilteredBatcher(dim int, backend FilteredBackend, maxBatch int, maxWait time.Duration) *Batcher {
 	if maxBatch < 1 {
 		maxBatch = 1

@@ -166,6 +166,30 @@ func HnswPqSearchFiltered(h, f Handle, dim uint32, queries []float32, nq int, k,
 	return ids, sc, cnt, err
 }
 
+// HnswPqSearchFilteredBatch: a filter per query over the walk on the quantiser's codes (coltt_hnsw_pq_search_filtered_batch).  Row i equals
+// HnswPqSearchFiltered(h, filters[i], query i, 1, k, ef, rerank, mode); paths[i] is the path that call takes (FilterWalk / FilterExact).  Every
+// handle is checked before anything runs: one bad filter fails the whole call, and the error names its position.
+func HnswPqSearchFilteredBatch(h Handle, filters []Handle, dim uint32, queries []float32, nq int, k, ef, rerank uint32, mode int) ([]uint64, []float32, []uint32, []int32, error) {
+	if nq == 0 || k == 0 {
+		return nil, nil, make([]uint32, nq), make([]int32, nq), nil
+	}
+	if len(filters) != nq {
+		return nil, nil, nil, nil, fmt.Errorf("HnswPqSearchFilteredBatch: %d filters for %d queries", len(filters), nq)
+	}
+	if err := checkDim(queries, dim, nq); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	ids := make([]uint64, nq*int(k))
+	sc := make([]float32, nq*int(k))
+	cnt := make([]uint32, nq)
+	paths := make([]int32, nq)
+	err := call(func() C.int {
+		return C.coltt_hnsw_pq_search_filtered_batch(h, &filters[0], fptr(queries), C.size_t(nq), C.uint32_t(k), C.uint32_t(ef), C.uint32_t(rerank),
+			C.int(mode), uptr(ids), fptr(sc), (*C.uint32_t)(unsafe.Pointer(&cnt[0])), (*C.int32_t)(unsafe.Pointer(&paths[0])), nil)
+	})
+	return ids, sc, cnt, paths, err
+}
+
 // PqNbrStats: the neighbourhood blocks of the product-quantised walk (coltt_hnsw_pq_nbr_stats).  State: 0 = none (never built / off / not
 // affordable), 1 = current, 2 = stale (the next walk that reads them rebuilds).  Insert and Remove keep current blocks current: Patches counts the
 // calls that did, PatchedRows the blocks they rewrote, Builds the whole-array builds.

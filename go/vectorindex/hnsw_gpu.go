@@ -497,6 +497,36 @@ func (xx *Hnsw) SearchFilteredBatch(_ context.Context, queries []edge.Vector, k 
 	return out, nil
 }
 
+// SearchFilteredPqBatch(ctx, queries, k, filters, rerank) — a filter per query over the walk on product-quantiser codes in one call: result i ==
+// SearchFilteredPq(ctx, queries[i], k, filters[i], rerank).  One bad filter fails the whole call, as in SearchFilteredBatch.
+func (xx *Hnsw) SearchFilteredPqBatch(_ context.Context, queries []edge.Vector, k uint, filters []*HnswFilter, rerank uint) ([]SearchResult, error) {
+	if xx.err != nil {
+		return nil, xx.err
+	}
+	if len(filters) != len(queries) {
+		return nil, fmt.Errorf("SearchFilteredPqBatch: %d filters for %d queries", len(filters), len(queries))
+	}
+	nq := len(queries)
+	flat := make([]float32, 0, nq*int(xx.dim))
+	fh := make([]colttgpu.Handle, nq)
+	for i, q := range queries {
+		if filters[i] == nil {
+			return nil, fmt.Errorf("SearchFilteredPqBatch: no filter at position %d", i)
+		}
+		flat = append(flat, q...)
+		fh[i] = filters[i].h
+	}
+	ids, sc, cnt, _, err := colttgpu.HnswPqSearchFilteredBatch(xx.h, fh, uint32(xx.dim), flat, nq, uint32(k), 0, uint32(rerank), colttgpu.FilterAuto)
+	if err != nil {
+		return nil, err
+	}
+	out := make([]SearchResult, nq)
+	for i := range out {
+		out[i] = xx.attach(ids[i*int(k):], sc[i*int(k):], int(cnt[i]))
+	}
+	return out, nil
+}
+
 func (xx *Hnsw) attach(ids []uint64, sc []float32, n int) SearchResult {
 	res := make(SearchResult, n)
 	for i := 0; i < n; i++ {

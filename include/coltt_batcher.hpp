@@ -11,7 +11,8 @@
 // returning COLTT_OK or an error code, e.g. a lambda around coltt_hnsw_search / coltt_flat_search.
 //
 // FilteredBatcher: the same collector for filtered searches, each caller with its own filter handle (coltt_hnsw_filter_create).  One
-// batch mixes any number of filters; its backend takes one handle per query, e.g. a lambda around coltt_hnsw_search_filtered_batch.
+// batch mixes any number of filters; its backend takes one handle per query, e.g. a lambda around coltt_hnsw_search_filtered_batch, or
+// PqFilteredBackend(index, rerank) for the walk over product-quantiser codes (coltt_hnsw_pq_search_filtered_batch).
 #pragma once
 #include <chrono>
 #include <condition_variable>
@@ -223,5 +224,14 @@ class FilteredBatcher {
   bool stop_ = false; uint64_t n_batches_ = 0, n_queries_ = 0, n_retried_ = 0; size_t largest_ = 0;
   std::thread worker_;  // last member: started after everything else is initialised
 };
+
+// A ready-made FilteredBatcher backend over the product-quantised walk: coltt_hnsw_pq_search_filtered_batch on `index` (which carries a quantiser:
+// coltt_hnsw_pq_attach) with this `rerank`, ef and mode for every batch.  A filtered RPC served this way gets the answer of its own
+// coltt_hnsw_pq_search_filtered call.
+inline FilteredBatcher::Backend PqFilteredBackend(coltt_handle_t index, uint32_t rerank = 0, uint32_t ef = 0, int mode = COLTT_FILTER_AUTO) {
+  return [index, rerank, ef, mode](const coltt_handle_t* filters, const float* queries, size_t nq, uint32_t k, uint64_t* ids, float* scores, uint32_t* counts) {
+    return coltt_hnsw_pq_search_filtered_batch(index, filters, queries, nq, k, ef, rerank, mode, ids, scores, counts, nullptr, nullptr);
+  };
+}
 
 }  // namespace coltt

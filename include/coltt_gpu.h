@@ -253,7 +253,7 @@ int coltt_hnsw_search_device(coltt_handle_t h, const float* d_queries, size_t nq
  * more rows than the walk would, and has no dependent chain (measured crossover: DESIGN.md, "Filtered search").
  *
  * An empty filter or an empty index gives counts of 0 and is not an error.  Not served: collection groups (the walk over product-quantiser codes
- * takes one filter per call: coltt_hnsw_pq_search_filtered below).
+ * takes the same filter objects: coltt_hnsw_pq_search_filtered and coltt_hnsw_pq_search_filtered_batch below).
  *
  * A FILTER PER QUERY (coltt_hnsw_search_filtered_batch).  filters[i] is query i's filter; row i equals
  * coltt_hnsw_search_filtered(hnsw, filters[i], query i, 1, k, ef_override, mode, ...) on the same index state: the same ids, the same
@@ -298,10 +298,29 @@ int coltt_hnsw_search_filtered_batch(coltt_handle_t hnsw, const coltt_handle_t* 
  * entry point.
  * Errors.  No codes attached: COLTT_E_INVALID as coltt_hnsw_pq_search, checked first for every mode; an unknown, foreign or stale filter: the codes of
  * coltt_hnsw_search_filtered; ef > 4096 or an LDS need above 160 KiB: COLTT_E_UNSUPPORTED.  An empty filter or an empty index gives counts of 0 and
- * no error; nq == 0 is not an error.  Host pointers only.  Not served: device pointers, a filter per query, collection groups. */
+ * no error; nq == 0 is not an error.  Host pointers only.  Not served: device pointers, collection groups.
+ *
+ * A FILTER PER QUERY (coltt_hnsw_pq_search_filtered_batch).  filters[i] is query i's filter; row i equals
+ * coltt_hnsw_pq_search_filtered(hnsw, filters[i], query i, 1, k, ef_override_or_0, rerank, mode, ...) on the same index state: the same ids, the same exact
+ * score bits, the same count (entries past the count are unspecified).  The path is decided per query from that query's own filter by the rule above
+ * (n_live is read once per call); out_paths[i] (may be NULL) = the path that single call takes.  Each walking query walks at its own ef_walk with the
+ * single call's capacity of R (ef_walk when rerank == 0, else min(max(rerank, k), ef_walk)); EXACT rows are served by the exact scan of
+ * coltt_hnsw_search_filtered_batch.  Stats: n_dist, n_exp, n_hops and n_exact_rows are the sums of the single calls'; n_visit_resets is 0; ef_walk is the
+ * largest over the queries that walk (0 if none does); path is WALK or EXACT when every query takes that path and COLTT_FILTER_AUTO (0) when the batch is
+ * mixed.  A walk whose on-chip visited set fills up is run again over the byte map, as the single call re-runs itself, and counts once.
+ * Errors, all before anything runs (no output is written): no codes attached: COLTT_E_INVALID, checked first; filters == NULL with nq > 0:
+ * COLTT_E_INVALID; an unknown handle, a filter of another index, a stale filter: the single call's codes, coltt_last_error() names the first bad
+ * position; an unknown mode, or k == 0 with nq > 0: COLTT_E_INVALID; ef > 4096, or a query whose walk needs more than 160 KiB of LDS:
+ * COLTT_E_UNSUPPORTED.  Not errors: nq == 0; an empty filter (that row's count is 0, the other rows are served); an empty index.  A handle may repeat.
+ * The call holds every filter it reads (destroying one meanwhile is safe) and takes the index's lock shared.  Host pointers only.  Not served: device
+ * pointers, collection groups, a rerank per query. */
 int coltt_hnsw_pq_search_filtered(coltt_handle_t hnsw, coltt_handle_t filter, const float* queries, size_t nq, uint32_t k, uint32_t ef_override_or_0,
                                   uint32_t rerank, int mode /* COLTT_FILTER_* */, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                   coltt_hnsw_filter_stats* stats);
+int coltt_hnsw_pq_search_filtered_batch(coltt_handle_t hnsw, const coltt_handle_t* filters /*[nq]*/, const float* queries, size_t nq,
+                                        uint32_t k, uint32_t ef_override_or_0, uint32_t rerank, int mode /* COLTT_FILTER_* */,
+                                        uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                        int32_t* out_paths /*[nq], may be NULL*/, coltt_hnsw_filter_stats* stats);
 
 /* Capacity for n_slots vertices (and n_upper_rows upper-level adjacency rows; 0 = the expectation for this index's M) in ONE allocation per
  * array, before the inserts.  Optional — Insert grows the arrays by half their size when they are full — but an index whose final size is

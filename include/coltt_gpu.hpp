@@ -225,6 +225,30 @@ class Hnsw {
     if (paths) paths->assign(p.begin(), p.end());
     return out;
   }
+  // a filter per query over the walk on product-quantiser codes (coltt_hnsw_pq_search_filtered_batch): answer i ==
+  // PqSearchFiltered(queries[i], k, *filters[i], ef, rerank, mode); paths (may be null) receives the path each query took
+  std::vector<SearchResult> PqSearchFilteredBatch(const std::vector<Vector>& queries, unsigned k, const std::vector<const Filter*>& filters,
+                                                  unsigned ef = 0, unsigned rerank = 0, int mode = COLTT_FILTER_AUTO,
+                                                  std::vector<int>* paths = nullptr, coltt_hnsw_filter_stats* stats = nullptr) const {
+    const size_t nq = queries.size();
+    if (filters.size() != nq) throw Error(COLTT_E_INVALID, "PqSearchFilteredBatch: one filter per query");
+    std::vector<float> flat(nq * dim_);
+    std::vector<coltt_handle_t> fh(nq);
+    for (size_t i = 0; i < nq; i++) {
+      if (queries[i].size() != dim_) throw Error(COLTT_E_INVALID, "PqSearchFilteredBatch: query of the wrong dimension");
+      std::copy(queries[i].begin(), queries[i].end(), flat.begin() + i * dim_);
+      fh[i] = filters[i] ? filters[i]->handle() : 0;
+    }
+    std::vector<uint64_t> ids(nq * k); std::vector<float> sc(nq * k); std::vector<uint32_t> n(nq); std::vector<int32_t> p(nq);
+    check(coltt_hnsw_pq_search_filtered_batch(h_, fh.data(), flat.data(), nq, k, ef, rerank, mode, ids.data(), sc.data(), n.data(), p.data(), stats));
+    std::vector<SearchResult> out(nq);
+    for (size_t i = 0; i < nq; i++) {
+      out[i].resize(n[i]);
+      for (uint32_t j = 0; j < n[i]; j++) out[i][j] = {ids[i * k + j], sc[i * k + j]};
+    }
+    if (paths) paths->assign(p.begin(), p.end());
+    return out;
+  }
   // the neighbourhood blocks of the product-quantised walk (coltt_hnsw_pq_nbr_stats): State 0 = none, 1 = current, 2 = stale
   struct PqNbrStatsResult { uint64_t Builds = 0, Patches = 0, PatchedRows = 0; int State = 0; };
   PqNbrStatsResult PqNbrStats() const {
