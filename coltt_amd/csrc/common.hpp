@@ -100,6 +100,7 @@ constexpr size_t SMALL_CALL_BYTES = 64 * 1024;   // queries and answers up to th
 // calls coltt_policy_reload() (the Python binding does it when it sees the environment change; tests and tools toggle knobs that way).
 struct Policy {
   bool flat_one = true;        // COLTT_FLAT_ONE=0: <= 4-query FLAT searches through the scan + select chain
+  uint32_t flat_ids_chunk = 0; // COLTT_FLAT_IDS_CHUNK (test knob): rows per tile of the per-query-list FLAT scan, rounded up to a multiple of 32; 0 = sized by the batch
   bool staging = true;         // COLTT_STAGING=0: no page-locked staging of small host-buffer calls
   bool ev8 = true;             // COLTT_EV8=0: level-0 distances of the throughput kernels from the pair-owned core even over line-transposed rows
   bool f8_mfma = true;         // COLTT_F8_MFMA=0: new "f8" cosine stores keep no binary16 copy: their batches run the exact scan (read at create)

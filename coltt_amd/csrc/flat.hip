@@ -12,6 +12,7 @@
 // rank-sort of the candidates by the canonical (score, id) order).
 #include <algorithm>
 #include <atomic>
+#include <thread>
 
 #include "common.hpp"
 #include "exact.hpp"
@@ -374,6 +375,7 @@ struct FCtx {
   DevBuf w_pack;           // small host-buffer calls: ids | scores | counts in one block (one D2H; see PinnedBuf)
   PinnedBuf h_in, h_out;
   DevBuf w_one;            // flat_one_kernel: OneState | per-block records (reserved once, at its maximum)
+  DevBuf w_ids_plan, w_ids_part, w_ids_cand, w_ids_state;   // coltt_flat_search_ids_batch: slots | bases | tiles | query order ; per-tile records ; their compacted copy ; cnt | thr | overflow
   bool one_ready = false;  // ... and its state words initialised (the kernel leaves them reset)
   int init() {  // the caller has selected the store's device
     COLTT_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -405,6 +407,7 @@ struct Flat : Object {
   float min_norm() const { return __builtin_bit_cast(float, ~norm_bits[1]); }   // NaN bits while the store is empty
   std::atomic<uint64_t> mfma_groups{0}, mfma_fallbacks{0};  // groups served by the MFMA path / sent back to the exact path
   std::atomic<uint64_t> one_groups{0};                      // searches served by the one-launch kernel (<= 4 queries)
+  std::atomic<uint64_t> ids_one_pass{0}, ids_fallback{0}, ids_pairs{0};   // coltt_flat_search_ids_batch: calls by path, (query, row) pairs of the one-pass path
   ~Flat() override {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamDestroy(stream);
@@ -881,6 +884,360 @@ void commit_upsert(Flat* f, const UpsertPlan& p) {
   f->n = p.nn;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// FilterableVertexSearch for a batch of queries with a candidate list EACH (coltt_flat_search_ids_batch): the reference serves one
+// filtered query per RPC, each with its own id list (edge/none_vectorstore.go:182-253, pkg/inverted/search.go:113-119); the
+// shared-list entry points above make a batch of such RPCs pay a translation, an upload, a launch chain and a synchronisation each.
+//   host         every named list -> ascending distinct slots (once per list), concatenated; the queries ordered by list and cut into
+//                groups of <= QG that share one; every list cut into chunks of chunk_rows: a TILE is (one group, one chunk)
+//   scan         one launch, one block per tile: the group's queries in LDS, a lane pair per gathered row (flat_eval_row: the score
+//                keys of flat_scan_kernel by construction), every wave its k best per query as flat_one_kernel's sorted register
+//                list, the block's k best (canonical (key', id') order — ties by id, not slot) to part[(query, chunk)][k]
+//   select       one launch, one block per query: its chunks' records compacted into a list that holds all of them (mass ties cannot
+//                overflow it), then the ordinary selection
+// A tile's k best under a total order contain every member of the list's k best that lies in the tile: same answers as the
+// one-query calls, bit for bit.
+// ---------------------------------------------------------------------------------------------------
+inline uint32_t ids_qg_cap(uint32_t dim) { return dim <= 1024 ? 8u : (dim <= 4096 ? 4u : 1u); }   // query tile <= 64 KiB of LDS
+
+// The queries ordered by list (stable): order[first[l] .. first[l+1]) are the queries that name list l.
+void ids_order(const uint32_t* list_of, size_t nq, size_t n_lists, std::vector<uint32_t>& order, std::vector<uint32_t>& first) {
+  first.assign(n_lists + 1, 0);
+  for (size_t i = 0; i < nq; i++) first[(list_of ? list_of[i] : (uint32_t)i) + 1]++;
+  for (size_t l = 0; l < n_lists; l++) first[l + 1] += first[l];
+  order.resize(nq);
+  std::vector<uint32_t> at(first.begin(), first.end() - 1);
+  for (size_t i = 0; i < nq; i++) order[at[list_of ? list_of[i] : (uint32_t)i]++] = (uint32_t)i;
+}
+inline uint64_t ids_list_tiles(uint64_t len, uint32_t nq_list, uint32_t chunk_rows, uint32_t qpt) {
+  return ((len + chunk_rows - 1) / chunk_rows) * ((nq_list + qpt - 1) / qpt);
+}
+// The tile plan: for every list its query groups, for every group the list's chunks.  Writes at most cap tiles; returns how many there are.
+uint64_t ids_plan(const uint64_t* lens, size_t n_lists, const std::vector<uint32_t>& first, uint32_t chunk_rows, uint32_t qpt,
+                  uint32_t* out_tiles, uint64_t cap) {
+  uint64_t t = 0;
+  for (size_t l = 0; l < n_lists; l++) {
+    const uint64_t len = lens[l];
+    if (len == 0) continue;
+    for (uint32_t a = first[l]; a < first[l + 1]; a += qpt) {
+      const uint32_t g = std::min<uint32_t>(qpt, first[l + 1] - a);
+      for (uint64_t s0 = 0; s0 < len; s0 += chunk_rows, t++) {
+        if (t >= cap) continue;
+        uint32_t* o = out_tiles + t * 5;
+        o[0] = (uint32_t)l; o[1] = (uint32_t)s0; o[2] = (uint32_t)std::min<uint64_t>(len, s0 + chunk_rows); o[3] = a; o[4] = g;
+      }
+    }
+  }
+  return t;
+}
+// Rows per tile from the (row, query group) units of the batch: about eight blocks per CU on the 256 CUs of a large batch (the ragged
+// tiles balance themselves that deep), and never fewer than 256 rows — two 32-row groups per wave — so that a list of a few hundred
+// rows is one tile and its per-tile merge and record traffic stay small beside the row reads.
+inline uint32_t ids_auto_chunk(uint64_t units) {
+  const uint64_t c = (units / (256 * 8) + 31) / 32 * 32;
+  return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(c, 256), 1u << 24);
+}
+
+template <int METRIC, int QUANT, int QG>
+__global__ __launch_bounds__(256) void flat_ids_scan_kernel(
+    const uint8_t* __restrict__ rows, size_t stride, const float* __restrict__ norms, const uint32_t* __restrict__ slots,
+    const uint32_t* __restrict__ list_base, const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ order,
+    const uint32_t* __restrict__ part_first, const float* __restrict__ q_eff, const float* __restrict__ qnorms, int dim, uint32_t k, int nearest,
+    const uint64_t* __restrict__ ids, uint64_t dense_base, uint32_t chunk_rows, OneRec* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) float qs[];   // [QG][dimp], rows on 16-byte boundaries as in flat_scan_kernel
+  __shared__ __attribute__((aligned(16))) uint32_t m_key[4 * ONE_KMAX];
+  __shared__ __attribute__((aligned(16))) uint64_t m_id[4 * ONE_KMAX];
+  __shared__ uint32_t m_slot[4 * ONE_KMAX];
+  __shared__ uint32_t s_wn[4];
+  constexpr int U = QG == 1 ? 8 : 4;
+  const uint32_t* const tile = tiles + (size_t)blockIdx.x * 5;
+  const uint32_t s0 = tile[1], s1 = tile[2], qe0 = tile[3];
+  const int nq_grp = (int)tile[4];
+  const uint32_t* __restrict__ const gather = slots + list_base[tile[0]];
+  const int dimp = (dim + 3) & ~3;
+  for (int i = threadIdx.x; i < QG * dimp; i += blockDim.x) {
+    const int q = i / dimp, e = i - q * dimp;
+    qs[i] = (q < nq_grp && e < dim) ? q_eff[(size_t)order[qe0 + q] * dim + e] : 0.f;
+  }
+  __syncthreads();
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane & 1, p = lane >> 1;
+  const uint32_t flip = nearest ? 0u : 0xffffffffu;
+  const uint64_t idflip = nearest ? 0ull : ~0ull;
+  uint32_t* const w_key = m_key + wave * 64; uint64_t* const w_id = m_id + wave * 64; uint32_t* const w_slot = m_slot + wave * 64;   // this wave's merge scratch
+  float qn[QG];
+  uint32_t bk[QG], bs[QG], bn[QG], tk[QG];
+  uint64_t bi[QG], ti[QG];
+#pragma unroll
+  for (int q = 0; q < QG; q++) { qn[q] = q < nq_grp ? qnorms[order[qe0 + q]] : 0.f; bk[q] = 0xffffffffu; bs[q] = 0xffffffffu; bi[q] = ~0ull; bn[q] = 0; tk[q] = 0xffffffffu; ti[q] = ~0ull; }
+  const uint32_t ngroups = (s1 - s0 + 31) / 32;
+  for (uint32_t g = wave; g < ngroups; g += 4) {
+    const uint32_t pos = s0 + g * 32 + p;
+    const bool valid = pos < s1;
+    const uint32_t slot = gather[valid ? pos : s0];
+    const uint8_t* row = rows + (size_t)slot * stride;
+    float rn = 0.f;
+    if constexpr (METRIC == M_COS) rn = norms[slot];
+    const uint64_t rid = (ids ? ids[slot] : dense_base + slot) ^ idflip;
+    uint32_t sk[QG];
+    flat_eval_row<METRIC, QUANT, QG, U>(row, rn, qs, dimp, dim, half, qn, sk);
+#pragma unroll
+    for (int q = 0; q < QG; q++) {
+      const uint32_t kq = sk[q] ^ flip;
+      const bool pass = valid && half == 0 && q < nq_grp && (bn[q] < k || kq < tk[q] || (kq == tk[q] && rid < ti[q]));
+      const unsigned long long m = __ballot(pass);
+      if (!m) continue;
+      // flat_one_kernel's parallel merge of the passing rows into the wave's sorted list (final positions from one uniform loop over
+      // the candidates, one scatter through the wave's LDS scratch)
+      const bool have = (uint32_t)lane < bn[q];
+      uint32_t e_shift = 0, c_rank = 0, c_below = 0;
+      for (unsigned long long mm = m; mm; mm &= mm - 1) {
+        const int j = __builtin_ctzll(mm);
+        const uint32_t kc = (uint32_t)__builtin_amdgcn_readlane((int)kq, j);
+        bool c_lt_e = kc < bk[q], c_lt_c = kc < kq;
+        if (__ballot((have && kc == bk[q]) || (pass && kc == kq && lane != j))) {   // equal keys: the ids decide
+          const uint64_t ic = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(rid >> 32), j) << 32) |
+                              (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)rid, j);
+          c_lt_e = c_lt_e || (kc == bk[q] && ic < bi[q]);
+          c_lt_c = c_lt_c || (kc == kq && ic < rid);
+        }
+        e_shift += (have && c_lt_e) ? 1u : 0u;
+        const uint32_t below = (uint32_t)__builtin_popcountll(__ballot(have && !c_lt_e));
+        if (lane == j) c_below = below;
+        c_rank += (pass && c_lt_c) ? 1u : 0u;
+      }
+      const uint32_t pe = (uint32_t)lane + e_shift, pc = c_rank + c_below;
+      if (have && pe < 64u) { w_key[pe] = bk[q]; w_id[pe] = bi[q]; w_slot[pe] = bs[q]; }
+      if (pass && pc < 64u) { w_key[pc] = kq; w_id[pc] = rid; w_slot[pc] = slot; }
+      one_wave_sync();
+      const uint32_t nn = bn[q] + (uint32_t)__builtin_popcountll(m);
+      bn[q] = nn < 64u ? nn : 64u;
+      if ((uint32_t)lane < bn[q]) { bk[q] = w_key[lane]; bi[q] = w_id[lane]; bs[q] = w_slot[lane]; }
+      if (bn[q] >= k) { tk[q] = w_key[k - 1]; ti[q] = w_id[k - 1]; }
+      one_wave_sync();
+    }
+  }
+  // ---- block merge: the four waves' lists -> the tile's k best of every query, in order; unused record places hold ~0
+  const uint32_t chunk = s0 / chunk_rows;
+#pragma unroll
+  for (int q = 0; q < QG; q++) {
+    if (q >= nq_grp) break;
+    __syncthreads();
+    const uint32_t mine = bn[q] < k ? bn[q] : k;
+    if ((uint32_t)lane < k) {
+      const uint32_t i = (uint32_t)wave * k + lane;
+      const bool have = (uint32_t)lane < mine;
+      m_key[i] = have ? bk[q] : 0xffffffffu; m_id[i] = have ? bi[q] : ~0ull; m_slot[i] = have ? bs[q] : 0xffffffffu;
+    }
+    if (lane == 0) s_wn[wave] = mine;
+    __syncthreads();
+    const uint32_t all = s_wn[0] + s_wn[1] + s_wn[2] + s_wn[3];
+    OneRec* out = part + ((size_t)part_first[qe0 + q] + chunk) * k;
+    if ((uint32_t)tid < 4 * k && m_slot[tid] != 0xffffffffu) {
+      const uint32_t ki = m_key[tid]; const uint64_t ii = m_id[tid];
+      const uint32_t rank = sel_rank(m_key, m_id, 4 * k, ki, ii);
+      if (rank < k) out[rank] = ((unsigned long long)ki << 32) | m_slot[tid];
+    }
+    if ((uint32_t)tid < k && (uint32_t)tid >= all) out[tid] = ~0ull;   // fewer than k rows in this tile
+  }
+}
+
+// One block per query (in list order): its chunks' records -> one candidate list of n_chunks x k places, which therefore cannot
+// overflow whatever ties the data holds (cf. cap1 in search_prepared), then the ordinary selection writes the query's own batch row.
+template <uint32_t KCAP>
+__global__ __launch_bounds__(256) void flat_ids_select_kernel(
+    const OneRec* __restrict__ part, const uint32_t* __restrict__ order, const uint32_t* __restrict__ part_first,
+    const uint32_t* __restrict__ n_chunks, unsigned long long* __restrict__ cand, uint32_t* __restrict__ cnt, uint32_t* __restrict__ thr,
+    uint32_t k, int nearest, const uint64_t* __restrict__ ids, uint64_t dense_base, uint32_t* __restrict__ ovf,
+    uint64_t* __restrict__ out_ids, float* __restrict__ out_scores, uint32_t* __restrict__ out_counts) {
+  __shared__ uint32_t s_n;
+  const int tid = threadIdx.x;
+  const uint32_t j = blockIdx.x, q = order[j];
+  const uint32_t flip = nearest ? 0u : 0xffffffffu;
+  const uint32_t n_rec = n_chunks[j] * k;
+  const OneRec* src = part + (size_t)part_first[j] * k;
+  unsigned long long* dst = cand + (size_t)part_first[j] * k;
+  if (tid == 0) s_n = 0;
+  __syncthreads();
+  for (uint32_t i = tid; i < n_rec; i += 256) {
+    const unsigned long long e = src[i];
+    if ((uint32_t)e == 0xffffffffu) continue;
+    const uint32_t at = atomicAdd(&s_n, 1u);
+    dst[at] = ((unsigned long long)((uint32_t)(e >> 32) ^ flip) << 32) | (uint32_t)e;
+  }
+  __syncthreads();
+  if (tid == 0) cnt[j] = s_n;
+  __syncthreads();
+  flat_select_block<KCAP>(0, dst, cnt + j, thr + j, n_rec, k, nearest, ids, dense_base, ovf, out_ids + (size_t)q * k, out_scores + (size_t)q * k, out_counts + q);
+}
+
+struct IdsScanArgs {
+  const uint32_t *slots, *list_base, *tiles, *order, *part_first;
+  uint32_t n_tiles, chunk_rows, k; int nearest; OneRec* part;
+};
+template <int METRIC, int QUANT, int QG>
+int launch_ids_scan(Flat* f, FCtx* c, const IdsScanArgs& a) {
+  const size_t lds = (size_t)QG * ((f->dim + 3) & ~3u) * 4;
+  auto kern = flat_ids_scan_kernel<METRIC, QUANT, QG>;
+  if (lds > 40 * 1024) COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  kern<<<a.n_tiles, 256, lds, c->stream>>>(f->rows.as<uint8_t>(), f->stride, f->norms.as<float>(), a.slots, a.list_base, a.tiles, a.order, a.part_first,
+                                           c->w_qeff.as<float>(), c->w_qn.as<float>(), (int)f->dim, a.k, a.nearest,
+                                           f->dense ? nullptr : f->ids.as<uint64_t>(), f->dense_base, a.chunk_rows, a.part);
+  COLTT_HIP(hipGetLastError());
+  return COLTT_OK;
+}
+int ids_scan_dispatch(Flat* f, FCtx* c, uint32_t qpt, const IdsScanArgs& a) {
+#define COLTT_IDS_Q(M, Q) (qpt <= 1 ? launch_ids_scan<M, Q, 1>(f, c, a) : (qpt <= 4 ? launch_ids_scan<M, Q, 4>(f, c, a) : launch_ids_scan<M, Q, 8>(f, c, a)))
+  int rc = COLTT_OK;
+#define COLTT_IDS(Q) rc = f->metric == COLTT_COSINE ? COLTT_IDS_Q(M_COS, Q) : COLTT_IDS_Q(M_L2, Q)
+  COLTT_DISPATCH_QUANT(f->quant, COLTT_IDS)
+#undef COLTT_IDS
+#undef COLTT_IDS_Q
+  return rc;
+}
+
+// The batch with validated arguments, under the store's shared lock.
+int flat_ids_batch(Flat* f, FCtx* c, const float* queries, size_t nq, uint32_t k, int select, const uint64_t* cand_ids, const uint64_t* list_offsets,
+                   size_t n_lists, const uint32_t* list_of, uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+  const int nearest = select == COLTT_SELECT_NEAREST;
+  std::vector<uint32_t> order, first;
+  ids_order(list_of, nq, n_lists, order, first);
+  // id -> slot, once per NAMED list: the loop of coltt_flat_search_ids_mode (unknown ids skipped, a repeated id scored once).  List l
+  // is translated in place at base[l] of one slot array laid out by the lists' RAW lengths — what unknown and repeated ids leave unused
+  // stays a gap — so the lists are independent: a large batch is translated by a few threads (the store's maps are only read under the
+  // shared lock).  A list that arrives ascending and distinct (a roaring ToArray()) is neither sorted nor deduplicated again.
+  std::vector<uint64_t> base(n_lists + 1, 0), lens(n_lists, 0);
+  std::vector<uint32_t> named;
+  uint64_t raw = 0;
+  for (size_t l = 0; l < n_lists; l++) {
+    base[l] = raw;
+    if (first[l + 1] == first[l]) continue;
+    named.push_back((uint32_t)l);
+    raw += list_offsets[l + 1] - list_offsets[l];
+  }
+  base[n_lists] = raw;
+  if (raw > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "flat_search_ids_batch: more than 2^32-1 candidate ids in one call");
+  std::unique_ptr<uint32_t[]> slots(new uint32_t[raw ? raw : 1]);
+  auto translate = [&](size_t l) {
+    uint32_t* out = slots.get() + base[l];
+    size_t m = 0; bool ascending = true;
+    for (uint64_t i = list_offsets[l]; i < list_offsets[l + 1]; i++) {
+      const uint64_t id = cand_ids[i];
+      uint32_t s;
+      if (f->dense) { if (id < f->dense_base || id >= f->dense_base + f->n) continue; s = (uint32_t)(id - f->dense_base); }
+      else { auto it = f->id2slot.find(id); if (it == f->id2slot.end()) continue; s = it->second; }
+      ascending = ascending && (m == 0 || out[m - 1] < s);
+      out[m++] = s;
+    }
+    if (!ascending) { std::sort(out, out + m); m = (size_t)(std::unique(out, out + m) - out); }
+    lens[l] = m;
+  };
+  const size_t n_workers = std::min<size_t>({8, named.size(), (size_t)(raw >> 16)});   // a thread per 64 Ki ids at least
+  if (n_workers <= 1) { for (uint32_t l : named) translate(l); }
+  else {
+    std::atomic<size_t> next{0};
+    auto work = [&] { for (size_t i; (i = next.fetch_add(1)) < named.size();) translate(named[i]); };
+    std::vector<std::thread> th;
+    for (size_t t = 1; t < n_workers; t++) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+  }
+  uint32_t max_share = 0;
+  for (size_t l = 0; l < n_lists; l++) max_share = std::max(max_share, first[l + 1] - first[l]);
+
+  if (k > ONE_KMAX) {
+    // the per-wave register list holds 64 entries: larger k goes list by list through the shared-list path (one query group per list)
+    COLTT_TRY(c->w_ids_plan.reserve(std::max<size_t>(raw, 1) * 4));
+    if (raw) COLTT_HIP(hipMemcpyAsync(c->w_ids_plan.p, slots.get(), raw * 4, hipMemcpyHostToDevice, c->stream));
+    std::vector<float> qb((size_t)max_share * f->dim), sc((size_t)max_share * k);
+    std::vector<uint64_t> oi((size_t)max_share * k);
+    std::vector<uint32_t> oc(max_share);
+    float ms = 0.f;
+    for (size_t l = 0; l < n_lists; l++) {
+      const size_t g = first[l + 1] - first[l];
+      if (!g) continue;
+      for (size_t j = 0; j < g; j++) std::memcpy(qb.data() + j * f->dim, queries + (size_t)order[first[l] + j] * f->dim, (size_t)f->dim * 4);
+      COLTT_TRY(flat_search_common(f, c, qb.data(), false, g, k, select, COLTT_MODE_EXACT, c->w_ids_plan.as<uint32_t>() + base[l], lens[l],
+                                   oi.data(), sc.data(), oc.data(), false));
+      ms += f->last_ms.load();
+      for (size_t j = 0; j < g; j++) {
+        const size_t q = order[first[l] + j];
+        std::memcpy(out_ids + q * k, oi.data() + j * k, (size_t)k * 8);
+        std::memcpy(out_scores + q * k, sc.data() + j * k, (size_t)k * 4);
+        out_counts[q] = oc[j];
+      }
+    }
+    f->last_ms.store(ms);
+    f->ids_fallback.fetch_add(1);
+    return COLTT_OK;
+  }
+
+  const uint32_t qpt = std::min<uint32_t>(ids_qg_cap(f->dim), max_share <= 1 ? 1u : (max_share <= 4 ? 4u : 8u));
+  uint64_t units = 0, pairs = 0;
+  for (size_t l = 0; l < n_lists; l++) { units += lens[l] * ((first[l + 1] - first[l] + qpt - 1) / qpt); pairs += lens[l] * (first[l + 1] - first[l]); }
+  const uint32_t knob = policy().flat_ids_chunk;
+  const uint32_t chunk_rows = knob ? knob : ids_auto_chunk(units);
+  uint64_t n_tiles = 0, n_part = 0;   // tiles; (query, chunk) record blocks of k
+  for (size_t l = 0; l < n_lists; l++) {
+    n_tiles += ids_list_tiles(lens[l], first[l + 1] - first[l], chunk_rows, qpt);
+    n_part += ((lens[l] + chunk_rows - 1) / chunk_rows) * (first[l + 1] - first[l]);
+  }
+  if (n_tiles > 0x7fffffffull || n_part * k > 0x7fffffffull) return fail(COLTT_E_UNSUPPORTED, "flat_search_ids_batch: %llu tiles, %llu records: split the batch", (unsigned long long)n_tiles, (unsigned long long)(n_part * k));
+  // one device block: slots | list bases | tiles | query order | first record block of every query | its number of chunks (the slots
+  // go up from where they were translated, the rest from `plan`: two copies, whatever the number of queries and lists)
+  const size_t o_base = 0, o_tiles = o_base + n_lists, o_order = o_tiles + n_tiles * 5, o_first = o_order + nq, o_nch = o_first + nq;   // word offsets behind the slots
+  std::vector<uint32_t> plan(o_nch + nq);
+  uint32_t* const pw = plan.data();
+  for (size_t l = 0; l < n_lists; l++) pw[o_base + l] = (uint32_t)base[l];
+  ids_plan(lens.data(), n_lists, first, chunk_rows, qpt, pw + o_tiles, n_tiles);
+  std::memcpy(pw + o_order, order.data(), nq * 4);
+  {
+    uint32_t at = 0;
+    for (size_t l = 0; l < n_lists; l++) {
+      const uint32_t nch = (uint32_t)((lens[l] + chunk_rows - 1) / chunk_rows);
+      for (uint32_t j = first[l]; j < first[l + 1]; j++) { pw[o_first + j] = at; pw[o_nch + j] = nch; at += nch; }
+    }
+  }
+  COLTT_TRY(c->w_ids_plan.reserve((raw + plan.size()) * 4));
+  if (raw) COLTT_HIP(hipMemcpyAsync(c->w_ids_plan.p, slots.get(), raw * 4, hipMemcpyHostToDevice, c->stream));
+  COLTT_HIP(hipMemcpyAsync(c->w_ids_plan.as<uint32_t>() + raw, plan.data(), plan.size() * 4, hipMemcpyHostToDevice, c->stream));
+  COLTT_TRY(c->w_qraw.reserve(nq * f->dim * 4));
+  COLTT_HIP(hipMemcpyAsync(c->w_qraw.p, queries, nq * f->dim * 4, hipMemcpyHostToDevice, c->stream));
+  COLTT_TRY(prep_queries(f, c, c->w_qraw.as<float>(), nq));
+  COLTT_TRY(c->w_ids_part.reserve(std::max<size_t>(n_part * k, 1) * 8));
+  COLTT_TRY(c->w_ids_cand.reserve(std::max<size_t>(n_part * k, 1) * 8));
+  COLTT_TRY(c->w_ids_state.reserve((2 * nq + 1) * 4));
+  const size_t pack_bytes = nq * k * 12 + nq * 4;
+  COLTT_TRY(c->w_pack.reserve(std::max(pack_bytes, SMALL_CALL_BYTES)));
+  COLTT_TRY(c->h_out.reserve(std::max(pack_bytes, SMALL_CALL_BYTES)));
+  uint8_t* b = c->w_pack.as<uint8_t>();
+  uint64_t* d_oi = reinterpret_cast<uint64_t*>(b); float* d_os = reinterpret_cast<float*>(b + nq * k * 8); uint32_t* d_oc = reinterpret_cast<uint32_t*>(b + nq * k * 12);
+  const uint32_t* const d_slots = c->w_ids_plan.as<uint32_t>();
+  const uint32_t* const w = d_slots + raw;
+  uint32_t* st = c->w_ids_state.as<uint32_t>();
+  COLTT_HIP(hipMemsetAsync(st + 2 * nq, 0, 4, c->stream));
+  COLTT_HIP(hipEventRecord(c->ev0, c->stream));
+  if (n_tiles) {
+    const IdsScanArgs a{d_slots, w + o_base, w + o_tiles, w + o_order, w + o_first, (uint32_t)n_tiles, chunk_rows, k, nearest, c->w_ids_part.as<OneRec>()};
+    COLTT_TRY(ids_scan_dispatch(f, c, qpt, a));
+  }
+  flat_ids_select_kernel<SELECT_SMALL><<<(uint32_t)nq, 256, 0, c->stream>>>(c->w_ids_part.as<OneRec>(), w + o_order, w + o_first, w + o_nch, c->w_ids_cand.as<unsigned long long>(),
+                                                                          st, st + nq, k, nearest, f->dense ? nullptr : f->ids.as<uint64_t>(), f->dense_base, st + 2 * nq, d_oi, d_os, d_oc);
+  COLTT_HIP(hipGetLastError());
+  COLTT_HIP(hipEventRecord(c->ev1, c->stream));
+  COLTT_HIP(hipMemcpyAsync(c->h_out.p, c->w_pack.p, pack_bytes, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipStreamSynchronize(c->stream));
+  const uint8_t* hb = c->h_out.as<uint8_t>();
+  std::memcpy(out_ids, hb, nq * k * 8);
+  std::memcpy(out_scores, hb + nq * k * 8, nq * k * 4);
+  std::memcpy(out_counts, hb + nq * k * 12, nq * 4);
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+  f->last_ms.store(ms);
+  f->ids_one_pass.fetch_add(1);
+  f->ids_pairs.fetch_add(pairs);
+  return COLTT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1113,6 +1470,65 @@ int coltt_flat_search_ids_mode(coltt_handle_t h, const float* queries, size_t nq
   if (!slots.empty()) COLTT_HIP(hipMemcpyAsync(ctx.c->w_gather.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, ctx.c->stream));
   return flat_search_common(f.get(), ctx.c, queries, false, nq, k, select, mode, ctx.c->w_gather.as<uint32_t>(), slots.size(),
                             out_ids, out_scores, out_counts, false);
+}
+
+int coltt_flat_search_ids_batch(coltt_handle_t h, const float* queries, size_t nq, uint32_t k, int select,
+                                const uint64_t* cand_ids, const uint64_t* list_offsets, size_t n_lists, const uint32_t* list_of,
+                                uint64_t* out_ids, float* out_scores, uint32_t* out_counts) {
+  auto f = lookup<Flat>(h);
+  if (!f) return fail(COLTT_E_NOT_FOUND, "flat_search_ids_batch: unknown handle");
+  if (nq) {
+    if (!queries || !out_ids || !out_scores || !out_counts) return fail(COLTT_E_INVALID, "flat_search_ids_batch: NULL buffer");
+    if (!list_offsets) return fail(COLTT_E_INVALID, "flat_search_ids_batch: NULL list_offsets");
+    if (nq > 0xffffffffull || n_lists > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "flat_search_ids_batch: more than 2^32-1 queries or lists");
+    for (size_t l = 0; l < n_lists; l++)
+      if (list_offsets[l + 1] < list_offsets[l]) return fail(COLTT_E_INVALID, "flat_search_ids_batch: list_offsets decreases at list %zu", l);
+    if (n_lists && list_offsets[n_lists] > list_offsets[0] && !cand_ids) return fail(COLTT_E_INVALID, "flat_search_ids_batch: NULL candidates");
+    if (!list_of && n_lists != nq) return fail(COLTT_E_INVALID, "flat_search_ids_batch: list_of is NULL and n_lists (%zu) != nq (%zu)", n_lists, nq);
+    if (list_of)
+      for (size_t i = 0; i < nq; i++)
+        if (list_of[i] >= n_lists) return fail(COLTT_E_INVALID, "flat_search_ids_batch: list_of[%zu] = %u is not one of the %zu lists", i, list_of[i], n_lists);
+  }
+  if (select != COLTT_SELECT_REFERENCE && select != COLTT_SELECT_NEAREST) return fail(COLTT_E_INVALID, "flat search: bad select %d", select);
+  if (k == 0 || k > K_MAX) return fail(COLTT_E_UNSUPPORTED, "flat search: k=%u outside [1,%u]", k, K_MAX);
+  if (nq == 0) return COLTT_OK;
+  // the lock is held for the whole call: coltt_flat_remove moves the last row into the hole, so a slot means a row only under it
+  ReadLock g(f->rw);
+  COLTT_DEVICE(f->device);
+  CtxLease<FCtx> ctx(f->pool);
+  if (!ctx.c) return COLTT_E_DEVICE;
+  return flat_ids_batch(f.get(), ctx.c, queries, nq, k, select, cand_ids, list_offsets, n_lists, list_of, out_ids, out_scores, out_counts);
+}
+
+int coltt_flat_ids_batch_stats(coltt_handle_t h, uint64_t* out_one_pass_calls, uint64_t* out_fallback_calls, uint64_t* out_pairs) {
+  auto f = lookup<Flat>(h);
+  if (!f) return fail(COLTT_E_NOT_FOUND, "flat_ids_batch_stats: unknown handle");
+  if (out_one_pass_calls) *out_one_pass_calls = f->ids_one_pass.load();
+  if (out_fallback_calls) *out_fallback_calls = f->ids_fallback.load();
+  if (out_pairs) *out_pairs = f->ids_pairs.load();
+  return COLTT_OK;
+}
+
+int coltt_flat_ids_plan_host(const uint64_t* list_lens, size_t n_lists, const uint32_t* list_of, size_t nq, uint32_t chunk_rows,
+                             uint32_t queries_per_tile, uint32_t* out_tiles, uint32_t* out_query_order, uint64_t cap, uint64_t* out_n_tiles) {
+  if (!out_n_tiles) return fail(COLTT_E_INVALID, "flat_ids_plan_host: out_n_tiles is NULL");
+  *out_n_tiles = 0;
+  if ((n_lists && !list_lens) || (nq && !out_query_order) || (cap && !out_tiles)) return fail(COLTT_E_INVALID, "flat_ids_plan_host: NULL buffer");
+  if (chunk_rows == 0 || chunk_rows % 32 != 0) return fail(COLTT_E_INVALID, "flat_ids_plan_host: chunk_rows %u is not a positive multiple of 32", chunk_rows);
+  if (queries_per_tile == 0) return fail(COLTT_E_INVALID, "flat_ids_plan_host: queries_per_tile is 0");
+  if (nq > 0xffffffffull || n_lists > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "flat_ids_plan_host: more than 2^32-1 queries or lists");
+  if (!list_of && n_lists != nq) return fail(COLTT_E_INVALID, "flat_ids_plan_host: list_of is NULL and n_lists (%zu) != nq (%zu)", n_lists, nq);
+  if (list_of)
+    for (size_t i = 0; i < nq; i++)
+      if (list_of[i] >= n_lists) return fail(COLTT_E_INVALID, "flat_ids_plan_host: list_of[%zu] = %u is not one of the %zu lists", i, list_of[i], n_lists);
+  for (size_t l = 0; l < n_lists; l++)
+    if (list_lens[l] > 0xffffffffull) return fail(COLTT_E_INVALID, "flat_ids_plan_host: list %zu is longer than 2^32-1 rows", l);
+  std::vector<uint32_t> order, first;
+  ids_order(list_of, nq, n_lists, order, first);
+  if (nq) std::memcpy(out_query_order, order.data(), nq * 4);
+  *out_n_tiles = ids_plan(list_lens, n_lists, first, chunk_rows, queries_per_tile, out_tiles, cap);
+  if (*out_n_tiles > cap) return fail(COLTT_E_INVALID, "flat_ids_plan_host: %llu tiles do not fit cap %llu", (unsigned long long)*out_n_tiles, (unsigned long long)cap);
+  return COLTT_OK;
 }
 
 

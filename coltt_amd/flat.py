@@ -111,6 +111,36 @@ class FlatSpace:
                                                    C.c_size_t(len(cand)), L.vp(ids), L.vp(sc), L.vp(cnt)))
         return ids, sc, cnt
 
+    # -- a batch of FilterableVertexSearch RPCs, every query with its own candidate list (coltt_flat_search_ids_batch)
+    def FilterableVertexSearchBatch(self, lists, targets, topK, select=L.SELECT_REFERENCE, list_of=None, offsets=None):
+        """lists: a sequence of id arrays; query i is searched over lists[list_of[i]] (list_of=None: over lists[i], len(lists) == nq).
+        Row i equals FilterableVertexSearch(that list, targets[i:i+1], topK, select).  With `offsets` ([n_lists + 1]) `lists` is the
+        C ABI's form instead: ONE id array, list l = lists[offsets[l]:offsets[l+1]] (nothing is concatenated here)."""
+        q = np.ascontiguousarray(targets, np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        if offsets is not None:
+            cand = np.ascontiguousarray(lists, np.uint64).reshape(-1)
+            off = np.ascontiguousarray(offsets, np.uint64).reshape(-1)
+            ls = range(len(off) - 1)
+        else:
+            ls = [np.ascontiguousarray(c, np.uint64).reshape(-1) for c in lists]
+            off = np.zeros(len(ls) + 1, np.uint64)
+            if ls:
+                off[1:] = np.cumsum([len(c) for c in ls], dtype=np.uint64)
+            cand = np.concatenate(ls) if ls else np.zeros(0, np.uint64)
+        lo = None if list_of is None else np.ascontiguousarray(list_of, np.uint32).reshape(-1)
+        if lo is not None and len(lo) != nq:
+            raise ValueError(f"list_of has {len(lo)} entries for {nq} queries")
+        ids = np.zeros((nq, max(topK, 1)), np.uint64); sc = np.zeros((nq, max(topK, 1)), np.float32); cnt = np.zeros(nq, np.uint32)
+        L.check(L.lib().coltt_flat_search_ids_batch(self.h, L.vp(q), C.c_size_t(nq), C.c_uint32(topK), select, L.vp(cand if len(cand) else None),
+                                                    L.vp(off), C.c_size_t(len(ls)), L.vp(lo), L.vp(ids), L.vp(sc), L.vp(cnt)))
+        return ids, sc, cnt
+
+    def IdsBatchStats(self):
+        a, b, p = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.check(L.lib().coltt_flat_ids_batch_stats(self.h, C.byref(a), C.byref(b), C.byref(p)))
+        return {"one_pass_calls": a.value, "fallback_calls": b.value, "pairs": p.value}
+
     # -- SaveVertex / LoadVertex (edge/none_vectorstore.go:308-516)
     def SaveVertex(self):
         n = C.c_uint64(0)

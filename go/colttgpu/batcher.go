@@ -27,6 +27,7 @@ type Batcher struct {
 	dim      int
 	backend  Backend
 	fbackend FilteredBackend // set by NewFilteredBatcher: the filtered mode
+	ibackend IdsBackend      // set by NewIdsBatcher: the ids mode
 	MaxBatch int
 	MaxWait  time.Duration
 	in       chan *pending
@@ -37,7 +38,8 @@ type Batcher struct {
 type pending struct {
 	q      []float32
 	k      uint32
-	filter Handle // filtered mode: the caller's filter
+	filter Handle   // filtered mode: the caller's filter
+	cand   []uint64 // ids mode: the caller's candidate ids
 	done   chan batchResult
 }
 type batchResult struct {
@@ -105,12 +107,42 @@ func NewFilteredBatcher(dim int, backend FilteredBackend, maxBatch int, maxWait 
 	return b
 }
 
+// Ids mode (same semantics as coltt::IdsBatcher in include/coltt_batcher.hpp): every caller brings its own candidate id list — the
+// reference's FilterableVertexSearch RPC, whose filter expression the inverted index has turned into ids (edge/none_vectorstore.go:182-253).
+// Batches are grouped by k only; lists[i] belongs to query i.  A batch the backend refuses as a whole is re-issued one query at a time.
+type IdsBackend func(lists [][]uint64, queries []float32, nq int, k uint32) (ids []uint64, scores []float32, counts []uint32, err error)
+
+// FlatIdsBackend: FlatSearchIdsBatch on a FLAT store; every caller gets the answer of its own filtered FlatSearch call.
+func FlatIdsBackend(h Handle, dim uint32, sel int) IdsBackend {
+	return func(lists [][]uint64, q []float32, nq int, k uint32) ([]uint64, []float32, []uint32, error) {
+		return FlatSearchIdsBatch(h, dim, q, nq, k, sel, lists, nil)
+	}
+}
+
+func NewIdsBatcher(dim int, backend IdsBackend, maxBatch int, maxWait time.Duration) *Batcher {
+	if maxBatch < 1 {
+		maxBatch = 1
+	}
+	b := &Batcher{dim: dim, ibackend: backend, MaxBatch: maxBatch, MaxWait: maxWait, in: make(chan *pending, 4*maxBatch),
+		quit: make(chan struct{})}
+	go b.loop()
+	return b
+}
+
+// SearchIds (ids mode) blocks until the batch this query rode in has been answered.  The ids are copied before they are queued.
+func (b *Batcher) SearchIds(q []float32, k uint, cand []uint64) ([]BatchItem, error) {
+	if b.ibackend == nil {
+		return nil, fmt.Errorf("SearchIds: not an ids batcher (NewIdsBatcher)")
+	}
+	return b.search(q, k, 0, append([]uint64(nil), cand...))
+}
+
 // SearchFiltered (filtered mode) blocks until the batch this query rode in has been answered.
 func (b *Batcher) SearchFiltered(q []float32, k uint, filter Handle) ([]BatchItem, error) {
 	if b.fbackend == nil {
 		return nil, fmt.Errorf("SearchFiltered: not a filtered batcher (NewFilteredBatcher)")
 	}
-	return b.search(q, k, filter)
+	return b.search(q, k, filter, nil)
 }
 
 // Search blocks until the batch this query rode in has been answered.  The query is copied before it is queued.
@@ -118,17 +150,20 @@ func (b *Batcher) Search(q []float32, k uint) ([]BatchItem, error) {
 	if b.fbackend != nil {
 		return nil, fmt.Errorf("Search: a filtered batcher takes SearchFiltered")
 	}
-	return b.search(q, k, 0)
+	if b.ibackend != nil {
+		return nil, fmt.Errorf("Search: an ids batcher takes SearchIds")
+	}
+	return b.search(q, k, 0, nil)
 }
 
-func (b *Batcher) search(q []float32, k uint, filter Handle) ([]BatchItem, error) {
+func (b *Batcher) search(q []float32, k uint, filter Handle, cand []uint64) ([]BatchItem, error) {
 	if len(q) != b.dim {
 		return nil, fmt.Errorf("Dim Length UnmatchdError: expect dimension: [%d], but got [%d]", b.dim, len(q))
 	}
 	if k == 0 {
 		return []BatchItem{}, nil
 	}
-	p := &pending{q: append([]float32(nil), q...), k: uint32(k), filter: filter, done: make(chan batchResult, 1)}
+	p := &pending{q: append([]float32(nil), q...), k: uint32(k), filter: filter, cand: cand, done: make(chan batchResult, 1)}
 	select {
 	case b.in <- p:
 	case <-b.quit:
@@ -216,6 +251,10 @@ func (b *Batcher) flush(batch []*pending) {
 			b.flushFiltered(grp, flat, k)
 			continue
 		}
+		if b.ibackend != nil {
+			b.flushIds(grp, flat, k)
+			continue
+		}
 		ids, sc, cnt, err := b.backend(flat, nq, k)
 		for i, p := range grp {
 			if err != nil {
@@ -259,6 +298,33 @@ func (b *Batcher) flushFiltered(grp []*pending, flat []float32, k uint32) {
 	}
 	for i, p := range grp {
 		ids1, sc1, cnt1, err1 := b.fbackend(fh[i:i+1], flat[i*b.dim:(i+1)*b.dim], 1, k)
+		if err1 != nil {
+			p.done <- batchResult{nil, err1}
+			continue
+		}
+		p.done <- batchResult{rows(ids1, sc1, cnt1[0], k, 0), nil}
+	}
+}
+
+// flushIds: one backend call for the group, a list per query; if it fails as a whole, one call per query (each caller gets its own call's result)
+func (b *Batcher) flushIds(grp []*pending, flat []float32, k uint32) {
+	lists := make([][]uint64, len(grp))
+	for i, p := range grp {
+		lists[i] = p.cand
+	}
+	ids, sc, cnt, err := b.ibackend(lists, flat, len(grp), k)
+	if err == nil || len(grp) == 1 {
+		for i, p := range grp {
+			if err != nil {
+				p.done <- batchResult{nil, err}
+				continue
+			}
+			p.done <- batchResult{rows(ids, sc, cnt[i], k, i), nil}
+		}
+		return
+	}
+	for i, p := range grp {
+		ids1, sc1, cnt1, err1 := b.ibackend(lists[i:i+1], flat[i*b.dim:(i+1)*b.dim], 1, k)
 		if err1 != nil {
 			p.done <- batchResult{nil, err1}
 			continue

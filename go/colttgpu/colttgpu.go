@@ -427,6 +427,52 @@ func FlatSearch(h Handle, dim uint32, queries []float32, nq int, k uint32, sel, 
 	return ids, sc, cnt, err
 }
 
+// FlatSearchIdsBatch: a batch of FilterableVertexSearch RPCs in one call (coltt_flat_search_ids_batch), every query with its own candidate
+// list: query i is searched over lists[listOf[i]] (listOf == nil: over lists[i], len(lists) == nq).  Row i equals FlatSearch(h, dim,
+// query i, 1, k, sel, ModeExact, that list, true).  Exact-order arithmetic; the lists are translated to rows once per list.
+func FlatSearchIdsBatch(h Handle, dim uint32, queries []float32, nq int, k uint32, sel int, lists [][]uint64, listOf []uint32) ([]uint64, []float32, []uint32, error) {
+	if nq == 0 || k == 0 {
+		return nil, nil, make([]uint32, nq), nil
+	}
+	if err := checkDim(queries, dim, nq); err != nil {
+		return nil, nil, nil, err
+	}
+	if listOf != nil && len(listOf) != nq {
+		return nil, nil, nil, fmt.Errorf("FlatSearchIdsBatch: %d list indices for %d queries", len(listOf), nq)
+	}
+	off := make([]uint64, len(lists)+1)
+	total := 0
+	for l, c := range lists {
+		total += len(c)
+		off[l+1] = uint64(total)
+	}
+	cand := make([]uint64, 0, total) // the library copies inputs before returning: no Go pointer is retained
+	for _, c := range lists {
+		cand = append(cand, c...)
+	}
+	ids := make([]uint64, nq*int(k))
+	sc := make([]float32, nq*int(k))
+	cnt := make([]uint32, nq)
+	cp := (*C.uint32_t)(unsafe.Pointer(&cnt[0]))
+	var lp *C.uint32_t
+	if listOf != nil {
+		lp = (*C.uint32_t)(unsafe.Pointer(&listOf[0]))
+	}
+	err := call(func() C.int {
+		return C.coltt_flat_search_ids_batch(h, fptr(queries), C.size_t(nq), C.uint32_t(k), C.int(sel), uptr(cand), uptr(off), C.size_t(len(lists)), lp,
+			uptr(ids), fptr(sc), cp)
+	})
+	return ids, sc, cnt, err
+}
+
+// FlatIdsBatchStats: FlatSearchIdsBatch calls served by the one-pass path and by the k > 64 path, and the (query, row) pairs the one-pass
+// path scored (coltt_flat_ids_batch_stats).
+func FlatIdsBatchStats(h Handle) (onePass, fallback, pairs uint64, err error) {
+	var a, b, p C.uint64_t
+	err = call(func() C.int { return C.coltt_flat_ids_batch_stats(h, &a, &b, &p) })
+	return uint64(a), uint64(b), uint64(p), err
+}
+
 // FlatSaveVertex / FlatLoadVertex: the edge `.vertex` stream (none_vectorstore.go:308-516 and the f16/f8/bf16 twins).
 // FlatOneLaunchSearches: how many searches of <= 4 queries the one-launch kernel served (coltt_flat_one_launch_searches) —
 // a diagnostic for dashboards: the RPC path of the reference issues exactly this shape (edge/edge.go:610-690).

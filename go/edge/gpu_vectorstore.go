@@ -40,6 +40,9 @@ type gpuVecSpace struct {
 	Select int
 	// ModeExact = reference AVX summation order (bit-identical scores); ModeMFMA = matrix-core candidates + exact re-score
 	Mode int
+	// IdsBatcher (optional; colttgpu.NewIdsBatcher over colttgpu.FlatIdsBackend(h, dim, Select)): when set, FilterableVertexSearch
+	// RPCs ride in shared coltt_flat_search_ids_batch calls, each with its own candidate list, instead of one call each
+	IdsBatcher *colttgpu.Batcher
 }
 
 func newGpuVectorstore(collectionName string, metadata Metadata) *gpuVecSpace {
@@ -203,6 +206,18 @@ func (s *gpuVecSpace) FilterableVertexSearch(filter *inverted.FilterExpression, 
 	}
 	if topK <= 0 {
 		return []*SearchResultItem{}, nil
+	}
+	if s.IdsBatcher != nil {
+		items, err := s.IdsBatcher.SearchIds(target, uint(topK), candidates)
+		if err != nil {
+			return nil, err
+		}
+		ids := make([]uint64, len(items))
+		sc := make([]float32, len(items))
+		for i, it := range items {
+			ids[i], sc[i] = it.Id, it.Score
+		}
+		return s.results(ids, sc, len(items)), nil
 	}
 	ids, sc, cnt, err := colttgpu.FlatSearch(s.h, s.Dim(), target, 1, uint32(topK), s.Select, colttgpu.ModeExact, candidates, true)
 	if err != nil {

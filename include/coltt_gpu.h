@@ -131,6 +131,39 @@ int coltt_flat_search_ids(coltt_handle_t h, const float* queries, size_t nq, uin
 int coltt_flat_search_ids_mode(coltt_handle_t h, const float* queries, size_t nq, uint32_t k, int select, int mode,
                                const uint64_t* cand_ids, size_t n_cand,
                                uint64_t* out_ids, float* out_scores, uint32_t* out_counts);
+/* FilterableVertexSearch for a batch of queries with a candidate list EACH — the reference serves one filtered query per RPC, every
+ * RPC with its own filter expression and therefore its own id list (edge/none_vectorstore.go:182-253; pkg/inverted/search.go:113-119).
+ * List l is cand_ids[list_offsets[l] .. list_offsets[l+1]); query i is searched over list list_of[i] (list_of == NULL requires
+ * n_lists == nq: query i uses list i).  Several queries may name one list; a list nobody names is ignored.  Row i of the outputs
+ * ([nq][k] / [nq]) EQUALS coltt_flat_search_ids(h, query i, 1, k, select, its list, its length, ...) on the same store state: the same
+ * count (min(k, live distinct candidates)), the same ids ascending by (score, id), the same f32 score bits; entries past the count are
+ * unspecified.  Ids that are not stored are skipped, an id repeated inside a list is scored once, an empty list gives count 0 (the
+ * other rows are served), an empty store gives all counts 0, nq == 0 is not an error.
+ * Errors — all checked before anything runs, no output is written: COLTT_E_NOT_FOUND unknown handle; COLTT_E_INVALID for NULL queries /
+ * outputs / list_offsets with nq > 0, NULL cand_ids while the lists are not all empty, list_offsets that decrease, list_of == NULL with
+ * n_lists != nq, a list_of[i] >= n_lists (coltt_last_error names the first such i), a bad select; COLTT_E_UNSUPPORTED for k == 0 or
+ * k > 2048, as coltt_flat_search answers.
+ * Host pointers only.  The call holds the store's lock shared for its whole duration: coltt_flat_remove moves the last row into the
+ * hole, so a row's position is stable only under the lock — which is also why there is no reusable FLAT filter handle: the lists are
+ * translated per call, once per list (not once per query).  Exact-order arithmetic only (queries with different row sets share no
+ * GEMM).  k <= 64: one translation, one upload, ONE scan launch over ragged (query group, list chunk) tiles and one selection launch
+ * for the whole batch; larger k: the same answers list by list through the shared-list path, still in this one call. */
+int coltt_flat_search_ids_batch(coltt_handle_t h, const float* queries, size_t nq, uint32_t k, int select,
+                                const uint64_t* cand_ids, const uint64_t* list_offsets /*[n_lists + 1]*/, size_t n_lists,
+                                const uint32_t* list_of /*[nq], or NULL when n_lists == nq*/,
+                                uint64_t* out_ids, float* out_scores, uint32_t* out_counts);
+/* coltt_flat_search_ids_batch calls served by the one-pass path and by the k > 64 path since creation, and the (query, row) pairs the
+ * one-pass path scored (the sum over its queries of their live distinct candidates); any output may be NULL */
+int coltt_flat_ids_batch_stats(coltt_handle_t h, uint64_t* out_one_pass_calls, uint64_t* out_fallback_calls, uint64_t* out_pairs);
+/* Host only, no device: the tile plan the one-pass path launches for lists of list_lens[l] rows (after translation), the same code
+ * the search calls — for tests.  Queries are ordered by list (out_query_order[nq]: entry -> query, stable) and cut into groups of at
+ * most queries_per_tile that share a list; every list is cut into chunks of chunk_rows (a positive multiple of 32).  A tile is
+ * {list, s0, s1, first query entry, number of queries}: rows [s0, s1) of the list against out_query_order[first .. first + number).
+ * A list of length 0 has no tile.  *out_n_tiles is the number of tiles of the plan; at most cap are written, and a plan that does not
+ * fit is COLTT_E_INVALID (with *out_n_tiles set, so the caller can size the buffer). */
+int coltt_flat_ids_plan_host(const uint64_t* list_lens /*[n_lists]*/, size_t n_lists, const uint32_t* list_of /*[nq] or NULL*/, size_t nq,
+                             uint32_t chunk_rows, uint32_t queries_per_tile, uint32_t* out_tiles /*[cap][5]*/,
+                             uint32_t* out_query_order /*[nq]*/, uint64_t cap, uint64_t* out_n_tiles);
 
 /* SaveVertex / LoadVertex (edge/none_vectorstore.go:308-516; f16_vectorstore.go:317-532 and the f8/bf16 twins): 16 shards
  * x {u64 count, count x {u64 key, u32 vecLen, vecLen x big-endian STORED code (f32 | u16 | u8), u32 metaCount, typed

@@ -86,6 +86,30 @@ class VecSpace {
     for (uint32_t i = 0; i < n; i++) r[i] = {ids[i], sc[i]};
     return r;
   }
+  // a batch of FilterableVertexSearch RPCs in one call, every target with its own candidate list (coltt_flat_search_ids_batch): result i
+  // equals FilterableVertexSearch(candidates[list_of[i]], targets[i], topK, select); an empty list_of means target i uses candidates[i]
+  std::vector<SearchResult> FilterableVertexSearchBatch(const std::vector<std::vector<uint64_t>>& candidates, const std::vector<Vector>& targets,
+                                                        int topK, int select = COLTT_SELECT_REFERENCE, const std::vector<uint32_t>& list_of = {}) const {
+    const size_t nq = targets.size();
+    std::vector<float> q(nq * dim_);
+    for (size_t i = 0; i < nq; i++) {
+      if (targets[i].size() != dim_) throw Error(COLTT_E_INVALID, "FilterableVertexSearchBatch: a target's length differs from the store's dimension");
+      std::copy(targets[i].begin(), targets[i].end(), q.begin() + i * dim_);
+    }
+    if (!list_of.empty() && list_of.size() != nq) throw Error(COLTT_E_INVALID, "FilterableVertexSearchBatch: list_of needs one entry per target");
+    std::vector<uint64_t> off(candidates.size() + 1, 0), cand;
+    for (size_t l = 0; l < candidates.size(); l++) { cand.insert(cand.end(), candidates[l].begin(), candidates[l].end()); off[l + 1] = cand.size(); }
+    const size_t kk = topK > 0 ? (size_t)topK : 1;
+    std::vector<uint64_t> ids(nq * kk); std::vector<float> sc(nq * kk); std::vector<uint32_t> n(nq, 0);
+    check(coltt_flat_search_ids_batch(h_, q.data(), nq, (uint32_t)topK, select, cand.data(), off.data(), candidates.size(),
+                                      list_of.empty() ? nullptr : list_of.data(), ids.data(), sc.data(), n.data()));
+    std::vector<SearchResult> out(nq);
+    for (size_t i = 0; i < nq; i++) {
+      out[i].resize(n[i]);
+      for (uint32_t j = 0; j < n[i]; j++) out[i][j] = {ids[i * kk + j], sc[i * kk + j]};
+    }
+    return out;
+  }
   // SaveVertex / LoadVertex (none_vectorstore.go:308-516 and twins): the `.vertex` byte stream, metadata written as empty maps
   std::vector<uint8_t> SaveVertex() const {
     uint64_t n = 0;
