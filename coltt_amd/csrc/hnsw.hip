@@ -23,6 +23,7 @@
 #include "prep.hpp"
 
 #include "hnsw_kernels.hpp"   // the search kernels (one-wave walk, large-ef walk, latency kernel, walk over PQ codes + re-rank)
+#include "filter_expr.hpp"    // filter expressions: evaluate, compact, read-back
 
 using namespace coltt;
 using namespace coltt::dev;
@@ -2645,13 +2646,24 @@ int coltt_last_kernel_ms(coltt_handle_t h, float* out_ms) {
 // An extension the reference does not have (its Core.HybridSearch post-filters an unfiltered search): definitions in include/coltt_gpu.h.
 namespace {
 
+// The two device allocations the outputs of one coltt_hnsw_filter_eval(_batch) call share (filter_expr.hpp): freed when the last output goes.
+struct FilterSlab {
+  int device = 0;
+  DevBuf bits, lists;
+  ~FilterSlab() { (void)hipSetDevice(device); }
+};
+
 struct HnswFilter : Object {
   coltt_handle_t index = 0; uint64_t gen = 0;   // built against this index at this generation (Hnsw::gen)
   uint32_t slots = 0;                           // the index's slots when the filter was built: the bitmap covers [0, slots)
   uint64_t allowed = 0;
   DevBuf bits;   // [ceil(slots / 32)] u32, bit s = slot s allowed
   DevBuf list;   // [allowed] u32, the allowed slots ascending (the exact path's gather list)
-  ~HnswFilter() override { (void)hipSetDevice(device); }
+  std::shared_ptr<FilterSlab> slab;   // set: bits and list point into the slab and are not this filter's to free
+  ~HnswFilter() override {
+    (void)hipSetDevice(device);
+    if (slab) { bits.p = nullptr; list.p = nullptr; }
+  }
 };
 
 // AUTO: with A allowed vertices out of n_live, a walk at ef meets about ef * A / n_live allowed ones among its result-set-sized share of
@@ -3220,6 +3232,119 @@ int pq_filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl,
   st->n_dist = h_stats[0]; st->n_exp = h_stats[1]; st->n_hops = h_stats[2]; st->n_visit_resets = 0; st->n_exact_rows = h_stats[3] + h_stats[5];
   return COLTT_OK;
 }
+
+// coltt_hnsw_filter_eval / _eval_batch (definitions: include/coltt_gpu.h, "Filter expressions"; kernels: filter_expr.hpp).  n_out programmes
+// over one leaf table under one index state: one upload (leaf table, programme offsets, programmes), the evaluate launch, the counts back
+// (they size the lists), the list offsets up, the compact launch.  The outputs' bitmaps and lists are slices of one slab each.
+int filter_eval_common(coltt_handle_t h, const char* who, const int32_t* progs, const uint64_t* prog_off, size_t n_out,
+                       const coltt_handle_t* leaves, size_t n_leaves, uint64_t* out_allowed, coltt_handle_t* out) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "%s: unknown index handle", who);
+  if (n_out == 0) return COLTT_OK;
+  if (!out) return fail(COLTT_E_INVALID, "%s: out is NULL", who);
+  if (!prog_off) return fail(COLTT_E_INVALID, "%s: NULL programme offsets", who);
+  if (n_leaves && !leaves) return fail(COLTT_E_INVALID, "%s: NULL leaves", who);
+  uint64_t total = 0;
+  for (size_t i = 0; i < n_out; i++) {   // every programme is checked before anything is created
+    if (prog_off[i + 1] < prog_off[i]) return fail(COLTT_E_INVALID, "%s: programme %zu: its offsets descend", who, i);
+    const uint64_t len = prog_off[i + 1] - prog_off[i];
+    const int rc = coltt_hnsw_filter_prog_check_host(progs ? progs + prog_off[i] : nullptr, (size_t)len, n_leaves, nullptr);
+    if (rc != COLTT_OK) {
+      const std::string why = coltt_last_error();
+      return fail(rc, "%s: programme %zu: %s", who, i, why.c_str());
+    }
+    total += len;
+  }
+  ReadLock g(x->rw);
+  std::unordered_map<coltt_handle_t, std::shared_ptr<HnswFilter>> held;   // each distinct leaf, until the call returns (a concurrent destroy only unregisters it)
+  std::vector<HnswFilter*> lf(n_leaves);
+  for (size_t i = 0; i < n_leaves; i++) {
+    auto it = held.find(leaves[i]);
+    if (it == held.end()) {
+      auto f = lookup<HnswFilter>(leaves[i]);
+      if (!f) return fail(COLTT_E_NOT_FOUND, "%s: unknown filter handle at leaf %zu", who, i);
+      if (f->index != h) return fail(COLTT_E_INVALID, "%s: the filter at leaf %zu was built for another index", who, i);
+      if (f->gen != x->gen) return fail(COLTT_E_INVALID, "%s: the filter at leaf %zu is stale (the index was loaded since it was built)", who, i);
+      it = held.emplace(leaves[i], std::move(f)).first;
+    }
+    lf[i] = it->second.get();
+  }
+  COLTT_DEVICE(x->device);
+  const uint32_t n_slots = (uint32_t)x->n, n_words = (n_slots + 31) / 32, n_wg = ceil_div(n_words, FEX_TILE_WORDS);
+  if ((uint64_t)n_out * std::max(1u, n_wg) > 0x7fffffffull || total > 0xffffffffull)
+    return fail(COLTT_E_UNSUPPORTED, "%s: %zu programmes over %u slots exceed one launch", who, n_out, n_slots);
+  std::vector<std::shared_ptr<HnswFilter>> res(n_out);
+  for (auto& f : res) {
+    f = std::make_shared<HnswFilter>();
+    f->device = x->device; f->index = h; f->gen = x->gen; f->slots = n_slots;
+  }
+  if (n_words) {
+    CtxLease<HCtx> ctx(x->pool);
+    if (!ctx.c) return COLTT_E_DEVICE;
+    HCtx* c = ctx.c;
+    auto slab = std::make_shared<FilterSlab>();
+    slab->device = x->device;
+    const size_t stride = ((size_t)n_words + 63) & ~(size_t)63;   // words per output bitmap: 256-byte slices
+    COLTT_TRY(slab->bits.reserve(n_out * stride * 4));
+    // one upload: [leaf table][list offsets, filled later][programme offsets][programmes]
+    const size_t o_loff = n_leaves * sizeof(FexLeaf), o_poff = o_loff + n_out * 8, o_prog = o_poff + (n_out + 1) * 4, bytes = o_prog + (size_t)total * 4;
+    COLTT_TRY(c->h_in.reserve(bytes));
+    COLTT_TRY(c->w_fdesc.reserve(bytes));
+    COLTT_TRY(c->w_scnt.reserve(n_out * (size_t)n_wg * 4));
+    COLTT_TRY(c->h_out.reserve(n_out * (size_t)n_wg * 4));
+    uint8_t* hb = static_cast<uint8_t*>(c->h_in.p);
+    FexLeaf* h_leaf = reinterpret_cast<FexLeaf*>(hb);
+    uint64_t* h_loff = reinterpret_cast<uint64_t*>(hb + o_loff);
+    uint32_t* h_poff = reinterpret_cast<uint32_t*>(hb + o_poff);
+    int32_t* h_prog = reinterpret_cast<int32_t*>(hb + o_prog);
+    for (size_t i = 0; i < n_leaves; i++) h_leaf[i] = FexLeaf{lf[i]->bits.as<uint32_t>(), std::min((lf[i]->slots + 31) / 32, n_words), 0u};
+    uint32_t at = 0;
+    for (size_t i = 0; i < n_out; i++) {
+      h_loff[i] = 0; h_poff[i] = at;
+      const size_t len = (size_t)(prog_off[i + 1] - prog_off[i]);
+      std::memcpy(h_prog + at, progs + prog_off[i], len * 4);
+      at += (uint32_t)len;
+    }
+    h_poff[n_out] = at;
+    uint8_t* db = c->w_fdesc.as<uint8_t>();
+    COLTT_HIP(hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, c->stream));
+    const uint32_t grid = (uint32_t)(n_out * n_wg);
+    filter_eval_kernel<<<grid, FEX_THREADS, 0, c->stream>>>(reinterpret_cast<const FexLeaf*>(db), reinterpret_cast<const uint32_t*>(db + o_poff),
+                                                            reinterpret_cast<const int32_t*>(db + o_prog), x->any_deleted ? x->del_bits.as<uint32_t>() : nullptr,
+                                                            n_slots, n_words, n_wg, slab->bits.as<uint32_t>(), stride, c->w_scnt.as<uint32_t>());
+    COLTT_HIP(hipGetLastError());
+    COLTT_HIP(hipMemcpyAsync(c->h_out.p, c->w_scnt.p, n_out * (size_t)n_wg * 4, hipMemcpyDeviceToHost, c->stream));
+    COLTT_HIP(hipStreamSynchronize(c->stream));
+    const uint32_t* h_cnt = static_cast<const uint32_t*>(c->h_out.p);
+    uint64_t entries = 0;   // the lists: 256-byte slices of the second slab
+    for (size_t i = 0; i < n_out; i++) {
+      uint64_t a = 0;
+      for (uint32_t t = 0; t < n_wg; t++) a += h_cnt[i * n_wg + t];
+      res[i]->allowed = a;
+      h_loff[i] = entries;
+      entries += (a + 63) & ~63ull;
+    }
+    if (entries) {
+      COLTT_TRY(slab->lists.reserve((size_t)entries * 4));
+      COLTT_HIP(hipMemcpyAsync(db + o_loff, h_loff, n_out * 8, hipMemcpyHostToDevice, c->stream));
+      filter_compact_kernel<<<grid, FEX_THREADS, 0, c->stream>>>(slab->bits.as<uint32_t>(), stride, n_words, n_wg, c->w_scnt.as<uint32_t>(),
+                                                                 reinterpret_cast<const uint64_t*>(db + o_loff), slab->lists.as<uint32_t>());
+      COLTT_HIP(hipGetLastError());
+      COLTT_HIP(hipStreamSynchronize(c->stream));   // the outputs are read on other streams from here on
+    }
+    for (size_t i = 0; i < n_out; i++) {
+      HnswFilter* f = res[i].get();
+      f->slab = slab;
+      f->bits.p = slab->bits.as<uint32_t>() + i * stride; f->bits.cap = (size_t)n_words * 4;
+      if (f->allowed) { f->list.p = slab->lists.as<uint32_t>() + h_loff[i]; f->list.cap = (size_t)f->allowed * 4; }
+    }
+  }
+  for (size_t i = 0; i < n_out; i++) {
+    if (out_allowed) out_allowed[i] = res[i]->allowed;
+    out[i] = Registry::get().add(res[i]);
+  }
+  return COLTT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3268,6 +3393,58 @@ int coltt_hnsw_filter_create(coltt_handle_t h, const uint64_t* ids, size_t n, ui
 int coltt_hnsw_filter_destroy(coltt_handle_t fh) {
   if (!lookup<HnswFilter>(fh)) return fail(COLTT_E_NOT_FOUND, "hnsw_filter_destroy: unknown filter handle");
   Registry::get().erase(fh);
+  return COLTT_OK;
+}
+
+int coltt_hnsw_filter_prog_check_host(const int32_t* prog, size_t n_prog, size_t n_leaves, uint32_t* out_depth) {
+  size_t pos = 0; const char* why = "";
+  const int rc = fex_prog_check(prog, n_prog, n_leaves, out_depth, &pos, &why);
+  if (rc != COLTT_OK) return fail(rc, "filter programme: %s at position %zu", why, pos);
+  return COLTT_OK;
+}
+
+int coltt_hnsw_filter_eval(coltt_handle_t h, const int32_t* prog, size_t n_prog, const coltt_handle_t* leaves, size_t n_leaves,
+                           uint64_t* out_allowed, coltt_handle_t* out) {
+  if (!out) return fail(COLTT_E_INVALID, "hnsw_filter_eval: out is NULL");
+  const uint64_t off[2] = {0, (uint64_t)n_prog};
+  return filter_eval_common(h, "hnsw_filter_eval", prog, off, 1, leaves, n_leaves, out_allowed, out);
+}
+
+int coltt_hnsw_filter_eval_batch(coltt_handle_t h, const int32_t* progs, const uint64_t* prog_off, size_t n_out, const coltt_handle_t* leaves,
+                                 size_t n_leaves, uint64_t* out_allowed, coltt_handle_t* out) {
+  return filter_eval_common(h, "hnsw_filter_eval_batch", progs, prog_off, n_out, leaves, n_leaves, out_allowed, out);
+}
+
+int coltt_hnsw_filter_info(coltt_handle_t fh, coltt_handle_t* out_index, uint64_t* out_allowed, uint64_t* out_slots) {
+  auto f = lookup<HnswFilter>(fh);
+  if (!f) return fail(COLTT_E_NOT_FOUND, "hnsw_filter_info: unknown filter handle");
+  if (out_index) *out_index = f->index;
+  if (out_allowed) *out_allowed = f->allowed;
+  if (out_slots) *out_slots = f->slots;
+  return COLTT_OK;
+}
+
+int coltt_hnsw_filter_ids(coltt_handle_t fh, uint64_t* out_ids, uint64_t cap, uint64_t* out_n) {
+  auto f = lookup<HnswFilter>(fh);   // held until the call returns
+  if (!f) return fail(COLTT_E_NOT_FOUND, "hnsw_filter_ids: unknown filter handle");
+  if (cap && !out_ids) return fail(COLTT_E_INVALID, "hnsw_filter_ids: NULL out_ids");
+  auto x = lookup<Hnsw>(f->index);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_filter_ids: the filter's index is gone");
+  ReadLock g(x->rw);
+  if (f->gen != x->gen) return fail(COLTT_E_INVALID, "hnsw_filter_ids: the filter is stale (the index was loaded since it was built)");
+  if (out_n) *out_n = f->allowed;
+  const uint64_t m = std::min<uint64_t>(cap, f->allowed);
+  if (m == 0) return COLTT_OK;
+  COLTT_DEVICE(x->device);
+  CtxLease<HCtx> ctx(x->pool);
+  if (!ctx.c) return COLTT_E_DEVICE;
+  HCtx* c = ctx.c;
+  COLTT_TRY(c->w_out_ids.reserve(m * 8));
+  filter_ids_kernel<<<ceil_div(m, 256), 256, 0, c->stream>>>(f->list.as<uint32_t>(), m, x->dense ? nullptr : x->ids.as<uint64_t>(), x->dense_base,
+                                                             c->w_out_ids.as<uint64_t>());
+  COLTT_HIP(hipGetLastError());
+  COLTT_HIP(hipMemcpyAsync(out_ids, c->w_out_ids.p, m * 8, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipStreamSynchronize(c->stream));
   return COLTT_OK;
 }
 

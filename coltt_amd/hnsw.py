@@ -32,6 +32,83 @@ class HnswFilterStats(C.Structure):
                 ("ef_walk", C.c_uint32), ("path", C.c_int32), ("n_exact_rows", C.c_uint64)]
 
 
+# filter expressions (coltt_hnsw_filter_eval; include/coltt_gpu.h, "Filter expressions"): the operators of a postfix programme
+FOP_AND, FOP_OR, FOP_ANDNOT, FOP_NOT, FOP_ALL = -1, -2, -3, -4, -5
+_FOP_BY_NAME = {"and": FOP_AND, "or": FOP_OR, "andnot": FOP_ANDNOT, "not": FOP_NOT, "all": FOP_ALL}
+_FOP_ARITY = {FOP_AND: 2, FOP_OR: 2, FOP_ANDNOT: 2, FOP_NOT: 1, FOP_ALL: 0}
+
+
+def filter_postfix(tree):
+    """A nested expression -> the postfix programme of coltt_hnsw_filter_eval.  A node is a leaf index (int >= 0), the string "all", or a
+    tuple (op, operand, ...) with op one of "and", "or", "andnot", "not"; "and" / "or" take two or more operands and fold from the left
+    (the shape of evaluateCompositeFilter, pkg/inverted/search.go:50-77), "andnot" takes two, "not" one."""
+    out = []
+
+    def walk(t):
+        if isinstance(t, (int, np.integer)) and not isinstance(t, bool):
+            if t < 0:
+                raise ValueError(f"filter_postfix: leaf index {t}")
+            out.append(int(t))
+            return
+        if isinstance(t, str):
+            t = (t,)
+        if not isinstance(t, tuple) or not t or not isinstance(t[0], str) or t[0].lower() not in _FOP_BY_NAME:
+            raise ValueError(f"filter_postfix: not an expression: {t!r}")
+        op = _FOP_BY_NAME[t[0].lower()]
+        args = t[1:]
+        ar = _FOP_ARITY[op]
+        if (op in (FOP_AND, FOP_OR) and len(args) < 2) or (op not in (FOP_AND, FOP_OR) and len(args) != ar):
+            raise ValueError(f"filter_postfix: {t[0]!r} with {len(args)} operands")
+        if ar == 0:
+            out.append(op)
+            return
+        walk(args[0])
+        if ar == 1:
+            out.append(op)
+        for a in args[1:]:
+            walk(a)
+            out.append(op)
+
+    walk(tree)
+    return out
+
+
+def filter_tree(prog):
+    """The inverse of filter_postfix for a well-formed programme: nested binary tuples."""
+    names = {v: k for k, v in _FOP_BY_NAME.items()}
+    st = []
+    for v in prog:
+        v = int(v)
+        if v >= 0:
+            st.append(v)
+        elif v == FOP_ALL:
+            st.append("all")
+        elif v == FOP_NOT:
+            st.append(("not", st.pop()))
+        elif v in names:
+            b = st.pop(); a = st.pop()
+            st.append((names[v], a, b))
+        else:
+            raise ValueError(f"filter_tree: unknown operator {v}")
+    if len(st) != 1:
+        raise ValueError("filter_tree: the programme does not leave exactly one value")
+    return st[0]
+
+
+def filter_prog_check(prog, n_leaves):
+    """coltt_hnsw_filter_prog_check_host (no device): the deepest stack of a well-formed programme; raises ColttError otherwise."""
+    p = np.ascontiguousarray(np.asarray(prog, dtype=np.int32).reshape(-1))
+    d = C.c_uint32(0)
+    L.check(L.lib().coltt_hnsw_filter_prog_check_host(L.vp(p), C.c_size_t(p.size), C.c_size_t(int(n_leaves)), C.byref(d)))
+    return d.value
+
+
+def _prog_array(prog):
+    if isinstance(prog, (tuple, str)):
+        prog = filter_postfix(prog)
+    return np.ascontiguousarray(np.asarray(prog, dtype=np.int32).reshape(-1))
+
+
 class HnswFilter:
     """An allow-list of ids against one index (coltt_hnsw_filter_create; include/coltt_gpu.h, "Filtered HNSW search" — an extension the
     reference does not have).  `.allowed` = the live vertices it allows."""
@@ -41,6 +118,27 @@ class HnswFilter:
         h = C.c_uint64(0); n = C.c_uint64(0)
         L.check(L.lib().coltt_hnsw_filter_create(index.h, L.vp(a), C.c_size_t(a.size), C.byref(n), C.byref(h)))
         self.h, self.allowed = h, n.value
+
+    @classmethod
+    def _from_handle(cls, h, allowed):
+        o = cls.__new__(cls)
+        o.h, o.allowed = C.c_uint64(int(h)), int(allowed)
+        return o
+
+    def info(self):
+        """coltt_hnsw_filter_info: the handle of the index it was built for, its allowed count, the slots it covers"""
+        ix = C.c_uint64(0); a = C.c_uint64(0); s = C.c_uint64(0)
+        L.check(L.lib().coltt_hnsw_filter_info(self.h, C.byref(ix), C.byref(a), C.byref(s)))
+        return {"index": ix.value, "allowed": a.value, "slots": s.value}
+
+    def ids(self, cap=None):
+        """coltt_hnsw_filter_ids: the allowed ids in ascending slot order (the first `cap` of them), gathered on the device"""
+        n = C.c_uint64(0)
+        if cap is None:
+            cap = self.allowed
+        o = np.zeros(int(cap), np.uint64)
+        L.check(L.lib().coltt_hnsw_filter_ids(self.h, L.vp(o), C.c_uint64(int(cap)), C.byref(n)))
+        return o[:min(int(cap), n.value)]
 
     def close(self):
         if getattr(self, "h", None) is not None:
@@ -161,6 +259,30 @@ class Hnsw:
     # -- filtered search (an extension the reference does not have): the k nearest among the ids of `flt`
     def Filter(self, ids):
         return HnswFilter(self, ids)
+
+    def FilterEval(self, prog, leaves):
+        """coltt_hnsw_filter_eval: the filter of a postfix programme (a list of leaf indices / FOP_*; a nested tuple goes through
+        filter_postfix) over resident filters `leaves`, evaluated on the device.  An ordinary HnswFilter."""
+        p = _prog_array(prog)
+        lh = np.array([0 if f.h is None else f.h.value for f in leaves], np.uint64)
+        h = C.c_uint64(0); n = C.c_uint64(0)
+        L.check(L.lib().coltt_hnsw_filter_eval(self.h, L.vp(p), C.c_size_t(p.size), L.vp(lh) if lh.size else None, C.c_size_t(lh.size),
+                                               C.byref(n), C.byref(h)))
+        return HnswFilter._from_handle(h.value, n.value)
+
+    def FilterEvalBatch(self, progs, leaves):
+        """coltt_hnsw_filter_eval_batch: one filter per programme over the shared leaf table, under one index state, in two kernel
+        launches whatever len(progs) is.  Returns a list of HnswFilter."""
+        ps = [_prog_array(p) for p in progs]
+        off = np.zeros(len(ps) + 1, np.uint64)
+        if ps:
+            off[1:] = np.cumsum([p.size for p in ps])
+        flat = np.ascontiguousarray(np.concatenate(ps)) if ps else np.zeros(0, np.int32)
+        lh = np.array([0 if f.h is None else f.h.value for f in leaves], np.uint64)
+        out = np.zeros(max(len(ps), 1), np.uint64); al = np.zeros(max(len(ps), 1), np.uint64)
+        L.check(L.lib().coltt_hnsw_filter_eval_batch(self.h, L.vp(flat), L.vp(off), C.c_size_t(len(ps)), L.vp(lh) if lh.size else None,
+                                                     C.c_size_t(lh.size), L.vp(al), L.vp(out)))
+        return [HnswFilter._from_handle(out[i], al[i]) for i in range(len(ps))]
 
     def SearchFiltered(self, queries, k, flt, ef=0, mode=FILTER_AUTO, with_stats=False):
         q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.dim)

@@ -188,6 +188,101 @@ func HnswFilterDestroy(f Handle) error {
 	return call(func() C.int { return C.coltt_hnsw_filter_destroy(f) })
 }
 
+// Operators of a filter programme (coltt_gpu.h: COLTT_FOP_*).  A programme is postfix: a value >= 0 pushes leaves[value].
+const (
+	FopAnd    int32 = -1 // a b -> a & b
+	FopOr     int32 = -2 // a b -> a | b
+	FopAndNot int32 = -3 // a b -> a & ~b
+	FopNot    int32 = -4 // a   -> live & ~a
+	FopAll    int32 = -5 //     -> live
+)
+
+func hptr(h []Handle) *Handle {
+	if len(h) == 0 {
+		return nil
+	}
+	return &h[0]
+}
+
+// HnswFilterEval: the filter of a postfix programme over resident filters, evaluated on the device (coltt_hnsw_filter_eval).  The result
+// is an ordinary filter: the same as HnswFilterCreate over the ids of { live slots : expr }.  Release it with HnswFilterDestroy.
+func HnswFilterEval(h Handle, prog []int32, leaves []Handle) (Handle, uint64, error) {
+	var f Handle
+	var allowed C.uint64_t
+	err := call(func() C.int {
+		var p *C.int32_t
+		if len(prog) > 0 {
+			p = (*C.int32_t)(unsafe.Pointer(&prog[0]))
+		}
+		return C.coltt_hnsw_filter_eval(h, p, C.size_t(len(prog)), hptr(leaves), C.size_t(len(leaves)), &allowed, &f)
+	})
+	return f, uint64(allowed), err
+}
+
+// HnswFilterEvalBatch: one filter per programme over a shared leaf table, under one index state, in two kernel launches whatever
+// len(progs) is (coltt_hnsw_filter_eval_batch).  Nothing is created if any programme or handle is bad; the error names the first.
+func HnswFilterEvalBatch(h Handle, progs [][]int32, leaves []Handle) ([]Handle, []uint64, error) {
+	n := len(progs)
+	if n == 0 {
+		return nil, nil, nil
+	}
+	off := make([]uint64, n+1)
+	var flat []int32
+	for i, p := range progs {
+		flat = append(flat, p...)
+		off[i+1] = uint64(len(flat))
+	}
+	out := make([]Handle, n)
+	allowed := make([]uint64, n)
+	err := call(func() C.int {
+		var p *C.int32_t
+		if len(flat) > 0 {
+			p = (*C.int32_t)(unsafe.Pointer(&flat[0]))
+		}
+		return C.coltt_hnsw_filter_eval_batch(h, p, (*C.uint64_t)(unsafe.Pointer(&off[0])), C.size_t(n), hptr(leaves), C.size_t(len(leaves)),
+			(*C.uint64_t)(unsafe.Pointer(&allowed[0])), &out[0])
+	})
+	if err != nil {
+		return nil, nil, err
+	}
+	return out, allowed, nil
+}
+
+// HnswFilterIds: the ids filter f allows, in ascending slot order, at most limit of them (coltt_hnsw_filter_ids; gathered on the device).
+// The second result is the filter's allowed count.
+func HnswFilterIds(f Handle, limit uint64) ([]uint64, uint64, error) {
+	var n C.uint64_t
+	ids := make([]uint64, limit)
+	err := call(func() C.int { return C.coltt_hnsw_filter_ids(f, uptr(ids), C.uint64_t(limit), &n) })
+	if err != nil {
+		return nil, 0, err
+	}
+	if uint64(n) < limit {
+		ids = ids[:n]
+	}
+	return ids, uint64(n), nil
+}
+
+// HnswFilterInfo: the index a filter was built for, its allowed count and the slots it covers (coltt_hnsw_filter_info).
+func HnswFilterInfo(f Handle) (index Handle, allowed, slots uint64, err error) {
+	var a, s C.uint64_t
+	err = call(func() C.int { return C.coltt_hnsw_filter_info(f, &index, &a, &s) })
+	return index, uint64(a), uint64(s), err
+}
+
+// FilterProgCheck: the programme rules with no device (coltt_hnsw_filter_prog_check_host); returns the deepest stack.
+func FilterProgCheck(prog []int32, nLeaves int) (uint32, error) {
+	var d C.uint32_t
+	err := call(func() C.int {
+		var p *C.int32_t
+		if len(prog) > 0 {
+			p = (*C.int32_t)(unsafe.Pointer(&prog[0]))
+		}
+		return C.coltt_hnsw_filter_prog_check_host(p, C.size_t(len(prog)), C.size_t(nLeaves), &d)
+	})
+	return uint32(d), err
+}
+
 // Filter modes of HnswSearchFiltered (coltt_gpu.h: COLTT_FILTER_*)
 const (
 	FilterAuto  = 0

@@ -417,6 +417,103 @@ func (f *HnswFilter) Close() error {
 	return err
 }
 
+// FilterExpr — a filter expression over resident filters, the shape of the reference's composite filters (pkg/inverted/search.go:50-77,
+// evaluateCompositeFilter): a leaf is Leaf(i) = the i-th filter of the table given to EvalFilter, inner nodes are And / Or / AndNot / Not,
+// All() is every live vertex.  Postfix() is the programme the library evaluates on the device.
+type FilterExpr struct {
+	op   int32 // >= 0: leaf index; otherwise a colttgpu.Fop*
+	args []FilterExpr
+}
+
+func Leaf(i int) FilterExpr { return FilterExpr{op: int32(i)} }
+func All() FilterExpr       { return FilterExpr{op: colttgpu.FopAll} }
+func Not(a FilterExpr) FilterExpr {
+	return FilterExpr{op: colttgpu.FopNot, args: []FilterExpr{a}}
+}
+func AndNot(a, b FilterExpr) FilterExpr {
+	return FilterExpr{op: colttgpu.FopAndNot, args: []FilterExpr{a, b}}
+}
+
+// And / Or of two or more operands fold from the left, so the stack stays at two values however many terms a request has.
+func And(a, b FilterExpr, more ...FilterExpr) FilterExpr {
+	return FilterExpr{op: colttgpu.FopAnd, args: append([]FilterExpr{a, b}, more...)}
+}
+func Or(a, b FilterExpr, more ...FilterExpr) FilterExpr {
+	return FilterExpr{op: colttgpu.FopOr, args: append([]FilterExpr{a, b}, more...)}
+}
+
+func (e FilterExpr) Postfix() []int32 { return e.postfix(nil) }
+func (e FilterExpr) postfix(out []int32) []int32 {
+	if e.op >= 0 || e.op == colttgpu.FopAll {
+		return append(out, e.op)
+	}
+	out = e.args[0].postfix(out)
+	if e.op == colttgpu.FopNot {
+		return append(out, e.op)
+	}
+	for _, a := range e.args[1:] {
+		out = a.postfix(out)
+		out = append(out, e.op)
+	}
+	return out
+}
+
+// EvalFilter evaluates expr over the resident filters `leaves` on the device (coltt_hnsw_filter_eval).  The result is an ordinary,
+// immutable HnswFilter: exactly NewFilter over the ids of the live vertices the expression allows.  Not and All see vertices inserted
+// after their operands were built; And / Or / AndNot of plain leaves do not.  Refreshing a term ("add these ids, drop those") is
+// EvalFilter(AndNot(Or(Leaf(0), Leaf(1)), Leaf(2)), old, NewFilter(added), NewFilter(dropped)).
+func (xx *Hnsw) EvalFilter(expr FilterExpr, leaves ...*HnswFilter) (*HnswFilter, error) {
+	if xx.err != nil {
+		return nil, xx.err
+	}
+	lh := make([]colttgpu.Handle, len(leaves))
+	for i, l := range leaves {
+		if l == nil {
+			return nil, fmt.Errorf("EvalFilter: no filter at leaf %d", i)
+		}
+		lh[i] = l.h
+	}
+	f, n, err := colttgpu.HnswFilterEval(xx.h, expr.Postfix(), lh)
+	if err != nil {
+		return nil, err
+	}
+	return &HnswFilter{h: f, index: xx, Allowed: n}, nil
+}
+
+// EvalFilters: one filter per expression over a shared leaf table in one call (coltt_hnsw_filter_eval_batch): two kernel launches and
+// two device allocations whatever len(exprs) is.  One bad expression or leaf fails the whole call and nothing is created.
+func (xx *Hnsw) EvalFilters(exprs []FilterExpr, leaves ...*HnswFilter) ([]*HnswFilter, error) {
+	if xx.err != nil {
+		return nil, xx.err
+	}
+	lh := make([]colttgpu.Handle, len(leaves))
+	for i, l := range leaves {
+		if l == nil {
+			return nil, fmt.Errorf("EvalFilters: no filter at leaf %d", i)
+		}
+		lh[i] = l.h
+	}
+	progs := make([][]int32, len(exprs))
+	for i, e := range exprs {
+		progs[i] = e.Postfix()
+	}
+	hs, ns, err := colttgpu.HnswFilterEvalBatch(xx.h, progs, lh)
+	if err != nil {
+		return nil, err
+	}
+	out := make([]*HnswFilter, len(hs))
+	for i := range hs {
+		out[i] = &HnswFilter{h: hs[i], index: xx, Allowed: ns[i]}
+	}
+	return out, nil
+}
+
+// Ids: the ids the filter allows, in ascending slot order (gathered on the device)
+func (f *HnswFilter) Ids() ([]uint64, error) {
+	ids, _, err := colttgpu.HnswFilterIds(f.h, f.Allowed)
+	return ids, err
+}
+
 // SearchFiltered(ctx, query, k, f) — the k nearest among the vertices f allows (the library's AUTO path: a filtered walk, or an exact
 // scan of the allowed rows when the filter is selective).
 func (xx *Hnsw) SearchFiltered(_ context.Context, query edge.Vector, k uint, f *HnswFilter) (SearchResult, error) {

@@ -355,6 +355,45 @@ int coltt_hnsw_pq_search_filtered_batch(coltt_handle_t hnsw, const coltt_handle_
                                         uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                         int32_t* out_paths /*[nq], may be NULL*/, coltt_hnsw_filter_stats* stats);
 
+/* FILTER EXPRESSIONS: AND / OR / NOT over resident filters, evaluated on the device (coltt_hnsw_filter_eval).  The reference's callers hold an
+ * inverted index of per-term bitmaps and combine them per request by an AND / OR tree (pkg/inverted/search.go:26-119: evaluateSingleFilter,
+ * evaluateCompositeFilter, SearchWithExpression); here a term the caller keeps hot is one filter that stays on the device (a LEAF) and a
+ * request's tree is a postfix programme over a table of leaves — no id list crosses the bus and no host loop runs per id.
+ * Programme.  Postfix.  A value v >= 0 pushes leaves[v]; a negative value is one of the operators below.
+ * Definition.  Let n_slots be the index's slot count at the call and live(s) = slot s is not tombstoned at the call.  Leaf L has bit s = its
+ * stored bit when s < L's slot count (the index's when L was built), else 0.  The result allows exactly { s < n_slots : expr(s) and live(s) }
+ * and is an ordinary filter, indistinguishable from coltt_hnsw_filter_create(hnsw, the ids of that set) on the same index state: the same
+ * allowed count, the same bitmap words, the same ascending slot list — so every filtered entry point (the row walk, the walk over the
+ * quantiser's codes, EXACT, AUTO, both _batch calls) gives the same ids, score bits, counts, paths and stats with either.  NOT and ALL
+ * therefore see vertices inserted after their operand was built; AND / OR / ANDNOT of plain leaves do not.
+ * Refresh without a mutable filter: "add these ids, drop those" is the programme  old create(added) OR create(dropped) ANDNOT.  Filters stay
+ * immutable: no call changes a filter another thread is searching with.
+ * coltt_hnsw_filter_eval_batch: output i equals coltt_hnsw_filter_eval of programme i = progs[prog_off[i] .. prog_off[i+1]) over the shared
+ * leaf table, all under one index state (the lock is taken once).  Nothing is created if any programme or handle is bad; coltt_last_error()
+ * names the first bad programme and position.  One call launches two kernels and makes one host round trip (the counts that size the slot
+ * lists) whatever n_out is, and its outputs share two device allocations that are freed when the last of them is destroyed.
+ * coltt_hnsw_filter_ids writes the allowed ids in ascending slot order (as built) into out_ids: min(cap, allowed) of them, *out_n = allowed;
+ * the ids are gathered on the device.  coltt_hnsw_filter_info: the index the filter was built for, its allowed count and the slots it covers.
+ * Errors (the codes of coltt_hnsw_search_filtered where they overlap).  Unknown index or leaf handle: COLTT_E_NOT_FOUND.  A leaf of another
+ * index or a stale leaf, n_prog == 0, stack underflow, a programme that does not end with exactly one value on the stack, a leaf index
+ * >= n_leaves, an unknown operator, NULL out: COLTT_E_INVALID.  Stack depth above 8, n_prog above 4096: COLTT_E_UNSUPPORTED.  Not errors: an
+ * empty index (the result allows nothing), an empty result, a repeated leaf handle, n_out == 0.  coltt_hnsw_filter_prog_check_host applies
+ * exactly the programme rules with no device (*out_depth, may be NULL: the deepest stack); the evaluation calls it.
+ * The evaluation takes the index's lock shared and holds every leaf it reads: destroying one meanwhile is safe.  Host pointers only. */
+#define COLTT_FOP_AND    (-1)   /* a b -> a & b            */
+#define COLTT_FOP_OR     (-2)   /* a b -> a | b            */
+#define COLTT_FOP_ANDNOT (-3)   /* a b -> a & ~b           */
+#define COLTT_FOP_NOT    (-4)   /* a   -> live & ~a        */
+#define COLTT_FOP_ALL    (-5)   /*     -> live             */
+int coltt_hnsw_filter_eval(coltt_handle_t hnsw, const int32_t* prog, size_t n_prog, const coltt_handle_t* leaves, size_t n_leaves,
+                           uint64_t* out_allowed, coltt_handle_t* out);
+int coltt_hnsw_filter_eval_batch(coltt_handle_t hnsw, const int32_t* progs, const uint64_t* prog_off /*[n_out+1]*/, size_t n_out,
+                                 const coltt_handle_t* leaves, size_t n_leaves, uint64_t* out_allowed /*[n_out], may be NULL*/,
+                                 coltt_handle_t* out /*[n_out]*/);
+int coltt_hnsw_filter_ids(coltt_handle_t filter, uint64_t* out_ids, uint64_t cap, uint64_t* out_n);
+int coltt_hnsw_filter_info(coltt_handle_t filter, coltt_handle_t* out_index, uint64_t* out_allowed, uint64_t* out_slots);
+int coltt_hnsw_filter_prog_check_host(const int32_t* prog, size_t n_prog, size_t n_leaves, uint32_t* out_depth);   /* no device */
+
 /* Capacity for n_slots vertices (and n_upper_rows upper-level adjacency rows; 0 = the expectation for this index's M) in ONE allocation per
  * array, before the inserts.  Optional — Insert grows the arrays by half their size when they are full — but an index whose final size is
  * known should reserve it: growth copies every array (30 GB of rows at 10 M x 768 f32), and arrays allocated once from an empty heap get the

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdint>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -204,9 +205,40 @@ class Hnsw {
     Filter& operator=(const Filter&) = delete;
     uint64_t Allowed() const { return allowed_; }
     coltt_handle_t handle() const { return h_; }
+    // the allowed ids in ascending slot order, gathered on the device (coltt_hnsw_filter_ids); cap: at most that many
+    std::vector<uint64_t> Ids(uint64_t cap = UINT64_MAX) const {
+      std::vector<uint64_t> o((size_t)std::min<uint64_t>(cap, allowed_)); uint64_t n = 0;
+      check(coltt_hnsw_filter_ids(h_, o.data(), o.size(), &n));
+      return o;
+    }
+    // the slots of the index the filter covers (coltt_hnsw_filter_info)
+    uint64_t Slots() const { uint64_t s = 0; check(coltt_hnsw_filter_info(h_, nullptr, nullptr, &s)); return s; }
    private:
+    friend class Hnsw;
+    Filter(coltt_handle_t h, uint64_t allowed) : h_(h), allowed_(allowed) {}
     coltt_handle_t h_ = 0; uint64_t allowed_ = 0;
   };
+  // Filter expressions (coltt_gpu.h, "Filter expressions"): a postfix programme (leaf indices >= 0, COLTT_FOP_* operators) over resident
+  // filters, evaluated on the device.  The result is an ordinary Filter.
+  std::unique_ptr<Filter> FilterEval(const std::vector<int32_t>& prog, const std::vector<const Filter*>& leaves) const {
+    std::vector<coltt_handle_t> lh(leaves.size());
+    for (size_t i = 0; i < leaves.size(); i++) lh[i] = leaves[i] ? leaves[i]->handle() : 0;
+    coltt_handle_t h = 0; uint64_t allowed = 0;
+    check(coltt_hnsw_filter_eval(h_, prog.data(), prog.size(), lh.data(), lh.size(), &allowed, &h));
+    return std::unique_ptr<Filter>(new Filter(h, allowed));
+  }
+  // one Filter per programme over a shared leaf table, under one index state, in two kernel launches (coltt_hnsw_filter_eval_batch)
+  std::vector<std::unique_ptr<Filter>> FilterEvalBatch(const std::vector<std::vector<int32_t>>& progs, const std::vector<const Filter*>& leaves) const {
+    std::vector<coltt_handle_t> lh(leaves.size());
+    for (size_t i = 0; i < leaves.size(); i++) lh[i] = leaves[i] ? leaves[i]->handle() : 0;
+    std::vector<int32_t> flat; std::vector<uint64_t> off(progs.size() + 1, 0);
+    for (size_t i = 0; i < progs.size(); i++) { flat.insert(flat.end(), progs[i].begin(), progs[i].end()); off[i + 1] = flat.size(); }
+    std::vector<coltt_handle_t> hs(progs.size(), 0); std::vector<uint64_t> al(progs.size(), 0);
+    check(coltt_hnsw_filter_eval_batch(h_, flat.data(), off.data(), progs.size(), lh.data(), lh.size(), al.data(), hs.data()));
+    std::vector<std::unique_ptr<Filter>> out;
+    for (size_t i = 0; i < progs.size(); i++) out.emplace_back(new Filter(hs[i], al[i]));
+    return out;
+  }
   SearchResult SearchFiltered(const Vector& query, unsigned k, const Filter& f, unsigned ef = 0, int mode = COLTT_FILTER_AUTO,
                               coltt_hnsw_filter_stats* stats = nullptr) const {
     std::vector<uint64_t> ids(k); std::vector<float> sc(k); uint32_t n = 0;
