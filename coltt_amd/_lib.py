@@ -72,6 +72,9 @@ def lib():
             L.coltt_hnsw_pq_search_filtered_batch.restype = C.c_int
             L.coltt_hnsw_pq_search_filtered_batch.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "coltt_flat_mfma_eligible_host"):   # (metric, quant, dim, min_norm, max_norm, f8_expanded) -> 0 / 1; floats need argtypes
+            L.coltt_flat_mfma_eligible_host.restype = C.c_int
+            L.coltt_flat_mfma_eligible_host.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_float, C.c_float, C.c_int]
         _lib = L
         _sync_policy()
     return _lib

@@ -658,9 +658,53 @@ int launch_mfma_scan(Flat* f, FCtx* c, uint64_t b, uint64_t e, const _Float16* q
 // relative error bound of the Euclidean candidate value s~^2 against the exact s^2, in units of (||q||^2 + ||r||^2): D * 2^-24 from
 // the f32 accumulation of exact f16 products, 2^-10 more when f32 rows (and queries) are rounded to binary16 on their way into
 // LDS, and 3 * D * 2^-24 for the f32 rounding inside the two norms and the reference's own difference-form sum
+// (tests/flat_mfma_ref.py parses the four constants and checks that the two functions are built from them)
+constexpr float L2_ULP = 5.9604645e-8f;        // 2^-24
+constexpr float L2_ACC_TERMS = 4.0f;           // D * 2^-24 for the dot product + 3 * D * 2^-24 for the norms and the reference's sum
+constexpr float L2_ROUND_F16 = 9.8e-4f;        // >= 2^-10 + 2^-22: row and query element each off by <= 2^-11 of itself
+constexpr float L2_ABS_F16 = 8.9437e-8f;       // >= (1.5 + 2^-11) * 2^-24: see l2_abs
 float l2_eps(const Flat* f) {
-  const float acc = (float)f->dim * 5.9604645e-8f;
-  return 4.0f * acc + (f->quant == COLTT_Q_NONE ? 9.8e-4f : 0.f);
+  const float acc = (float)f->dim * L2_ULP;
+  return L2_ACC_TERMS * acc + (f->quant == COLTT_Q_NONE ? L2_ROUND_F16 : 0.f);
+}
+// ABSOLUTE error bound of the same value for f32 rows, in units of (||q|| + ||r||).  "Off by <= 2^-11 of itself" holds for an element in
+// binary16's NORMAL range only; below 2^-14 the cast rounds to a multiple of 2^-24, so in general x~ = x + e with
+//   |e| <= 2^-11 |x| + 2^-25   and   |e| <= |x|   (round to nearest; 0 is representable).
+// With a = q, b = r:  |dot~ - dot| <= sum |a_i| |e_b,i| + |b_i| |e_a,i| + |e_a,i| |e_b,i|.  Its relative part is l2_eps's; what is left is
+//   2^-25 (sum |a_i| + sum |b_i|)                        one operand's absolute part against the other operand,
+//   2^-36 (sum |a_i| + sum |b_i|)                        an absolute part against a relative part,
+//   sum 2^-25 min(|a_i|, |b_i|) <= 2^-26 (sum |a_i| + sum |b_i|)      both absolute parts (|e| <= |x| on one side),
+// and sum |a_i| <= sqrt(D) ||a||.  So |dot~ - dot|_abs <= (1.5 + 2^-11) * 2^-25 * sqrt(D) * (||q|| + ||r||), and the candidate value
+// ||q||^2 + ||r||^2 - 2 dot~ is off by twice that: L2_ABS_F16 * sqrt(D) * (||q|| + ||r||).  For rows of norm >= 1e-3 the term is noise
+// beside l2_eps's; for a store scaled down to 1e-6 per element it IS the error (the relative margin alone lost true neighbours there,
+// tests/test_flat_mfma_margin_host.py); where it exceeds the distances themselves everything is kept and the exact re-score (or, past the
+// candidate capacity, the exact re-run) answers.  2-byte rows are exact binary16 operands, denormals included: no such term.
+float l2_abs(const Flat* f) {
+  return f->quant == COLTT_Q_NONE ? L2_ABS_F16 * sqrtf((float)f->dim) : 0.f;
+}
+
+// May a store with these properties answer COLTT_MODE_MFMA through the matrix cores?  Pure host arithmetic (coltt_flat_mfma_eligible_host).
+// min_norm / max_norm: the running bounds of ||row||^2 over everything the store ever held (NaN while it is empty).
+bool mfma_eligible(int metric, int quant, uint32_t dim, float min_norm, float max_norm, bool f8x) {
+  // matrix-core candidates: cosine with every kernel generation; Euclidean (s~^2 = ||q||^2 + ||r||^2 - 2 dot, exact re-score) with
+  // the third-generation kernel, as long as every stored norm is finite (max_norm bounds the margin)
+  // (f32 rows are rounded to binary16 for candidate generation: ||row||^2 <= 4e9 keeps every element inside its range)
+  const bool l2_ok = metric == COLTT_EUCLIDEAN && max_norm == max_norm &&
+                     max_norm <= (quant == COLTT_Q_NONE ? 4.0e9f : 3.0e38f);
+  // Cosine: the candidate margin (flat_mfma.hpp: MF_MARGIN / MF_MARGIN_F32) is proved for rows of norm ~1 — f32 rows are rounded to
+  // binary16 on their way into the fragments, which is a RELATIVE perturbation only while the elements stay in binary16's normal
+  // range.  Upserts normalise (none_vectorstore.go:63-65), but a loaded stream is stored as it is (vectorstore load paths do not
+  // re-normalise), so a store that ever held a row with ||row||^2 outside [1/4, 4] answers through the exact scan.
+  // ("f8" rows: their binary16 copy holds exact values and the candidate value is scale-free — any finite, non-zero-range store qualifies)
+  const bool cos_ok = metric == COLTT_COSINE && (quant == COLTT_Q_F8 ? (f8x && max_norm == max_norm && max_norm < 3.0e38f) : (min_norm >= 0.25f && max_norm <= 4.0f));
+  // K need not be a multiple of the 32-column step with the DMA kernels: the query tile is zero-padded and the rows' overhang
+  // (padding, head of the next row — all finite as long as no stored norm ever was non-finite; Flat::reserve zeroes the rest)
+  // multiplies zeros.  dim >= 128: the raw-norm parity buffers assume >= 4 K steps per tile.
+  const bool finite_rows = max_norm == max_norm && max_norm < 3.0e38f;
+  const bool k_ok = (dim % MF_BK == 0 && dim >= 4 * MF_BK) || (finite_rows);
+  return (cos_ok || l2_ok) &&
+         (quant == COLTT_Q_NONE || quant == COLTT_Q_F16 || quant == COLTT_Q_BF16 || (quant == COLTT_Q_F8 && f8x && metric == COLTT_COSINE)) &&
+         k_ok && dim >= 8 && dim <= 4096;
 }
 
 // K of the candidate GEMM: dim padded to whole 32-column steps, and to at least FOUR steps — the kernel's raw-norm parity buffers
@@ -695,8 +739,9 @@ int search_group_mfma(Flat* f, FCtx* c, size_t q0, int g, uint32_t k, int neares
     else COLTT_TRY(launch_mfma_scan<256>(f, c, b, e, q16, qn, g, thr, nearest, cur, cnt, cap, seed, dimp, d_gather));
     if (f->metric == COLTT_COSINE)
       flat_pick_kernel<<<g, 256, 0, c->stream>>>(cur, oth, cnt, thr, cap, k, nearest, f->quant == COLTT_Q_NONE ? MF_MARGIN_F32 : MF_MARGIN, ovf);
-    else  // Euclidean: |s~^2 - s^2| <= eps * (||q||^2 + ||r||^2), eps = dot error (+ f16 rounding of f32 rows) + f32 rounding of the norms / the exact sum
-      flat_pick_kernel<<<g, 256, 0, c->stream>>>(cur, oth, cnt, thr, cap, k, nearest, 2.0f * l2_eps(f), ovf, qn, f->max_norm());
+    else  // Euclidean: |s~^2 - s^2| <= eps * (||q||^2 + ||r||^2) + abs * (||q|| + ||r||), eps = dot error (+ f16 rounding of f32 rows) + f32 rounding
+          // of the norms / the exact sum, abs = the rounding of f32 elements in binary16's subnormal range (l2_abs)
+      flat_pick_kernel<<<g, 256, 0, c->stream>>>(cur, oth, cnt, thr, cap, k, nearest, 2.0f * l2_eps(f), ovf, qn, f->max_norm(), 2.0f * l2_abs(f));
     std::swap(cur, oth);
     return COLTT_OK;
   };
@@ -732,28 +777,10 @@ int search_prepared(Flat* f, FCtx* c, size_t nq, uint32_t k, int select, int mod
                     uint64_t* d_out_ids, float* d_out_sc, uint32_t* d_out_cnt) {
   const int nearest = select == COLTT_SELECT_NEAREST;
   const uint32_t cap = std::max<uint32_t>(65536u, 8u * k);
-  // matrix-core candidates: cosine with every kernel generation; Euclidean (s~^2 = ||q||^2 + ||r||^2 - 2 dot, exact re-score) with
-  // the third-generation kernel, as long as every stored norm is finite (max_norm bounds the margin)
-  // (f32 rows are rounded to binary16 for candidate generation: ||row||^2 <= 4e9 keeps every element inside its range)
-  const float max_norm = f->max_norm(), min_norm = f->min_norm();
-  const bool l2_ok = f->metric == COLTT_EUCLIDEAN && max_norm == max_norm &&
-                     max_norm <= (f->quant == COLTT_Q_NONE ? 4.0e9f : 3.0e38f);
-  // Cosine: the candidate margin (flat_mfma.hpp: MF_MARGIN / MF_MARGIN_F32) is proved for rows of norm ~1 — f32 rows are rounded to
-  // binary16 on their way into the fragments, which is a RELATIVE perturbation only while the elements stay in binary16's normal
-  // range.  Upserts normalise (none_vectorstore.go:63-65), but a loaded stream is stored as it is (vectorstore load paths do not
-  // re-normalise), so a store that ever held a row with ||row||^2 outside [1/4, 4] answers through the exact scan.
-  // ("f8" rows: their binary16 copy holds exact values and the candidate value is scale-free — any finite, non-zero-range store qualifies)
-  const bool cos_ok = f->metric == COLTT_COSINE && (f->quant == COLTT_Q_F8 ? (f->f8x && max_norm == max_norm && max_norm < 3.0e38f) : (min_norm >= 0.25f && max_norm <= 4.0f));
-  // K need not be a multiple of the 32-column step with the DMA kernels: the query tile is zero-padded and the rows' overhang
-  // (padding, head of the next row — all finite as long as no stored norm ever was non-finite; Flat::reserve zeroes the rest)
-  // multiplies zeros.  dim >= 128: the raw-norm parity buffers assume >= 4 K steps per tile.
-  const bool finite_rows = max_norm == max_norm && max_norm < 3.0e38f;
-  const bool k_ok = (f->dim % MF_BK == 0 && f->dim >= 4 * MF_BK) || (finite_rows);
+  // matrix-core candidates: which stores qualify is mfma_eligible's decision
   // (a filtered search — d_gather: positions of a slot list — takes the matrix cores too, through the kernel's gather mode; the
   //  superseded experiment generations have none)
-  const bool mfma = mode == COLTT_MODE_MFMA && (cos_ok || l2_ok) &&
-                    (f->quant == COLTT_Q_NONE || f->quant == COLTT_Q_F16 || f->quant == COLTT_Q_BF16 || (f->quant == COLTT_Q_F8 && f->f8x && f->metric == COLTT_COSINE)) &&
-                    k_ok && f->dim >= 8 && f->dim <= 4096 && total > 0;
+  const bool mfma = mode == COLTT_MODE_MFMA && mfma_eligible(f->metric, f->quant, f->dim, f->min_norm(), f->max_norm(), f->f8x) && total > 0;
   // small batches: the whole search in one launch, whatever the mode asked for (exact-order scores either way)
   // (2-4 queries: while the scan is short — its four-query tile streams at about half the one-query rate, and past ~400 MB the chain's
   //  launch gaps no longer matter: 1 M x 128 f32 x 4 queries 286 us here, 212 us through the chain; 100 k x 768: 123 vs 185)
@@ -1662,9 +1689,12 @@ int coltt_flat_norm_bounds(coltt_handle_t h, float* out_min, float* out_max, int
   if (out_min) *out_min = mn;
   if (out_max) *out_max = mx;
   if (out_cosine_matrix_core_open)
-    *out_cosine_matrix_core_open = f->metric == COLTT_COSINE &&
-      (f->quant == COLTT_Q_F8 ? (f->f8x && mx == mx && mx < 3.0e38f) : (mn >= 0.25f && mx <= 4.0f)) ? 1 : 0;
+    *out_cosine_matrix_core_open = f->metric == COLTT_COSINE && mfma_eligible(f->metric, f->quant, f->dim, mn, mx, f->f8x) ? 1 : 0;
   return COLTT_OK;
+}
+
+int coltt_flat_mfma_eligible_host(int metric, int quant, uint32_t dim, float min_norm, float max_norm, int f8_expanded) {
+  return mfma_eligible(metric, quant, dim, min_norm, max_norm, f8_expanded != 0) ? 1 : 0;
 }
 
 int coltt_flat_one_launch_searches(coltt_handle_t h, uint64_t* out) {

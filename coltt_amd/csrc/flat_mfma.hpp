@@ -153,7 +153,7 @@ __device__ __forceinline__ bool mf_bad_norms(const f32x4 (&ir)[4]) {
 __global__ __launch_bounds__(256) void flat_pick_kernel(const unsigned long long* __restrict__ src_all, unsigned long long* __restrict__ dst_all,
                                                        uint32_t* __restrict__ cnt_all, uint32_t* __restrict__ thr_all, uint32_t cap,
                                                        uint32_t k, int nearest, float margin, uint32_t* __restrict__ overflow,
-                                                       const float* __restrict__ qn_l2 = nullptr, float max_row_norm = 0.f) {
+                                                       const float* __restrict__ qn_l2 = nullptr, float max_row_norm = 0.f, float abs_l2 = 0.f) {
   __shared__ uint32_t hist[256], wsum[4];
   __shared__ uint32_t s_digit, s_need, s_n;
   const int q = blockIdx.x, tid = threadIdx.x;
@@ -212,8 +212,9 @@ __global__ __launch_bounds__(256) void flat_pick_kernel(const unsigned long long
     }
     // k-th best approximate score, widened by the margin in the "worse" direction
     float t = key_score(prefix ^ flip);
-    // Euclidean candidates carry s~^2 = ||q||^2 + ||r||^2 - 2 dot~; its error scales with the norms: margin * (||q||^2 + max ||r||^2)
-    if (qn_l2) margin = qn_l2[q] <= 4.0e9f ? margin * (qn_l2[q] + max_row_norm) : __builtin_inff();   // out-of-range query: keep everything (-> exact fallback)
+    // Euclidean candidates carry s~^2 = ||q||^2 + ||r||^2 - 2 dot~; its error scales with the norms: margin * (||q||^2 + max ||r||^2), plus
+    // — f32 rows only, flat.hip: l2_abs — the absolute rounding of elements in binary16's subnormal range: abs_l2 * (||q|| + max ||r||)
+    if (qn_l2) margin = qn_l2[q] <= 4.0e9f ? margin * (qn_l2[q] + max_row_norm) + abs_l2 * (sqrtf(qn_l2[q]) + sqrtf(max_row_norm)) : __builtin_inff();   // out-of-range query: keep everything (-> exact fallback)
     float b = nearest ? t + margin : t - margin;
     bound_key = score_key(b) ^ flip;
     if (bound_key < prefix) bound_key = prefix;  // NaN / saturation guard

@@ -166,6 +166,12 @@ class FlatSpace:
         L.check(L.lib().coltt_flat_norm_bounds(self.h, C.byref(a), C.byref(b_), C.byref(o)))
         return a.value, b_.value, bool(o.value)
 
+    @staticmethod
+    def MfmaEligible(distance, quantization, dim, min_norm, max_norm, f8_expanded=False):
+        """coltt_flat_mfma_eligible_host: the decision a MODE_MFMA search takes for a store with these norm bounds; no device"""
+        return bool(L.lib().coltt_flat_mfma_eligible_host(int(distance), int(quantization), C.c_uint32(dim), C.c_float(min_norm), C.c_float(max_norm),
+                                                          int(bool(f8_expanded))))
+
     def OneLaunchSearches(self):
         a = C.c_uint64(0)
         L.check(L.lib().coltt_flat_one_launch_searches(self.h, C.byref(a)))

@@ -117,6 +117,11 @@ int coltt_flat_stats(coltt_handle_t h, uint64_t* mfma_groups, uint64_t* mfma_fal
  * that was never normalised) — such a store answers COLTT_MODE_MFMA batches through the exact scan: same answers, ~25x the time at batch
  * 256.  Nothing is logged when the latch closes; this is where a caller sees it.  An empty store reports NaN bounds. */
 int coltt_flat_norm_bounds(coltt_handle_t h, float* out_min, float* out_max, int32_t* out_cosine_matrix_core_open);
+/* Host only, no device: would a store of this metric, quantization and dimension whose stored ||row||^2 lie in [min_norm, max_norm] (the
+ * bounds coltt_flat_norm_bounds reports) answer COLTT_MODE_MFMA batches through the matrix cores (1) or through the exact scan (0)?  The
+ * same function the search calls — for tests and for callers that want to know before they load.  f8_expanded: the "f8" store keeps its
+ * binary16 copy (cosine only; COLTT_F8_MFMA).  Batches of 1-4 queries take the one-launch kernel whatever this says. */
+int coltt_flat_mfma_eligible_host(int metric, int quant, uint32_t dim, float min_norm, float max_norm, int f8_expanded);
 /* searches of <= 4 queries and k <= 64 are served by ONE kernel launch whatever `mode` says (scan in exact order, per-wave and
  * per-block k best, selection by the last block to finish): the reference's one-query-per-RPC shape (edge/edge_search.go).  Same
  * answers as both modes; this counts them (COLTT_FLAT_ONE=0 in the environment turns the path off). */
