@@ -10,6 +10,7 @@ from ._lib import (COSINE, EUCLIDEAN, Q_NONE, Q_F16, Q_F8, Q_BF16, SELECT_REFERE
                    MODE_EXACT, MODE_MFMA, ColttError, lib, lib_path, declared_symbols)
 from .flat import FlatSpace  # noqa: F401
 from .hnsw import Hnsw, HnswCfg, HnswFilter, FILTER_AUTO, FILTER_WALK, FILTER_EXACT  # noqa: F401
+from .hnsw import HnswCompactStats, compact_map_host  # noqa: F401
 from .hnsw import FOP_AND, FOP_OR, FOP_ANDNOT, FOP_NOT, FOP_ALL, filter_postfix, filter_tree, filter_prog_check  # noqa: F401
 from .cflat import MultiVectorSpace  # noqa: F401
 from .pq import PQSpace, PQ_COSINE, PQ_EUCLIDEAN, PQ_DOT  # noqa: F401

@@ -1,7 +1,7 @@
 // hnsw.hip — core/vectorindex.Hnsw on the GPU (core/vectorindex/hnsw.go).
 //
 // HBM layout (one index = one collection shard on one GPU), everything addressed by dense slot (u32 =
-// insertion index, never reused — the oracle uses the same numbering as its canonical order):
+// insertion index, never reused until Compact — the oracle uses the same numbering as its canonical order):
 //   rows      [cap][stride]     stored vectors (normalised for cosine; 4/2/1-byte codes)
 //   norms     [cap] f32         ||row||^2 in AVX order
 //   ids       [cap] u64         slot -> id                       (absent in dense-id mode)
@@ -24,6 +24,7 @@
 
 #include "hnsw_kernels.hpp"   // the search kernels (one-wave walk, large-ef walk, latency kernel, walk over PQ codes + re-rank)
 #include "filter_expr.hpp"    // filter expressions: evaluate, compact, read-back
+#include "hnsw_compact.hpp"   // coltt_hnsw_compact: the plan, the row movers, the adjacency re-pack
 
 using namespace coltt;
 using namespace coltt::dev;
@@ -2255,6 +2256,189 @@ int coltt_hnsw_remove(coltt_handle_t h, uint64_t id) {
   uint32_t n_l0 = 0;
   while (n_l0 < t_lv.size() && t_lv[t_lv.size() - 1 - n_l0] == 0) n_l0++;
   return pq_nbr_patch_end(x.get(), patch, 0, 0, n_l0 ? x->b_req.as<uint32_t>() + (t_nb.size() - n_l0) : nullptr, n_l0);
+}
+
+// ---- HNSW compaction (include/coltt_gpu.h, "HNSW compaction"; kernels and the hazard argument: hnsw_compact.hpp) --------------------------
+int coltt_hnsw_compact_map_host(const uint32_t* del_bits, uint64_t n_slots, const int32_t* levels, uint32_t* out_new_of_old,
+                                uint32_t* out_new_upper_off, uint64_t* out_live, uint64_t* out_upper_rows) {
+  if (n_slots >= 0x7fffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_compact_map_host: more than 2^31-1 slots");
+  if (n_slots && !levels && (out_new_upper_off || out_upper_rows)) return fail(COLTT_E_INVALID, "hnsw_compact_map_host: the upper-row outputs need levels");
+  compact::map_host(del_bits, n_slots, levels, out_new_of_old, out_new_upper_off, out_live, out_upper_rows);
+  return COLTT_OK;
+}
+
+int coltt_hnsw_compact(coltt_handle_t h, uint64_t stage_bytes_or_0, uint32_t* out_new_of_old, uint64_t cap_map, coltt_hnsw_compact_stats* stats) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_compact: unknown handle");
+  WriteLock g(x->rw);
+  COLTT_DEVICE(x->device);
+  const uint64_t n = x->n;
+  if (out_new_of_old && cap_map < n) return fail(COLTT_E_INVALID, "hnsw_compact: the map holds %llu entries, the index has %llu slots", (unsigned long long)cap_map, (unsigned long long)n);
+  coltt_hnsw_compact_stats st{};
+  st.slots_before = st.slots_after = n; st.upper_rows_before = st.upper_rows_after = x->n_upper;
+  if (x->live == n) {   // no tombstone: nothing is launched, nothing is renumbered
+    if (out_new_of_old) for (uint64_t s = 0; s < n; s++) out_new_of_old[s] = (uint32_t)s;
+    if (stats) *stats = st;
+    return COLTT_OK;
+  }
+  // ---- the plan, from the host mirrors
+  std::vector<uint32_t> nmap(n), nuo(x->live);
+  uint64_t live = 0, up_after = 0;
+  compact::map_host(x->h_del.data(), n, x->h_levels.data(), nmap.data(), nuo.data(), &live, &up_after);
+  // Remove elects the removed entrypoint's closest listed neighbour without asking whether it is alive (hnsw.go:197-217): a walk can start from a
+  // tombstone, a compacted index cannot — refused before anything changes rather than answered differently
+  if (live && x->entry >= 0 && nmap[(size_t)x->entry] == NBR_NONE)
+    return fail(COLTT_E_UNSUPPORTED, "hnsw_compact: the entrypoint (slot %d) is a tombstone; dropping it would change the answers", x->entry);
+  const size_t words = (size_t)((n + 31) / 32);
+  uint64_t first = 0;                                   // the first tombstone: the slots below it keep their numbers
+  while (nmap[first] != NBR_NONE) first++;
+  std::vector<uint32_t> old_of_new(live), rank(words, 0u), uold(up_after);
+  for (uint64_t s = 0; s < n; s++) if (nmap[s] != NBR_NONE) old_of_new[nmap[s]] = (uint32_t)s;
+  { uint32_t c = 0; for (size_t w = 0; w < words; w++) { rank[w] = c; const uint64_t in_word = std::min<uint64_t>(32, n - (uint64_t)w * 32);
+      const uint32_t mask = in_word == 32 ? 0xffffffffu : ((1u << in_word) - 1u); c += (uint32_t)__builtin_popcount(~x->h_del[w] & mask); } }
+  for (uint64_t j = 0; j < live; j++) {
+    const uint32_t s = old_of_new[j];
+    for (int32_t l = 0; l < x->h_levels[s]; l++) uold[(size_t)nuo[j] + l] = x->h_upper_off[s] + (uint32_t)l;
+  }
+  uint64_t ufirst = 0;                                  // the first upper row that moves
+  while (ufirst < up_after && uold[ufirst] == ufirst) ufirst++;
+  st.slots_after = live; st.upper_rows_after = up_after; st.rows_moved = live - first;
+  x->pq_nbr_stale.store(true);   // the slots are about to be renumbered: the next walk over the blocks rebuilds them, as after Load
+  if (live == 0) {               // every vertex is dead: the empty index
+    hipError_t e = hipMemsetAsync(x->del_bits.p, 0, words * 4, x->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
+    make_empty(x.get());
+    if (e != hipSuccess) return fail(COLTT_E_DEVICE, "hnsw_compact: %s", hipGetErrorString(e));
+    if (out_new_of_old) std::copy(nmap.begin(), nmap.end(), out_new_of_old);
+    if (stats) *stats = st;
+    return COLTT_OK;
+  }
+  // ---- what moves.  Per-slot arrays: rows of rb bytes; every allocation is made before the first kernel, so a refused one leaves the index as it was
+  struct Move { uint8_t* p; size_t rb; };
+  std::vector<Move> moves;
+  moves.push_back({x->rows.as<uint8_t>(), x->stride});
+  if (x->has_shadow16()) moves.push_back({x->rows_h.as<uint8_t>(), (size_t)x->dim * 2});
+  if (x->has_shadow8()) { moves.push_back({x->rows_b.as<uint8_t>(), (size_t)x->dim}); moves.push_back({x->rows_m.as<uint8_t>(), 8}); }
+  moves.push_back({x->norms.as<uint8_t>(), 4});
+  if (!x->dense) moves.push_back({x->ids.as<uint8_t>(), 8});
+  const bool pq_move = x->pq_on && x->pq_done == n && x->pq_codes.p;   // (writers leave every slot coded; otherwise the codes are made again below)
+  if (pq_move) moves.push_back({x->pq_codes.as<uint8_t>(), (size_t)x->pq_row});
+  const uint32_t W0 = (uint32_t)x->cfg.m_max0, WU = (uint32_t)x->cfg.m_max;
+  const bool with_n = x->metric == COLTT_COSINE, with_m = x->has_shadow8();
+  auto region = [](uint64_t rows, uint32_t W, size_t elem) { return ((size_t)rows * W * elem + 255) & ~(size_t)255; };   // one array's share of the staging block
+  auto adj_stage = [&](uint64_t rows, uint32_t W, bool level0) {
+    return 2 * region(rows, W, 4) + (level0 && with_n ? region(rows, W, 4) : 0) + (level0 && with_m ? region(rows, W, 8) : 0);
+  };
+  const uint64_t budget = stage_bytes_or_0 ? stage_bytes_or_0 : (64ull << 20);
+  // destinations per chunk: max(64, budget / row bytes), no more than there are rows to move, the launch's pieces within a 32-bit grid
+  auto chunk_of = [&](size_t rb, uint64_t count) { return std::min<uint64_t>({std::max<uint64_t>(64, budget / rb), std::max<uint64_t>(count, 1), (1ull << 34) / rb}); };
+  const uint64_t ch0 = chunk_of((size_t)W0 * 20, live - first), chU = chunk_of((size_t)WU * 8, up_after - ufirst);
+  size_t stage_need = 0;
+  if (live > first) {
+    for (const Move& m : moves) stage_need = std::max(stage_need, (size_t)chunk_of(m.rb, live - first) * m.rb);
+    stage_need = std::max(stage_need, adj_stage(ch0, W0, true));
+  }
+  if (up_after > ufirst) stage_need = std::max(stage_need, adj_stage(chU, WU, false));
+  DevBuf d_stage, d_plan;
+  const size_t off_rank = ((size_t)live * 4 + 255) & ~(size_t)255, off_uold = off_rank + ((words * 4 + 255) & ~(size_t)255),
+               off_cnt = off_uold + (((size_t)up_after * 4 + 255) & ~(size_t)255);
+  COLTT_TRY(d_plan.reserve(off_cnt + 256));
+  if (stage_need) COLTT_TRY(d_stage.reserve(stage_need));
+  if (x->dense) COLTT_TRY(x->ids.reserve(std::max<uint64_t>(x->cap, 1024) * 8, false, x->stream));
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  COLTT_HIP(hipEventCreate(&ev0));
+  if (hipEventCreate(&ev1) != hipSuccess) { (void)hipEventDestroy(ev0); return fail(COLTT_E_DEVICE, "hnsw_compact: hipEventCreate"); }
+  uint8_t* const plan = d_plan.as<uint8_t>(); uint8_t* const stage = d_stage.as<uint8_t>();
+  const uint32_t* d_oon = reinterpret_cast<const uint32_t*>(plan); const uint32_t* d_rank = reinterpret_cast<const uint32_t*>(plan + off_rank);
+  const uint32_t* d_uold = reinterpret_cast<const uint32_t*>(plan + off_uold);
+  unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(plan + off_cnt);
+  unsigned long long dropped = 0;
+  uint64_t bytes = 0;
+  // ---- from here on the index changes: a device failure leaves the EMPTY index
+  auto run = [&]() -> int {
+    hipStream_t s = x->stream;
+    COLTT_HIP(hipMemcpyAsync(plan, old_of_new.data(), live * 4, hipMemcpyHostToDevice, s));
+    COLTT_HIP(hipMemcpyAsync(plan + off_rank, rank.data(), words * 4, hipMemcpyHostToDevice, s));
+    if (up_after) COLTT_HIP(hipMemcpyAsync(plan + off_uold, uold.data(), up_after * 4, hipMemcpyHostToDevice, s));
+    COLTT_HIP(hipMemsetAsync(d_cnt, 0, 8, s));
+    COLTT_HIP(hipEventRecord(ev0, s));
+    // adjacency rows of one level class: rows [0, fst) are rewritten in place, rows [fst, cnt) go through the staging block chunk by chunk
+    auto adjacency = [&](uint32_t* ids, float* d, float* nn, float2* mm, uint32_t W, const uint32_t* list, uint64_t fst, uint64_t cnt, uint64_t ch) -> int {
+      compact::AdjJob j{};
+      j.src_ids = ids; j.src_d = d; j.src_n = nn; j.src_m = mm; j.W = W;
+      j.del_bits = x->del_bits.as<uint32_t>(); j.rank = d_rank; j.n_slots = (uint32_t)n; j.dropped = d_cnt;
+      const size_t row_b = (size_t)W * (8 + (nn ? 4 : 0) + (mm ? 8 : 0));
+      for (uint64_t b = 0; b < fst; b += 1u << 24) {
+        j.dst_ids = ids; j.dst_d = d; j.dst_n = nn; j.dst_m = mm; j.src_list = list + b; j.dst_row0 = b; j.m = (uint32_t)std::min<uint64_t>(1u << 24, fst - b);
+        compact::compact_adj_kernel<<<compact::adj_grid(j.m), 256, 0, s>>>(j);
+        bytes += (uint64_t)j.m * row_b;
+      }
+      const int vb4 = compact::width_of((size_t)W * 4), vb8 = compact::width_of((size_t)W * 8);
+      for (uint64_t b = fst; b < cnt; b += ch) {
+        const uint64_t m = std::min<uint64_t>(ch, cnt - b);
+        uint8_t* s_ids = stage; uint8_t* s_d = s_ids + region(m, W, 4); uint8_t* s_n = s_d + region(m, W, 4); uint8_t* s_m = s_n + (nn ? region(m, W, 4) : 0);
+        j.dst_ids = reinterpret_cast<uint32_t*>(s_ids); j.dst_d = reinterpret_cast<float*>(s_d);
+        j.dst_n = nn ? reinterpret_cast<float*>(s_n) : nullptr; j.dst_m = mm ? reinterpret_cast<float2*>(s_m) : nullptr;
+        j.src_list = list + b; j.dst_row0 = 0; j.m = (uint32_t)m;
+        compact::compact_adj_kernel<<<compact::adj_grid(m), 256, 0, s>>>(j);
+        compact::launch_copy(s, s_ids, reinterpret_cast<uint8_t*>(ids + b * W), m * W * 4, vb4);
+        compact::launch_copy(s, s_d, reinterpret_cast<uint8_t*>(d + b * W), m * W * 4, vb4);
+        if (nn) compact::launch_copy(s, s_n, reinterpret_cast<uint8_t*>(nn + b * W), m * W * 4, vb4);
+        if (mm) compact::launch_copy(s, s_m, reinterpret_cast<uint8_t*>(mm + b * W), m * W * 8, vb8);
+        bytes += 2 * m * row_b;
+      }
+      COLTT_HIP(hipGetLastError());
+      return COLTT_OK;
+    };
+    COLTT_TRY(adjacency(x->adj0.as<uint32_t>(), x->adj0_d.as<float>(), with_n ? x->adj0_n.as<float>() : nullptr, with_m ? x->adj0_m.as<float2>() : nullptr,
+                        W0, d_oon, first, live, ch0));
+    if (up_after) COLTT_TRY(adjacency(x->adjU.as<uint32_t>(), x->adjU_d.as<float>(), nullptr, nullptr, WU, d_uold, ufirst, up_after, chU));
+    for (const Move& mv : moves) {
+      const uint64_t ch = chunk_of(mv.rb, live - first);
+      const int vb = compact::width_of(mv.rb);
+      for (uint64_t b = first; b < live; b += ch) {
+        const uint64_t m = std::min<uint64_t>(ch, live - b);
+        compact::launch_gather(s, mv.p, mv.rb, d_oon + b, m, stage);
+        compact::launch_copy(s, stage, mv.p + b * mv.rb, m * mv.rb, vb);
+        bytes += 2 * m * mv.rb;
+      }
+      COLTT_HIP(hipGetLastError());
+    }
+    if (x->dense) {
+      compact::compact_dense_ids_kernel<<<ceil_div(live, 256), 256, 0, s>>>(x->ids.as<uint64_t>(), d_oon, live, x->dense_base);
+      COLTT_HIP(hipGetLastError());
+      bytes += live * 8;
+    }
+    COLTT_HIP(hipMemcpyAsync(x->upper_off.p, nuo.data(), live * 4, hipMemcpyHostToDevice, s));
+    COLTT_HIP(hipMemsetAsync(x->del_bits.p, 0, words * 4, s));   // last: every launch above read the old tombstones
+    COLTT_HIP(hipEventRecord(ev1, s));
+    COLTT_HIP(hipMemcpyAsync(&dropped, d_cnt, 8, hipMemcpyDeviceToHost, s));
+    COLTT_HIP(hipStreamSynchronize(s));
+    COLTT_HIP(hipEventElapsedTime(&st.ms, ev0, ev1));
+    return COLTT_OK;
+  };
+  int rc = run();
+  (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
+  if (rc != COLTT_OK) { (void)hipStreamSynchronize(x->stream); make_empty(x.get()); return rc; }
+  // ---- the host mirrors, from the plan
+  std::vector<int32_t> lv(live);
+  std::vector<uint64_t> nids(live);
+  for (uint64_t j = 0; j < live; j++) { const uint32_t s = old_of_new[j]; lv[j] = x->h_levels[s]; nids[j] = x->dense ? x->dense_base + s : x->h_ids[s]; }
+  x->h_levels = std::move(lv); x->h_ids = std::move(nids); x->h_upper_off = std::move(nuo);
+  x->h_del.assign((size_t)((live + 31) / 32), 0u);
+  x->id2slot.clear(); x->id2slot.reserve(live * 2);
+  for (uint64_t j = 0; j < live; j++) x->id2slot[x->h_ids[j]] = (uint32_t)j;
+  x->dense = false; x->dense_base = 0;
+  x->n = live; x->live = live; x->n_upper = up_after; x->any_deleted = false;
+  if (x->entry >= 0) x->entry = (int32_t)nmap[(size_t)x->entry];   // (alive: checked above)
+  x->pq_done = pq_move ? live : 0;
+  x->gen++;                      // the slots were renumbered: filters built before are stale
+  rc = sync_pq(x.get());
+  if (rc != COLTT_OK) { make_empty(x.get()); return rc; }
+  st.edges_dropped = dropped; st.bytes_moved = bytes;
+  if (out_new_of_old) std::copy(nmap.begin(), nmap.end(), out_new_of_old);
+  if (stats) *stats = st;
+  return COLTT_OK;
 }
 
 int coltt_hnsw_export(coltt_handle_t h, uint64_t* n_slots, uint64_t* n_rows, uint64_t* n_edges, uint64_t* ids,

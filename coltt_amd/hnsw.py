@@ -109,6 +109,29 @@ def _prog_array(prog):
     return np.ascontiguousarray(np.asarray(prog, dtype=np.int32).reshape(-1))
 
 
+class HnswCompactStats(C.Structure):
+    """coltt_hnsw_compact_stats (include/coltt_gpu.h, "HNSW compaction")"""
+    _fields_ = [("slots_before", C.c_uint64), ("slots_after", C.c_uint64), ("upper_rows_before", C.c_uint64), ("upper_rows_after", C.c_uint64),
+                ("edges_dropped", C.c_uint64), ("rows_moved", C.c_uint64), ("bytes_moved", C.c_uint64), ("ms", C.c_float)]
+
+
+def compact_map_host(del_bits, n_slots, levels):
+    """coltt_hnsw_compact_map_host (no device): the plan of Hnsw.Compact.  del_bits: uint32 words, bit s % 32 of word s // 32 = slot s is
+    tombstoned (None = none is); levels [n_slots].  Returns (new_of_old [n_slots], 0xffffffff for a dead slot; new_upper_off [live], indexed by
+    NEW slot, 0xffffffff for a vertex of level 0; live; upper_rows)."""
+    n = int(n_slots)
+    db = None if del_bits is None else np.ascontiguousarray(np.asarray(del_bits, dtype=np.uint32).reshape(-1))
+    if db is not None and db.size * 32 < n:
+        raise ValueError(f"compact_map_host: {db.size} bitmap words for {n} slots")
+    lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32).reshape(-1))
+    if lv.size < n:
+        raise ValueError(f"compact_map_host: {lv.size} levels for {n} slots")
+    new_of_old = np.empty(n, np.uint32); upper_off = np.empty(n, np.uint32)
+    live = C.c_uint64(0); up = C.c_uint64(0)
+    L.check(L.lib().coltt_hnsw_compact_map_host(L.vp(db), C.c_uint64(n), L.vp(lv), L.vp(new_of_old), L.vp(upper_off), C.byref(live), C.byref(up)))
+    return new_of_old, upper_off[:live.value].copy(), live.value, up.value
+
+
 class HnswFilter:
     """An allow-list of ids against one index (coltt_hnsw_filter_create; include/coltt_gpu.h, "Filtered HNSW search" — an extension the
     reference does not have).  `.allowed` = the live vertices it allows."""
@@ -243,6 +266,23 @@ class Hnsw:
     # -- Hnsw.Remove (hnsw.go:191-241)
     def Remove(self, id_):
         L.check(L.lib().coltt_hnsw_remove(self.h, C.c_uint64(int(id_))))
+
+    # -- reclaim the slots Remove left behind (an extension the reference does not have)
+    def Compact(self, stage_bytes=0, with_map=False):
+        """coltt_hnsw_compact: drop the tombstoned slots in place on the device — vertex s moves to slot new(s) = live slots below s, no answer of
+        any search changes, filters built before are stale.  stage_bytes: the staging block (0 = 64 MiB).  Returns the stats dict, with
+        with_map=True also new_of_old [slots before] (0xffffffff for a dropped slot)."""
+        ns = C.c_uint64(0)
+        m = None
+        if with_map:
+            L.check(L.lib().coltt_hnsw_export_raw(self.h, C.byref(ns), None, None, None, None, None, None))
+            m = np.empty(ns.value, np.uint32)
+        st = HnswCompactStats()
+        L.check(L.lib().coltt_hnsw_compact(self.h, C.c_uint64(int(stage_bytes)), L.vp(m), C.c_uint64(ns.value), C.byref(st)))
+        d = {k: getattr(st, k) for k, _ in HnswCompactStats._fields_}
+        if with_map:
+            return d, m[:d["slots_before"]]
+        return d
 
     # -- Hnsw.Search (hnsw.go:243-278) for a batch of queries
     def Search(self, queries, k, ef=0, with_stats=False):

@@ -147,6 +147,26 @@ func HnswReserve(h Handle, nSlots uint64) error {
 func HnswRemove(h Handle, id uint64) error {
 	return call(func() C.int { return C.coltt_hnsw_remove(h, C.uint64_t(id)) })
 }
+
+// HnswCompactStats mirrors coltt_hnsw_compact_stats.
+type HnswCompactStats struct {
+	SlotsBefore, SlotsAfter         uint64
+	UpperRowsBefore, UpperRowsAfter uint64
+	EdgesDropped                    uint64 // adjacency entries that named a tombstoned slot, all levels
+	RowsMoved                       uint64 // live slots whose number changed
+	BytesMoved                      uint64 // bytes the move kernels wrote, staging included
+	Ms                              float32
+}
+
+// HnswCompact reclaims the slots of removed vertices on the device (coltt_hnsw_compact — an extension the reference does not have): the
+// live vertices keep their order and move down, no search answer changes, filters built before the call are stale.  stageBytes: the
+// staging block (0 = 64 MiB).  The slots are renumbered: slot-indexed tables of the caller come from a fresh export afterwards.
+func HnswCompact(h Handle, stageBytes uint64) (HnswCompactStats, error) {
+	var st C.coltt_hnsw_compact_stats
+	err := call(func() C.int { return C.coltt_hnsw_compact(h, C.uint64_t(stageBytes), nil, 0, &st) })
+	return HnswCompactStats{uint64(st.slots_before), uint64(st.slots_after), uint64(st.upper_rows_before), uint64(st.upper_rows_after),
+		uint64(st.edges_dropped), uint64(st.rows_moved), uint64(st.bytes_moved), float32(st.ms)}, err
+}
 func HnswLen(h Handle) int {
 	var n C.uint64_t
 	C.coltt_hnsw_len(h, &n)

@@ -695,6 +695,21 @@ func (xx *Hnsw) Commit(w io.Writer, header bool) error {
 	return err
 }
 
+// Compact reclaims the device memory of removed vertices (coltt_hnsw_compact) — NOT in the reference, whose Remove frees its vertex to
+// the garbage collector.  An index that is updated in place (Core.Update = Remove + Insert) should call it now and then: answers do not
+// change, walks stop testing tombstones, later Inserts fill the freed slots.  It takes commitMu exclusive like Commit: Commit's blob table
+// is indexed by slot from HnswSlots, and the call renumbers the slots (the metadata here is keyed by id and stays as it is).  Filters
+// built before the call are stale: build them again from their ids.
+func (xx *Hnsw) Compact() (colttgpu.HnswCompactStats, error) {
+	if xx.err != nil {
+		return colttgpu.HnswCompactStats{}, xx.err
+	}
+	xx.commitMu.Lock()
+	defer xx.commitMu.Unlock()
+	st, err := colttgpu.HnswCompact(xx.h, 0)
+	return st, mapErr(err)
+}
+
 // Load(r, header) — hnsw_commit.go:164-278: the stream goes straight into HBM; metadata blobs are decoded here.
 func (xx *Hnsw) Load(r io.Reader, header bool) error {
 	data, err := io.ReadAll(r)

@@ -404,6 +404,54 @@ int coltt_hnsw_filter_prog_check_host(const int32_t* prog, size_t n_prog, size_t
  * known should reserve it: growth copies every array (30 GB of rows at 10 M x 768 f32), and arrays allocated once from an empty heap get the
  * largest contiguous physical fragments, which the random row reads of a search feel in their TLB miss rate. */
 int coltt_hnsw_reserve(coltt_handle_t h, uint64_t n_slots, uint64_t n_upper_rows);
+
+/* HNSW COMPACTION: reclaim the slots of removed vertices on the device (coltt_hnsw_compact) — an extension the reference does not have.
+ * coltt_hnsw_remove only sets a tombstone: the vertex keeps its row, its derived rows, its adjacency rows and its id, other vertices may keep edges to
+ * it, and every walk tests the tombstone bitmap per neighbour from then on.  The reference's write path makes that the normal case (Core.Update,
+ * core/core.go:471-564, is Remove + Insert under the same id), so a collection updated in place only grows.  This call drops the tombstoned slots in
+ * place, without a second copy of the collection and without the host.
+ * Definition.  Let live(s) = slot s is not tombstoned and new(s) = the number of live slots below s.  After the call the index holds exactly the live
+ * vertices, vertex s at slot new(s).  Its stored row bytes, norm, id, level and every derived per-slot datum (binary16 shadow, 8-bit shadow code row and
+ * (scale, error norm), the quantiser's code row) are the bytes they were.  Each of its adjacency rows, level 0 and upper, is the old row with the
+ * tombstoned entries dropped and the survivors renamed by new() — still ascending, padded with 0xffffffff — and the per-edge companions (stored
+ * distances, neighbour norms, neighbour (scale, error norm) pairs) re-packed in step.  upper_off is recomputed (the upper rows of dead vertices are
+ * gone), the entrypoint is new(entrypoint), no slot is tombstoned, the slot count is the live count.  Capacities are unchanged: nothing is reallocated,
+ * nothing shrinks, the freed tail is what later Inserts fill.
+ * new() is monotone, neighbour order and every tie-break of a search are "ascending slot" / (distance bits, slot), and every walk skips a tombstoned
+ * neighbour before anything else — so ids, score bits, counts, n_dist, n_exp and n_hops of every search are what they were before the call, and the
+ * stream of coltt_hnsw_commit (live vertices in ascending slot order per shard, dead neighbours skipped) is byte for byte the one committed before it.
+ * Ids.  An index in dense-id mode (ids == NULL at every insert) that loses a slot becomes an explicit-id index; later
+ * coltt_hnsw_insert_batch_device(ids == NULL, first_id, ...) calls keep working on it.
+ * Derived state.  The neighbourhood blocks of the product-quantised walk are left stale, as coltt_hnsw_load leaves them: the next walk that reads them
+ * rebuilds.  The slots are renumbered, so filters built before the call are stale (COLTT_E_INVALID), exactly as after coltt_hnsw_load: rebuild them
+ * from their ids.  Slot-indexed tables of the caller (the metadata blobs of coltt_hnsw_commit) are renumbered by out_new_of_old.
+ * No-op.  An index without tombstones is left alone: nothing is launched, filters stay valid, the stats report slots_after == slots_before and the map
+ * is the identity.  An index whose vertices are all dead becomes the empty index and accepts Inserts afterwards.
+ * out_new_of_old (may be NULL) receives new(s) for the slots s before the call, 0xffffffff for a tombstoned one; cap_map < the slot count with a
+ * non-NULL pointer is COLTT_E_INVALID, checked before anything runs.  An index whose entrypoint is itself a tombstone while live vertices remain
+ * (Remove elects the removed entrypoint's closest listed neighbour without asking whether it is alive, hnsw.go:197-217) is refused with
+ * COLTT_E_UNSUPPORTED and left as it is: its walks start from a vertex that would be dropped.
+ * How.  In place through a staging block of stage_bytes_or_0 bytes (0 = 64 MiB), allocated for the call and freed by it.  Destination rows are swept in
+ * ascending chunks of max(64, stage_bytes / row bytes) rows per array; a chunk's sources are gathered whole into the block and then copied to their
+ * destinations — new(s) <= s, so a chunk's destinations can only overlap its own sources or those of earlier chunks.  The slots below the first tombstone
+ * do not move; their adjacency rows are re-packed where they are.  Besides the block the call allocates 4 bytes per live slot and upper row and 4 bytes per
+ * 32 slots (the source lists and the per-word rank table the renaming reads); the plan itself is coltt_hnsw_compact_map_host over the host mirrors.
+ * Locking and failure.  The call takes the index's lock exclusive: searches wait and then see the compacted index.  A refused allocation leaves the
+ * index as it was (COLTT_E_NOMEM).  A device failure part-way leaves the EMPTY index, never a half-moved one, and returns the device error. */
+typedef struct coltt_hnsw_compact_stats {
+  uint64_t slots_before, slots_after;            /* slots_after == coltt_hnsw_len */
+  uint64_t upper_rows_before, upper_rows_after;
+  uint64_t edges_dropped;                        /* adjacency entries of live vertices that named a tombstoned slot, all levels */
+  uint64_t rows_moved;                           /* live slots whose number changed */
+  uint64_t bytes_moved;                          /* bytes the move kernels wrote, staging included */
+  float    ms;                                   /* device time of the call (hipEvents on the mutation stream) */
+} coltt_hnsw_compact_stats;
+int coltt_hnsw_compact(coltt_handle_t h, uint64_t stage_bytes_or_0, uint32_t* out_new_of_old /*[cap_map], may be NULL*/, uint64_t cap_map,
+                       coltt_hnsw_compact_stats* stats /*may be NULL*/);
+/* host only, no device: the plan the call above uses.  del_bits: bit s % 32 of word s / 32 = slot s is tombstoned (NULL = none).  out_new_of_old [n_slots]
+ * (dead = 0xffffffff), out_new_upper_off [live] indexed by NEW slot (0xffffffff for a vertex of level 0), the totals; every output may be NULL. */
+int coltt_hnsw_compact_map_host(const uint32_t* del_bits, uint64_t n_slots, const int32_t* levels, uint32_t* out_new_of_old,
+                                uint32_t* out_new_upper_off, uint64_t* out_live, uint64_t* out_upper_rows);
 /* Round 4: indexes whose rows are f32 / 2-byte codes of a byte length that is a multiple of 128 (dim 128, 256, 512, 768, 1024, 1536 ...)
  * keep a second, line-transposed copy of their rows (derived data, like the adjacency-carried norms) and evaluate the level-0
  * distances of a search with EIGHT lanes per row over it — whole 128-byte lines per load instruction — in the reference's summation

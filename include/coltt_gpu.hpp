@@ -188,6 +188,19 @@ class Hnsw {
 
   void Insert(uint64_t id, const Vector& value, int vertexLevel) { check(coltt_hnsw_insert(h_, id, value.data(), vertexLevel)); }  // hnsw.go:104
   void Remove(uint64_t id) { check(coltt_hnsw_remove(h_, id)); }                                                                    // hnsw.go:191
+  // Reclaim the slots Remove left behind — an extension the reference does not have (coltt_gpu.h, "HNSW compaction"): vertex s moves to slot
+  // new(s) = live slots below s, no search answer changes, Filters built before are stale.  stage_bytes: the staging block (0 = 64 MiB);
+  // new_of_old (may be NULL) receives new() for the slots before the call, 0xffffffff for a dropped one.
+  coltt_hnsw_compact_stats Compact(uint64_t stage_bytes = 0, std::vector<uint32_t>* new_of_old = nullptr) {
+    coltt_hnsw_compact_stats st{};
+    if (!new_of_old) { check(coltt_hnsw_compact(h_, stage_bytes, nullptr, 0, &st)); return st; }
+    uint64_t n = 0;
+    check(coltt_hnsw_export_raw(h_, &n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    new_of_old->resize(n);
+    check(coltt_hnsw_compact(h_, stage_bytes, new_of_old->data(), n, &st));
+    new_of_old->resize(st.slots_before);
+    return st;
+  }
   SearchResult Search(const Vector& query, unsigned k) const {                                                                       // hnsw.go:243
     std::vector<uint64_t> ids(k); std::vector<float> sc(k); uint32_t n = 0;
     check(coltt_hnsw_search(h_, query.data(), 1, k, 0, ids.data(), sc.data(), &n, nullptr));
