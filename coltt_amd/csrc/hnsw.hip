@@ -2868,153 +2868,56 @@ int filter_path(uint64_t allowed, uint64_t n_live, uint32_t ef, int mode, uint32
   return COLTT_FILTER_WALK;
 }
 
-template <int METRIC, int QUANT>
-int launch_search_filtered(Hnsw* x, HCtx* c, const SearchGeom& sg, const HnswFilter* f, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k,
-                           uint32_t* counter, uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
-  auto kern = sg.visg ? hnsw_search_filtered_kernel<METRIC, QUANT, true> : hnsw_search_filtered_kernel<METRIC, QUANT, false>;
-  if constexpr (QUANT != Q_F8) { if (x->r8) kern = sg.visg ? hnsw_search_filtered_kernel<METRIC, QUANT, true, true> : hnsw_search_filtered_kernel<METRIC, QUANT, false, true>; }
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
-  kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
-                                        k, sg.ef, sg.ef_pad, sg.hcap, counter, oi, os, oc, stats,
-                                        x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
-                                        x->w_vepoch.as<uint32_t>() + region_base, FilterView{f->bits.as<uint32_t>(), f->slots});
-  COLTT_HIP(hipGetLastError());
-  return COLTT_OK;
-}
+// ---- What the filtered drivers share (filter_search_common, filter_batch_common, pq_filter_search_common, pq_filter_batch_common); `who` is the entry
+// point's name in the messages.
 
-template <int METRIC, int QUANT>
-int launch_filter_exact(Hnsw* x, HCtx* c, const HnswFilter* f, uint32_t nq, uint32_t k, uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
-  // geometry: up to FILT_QG queries per wave while the wave's LDS (queries + one top-k each) stays within 64 KiB (two waves per SIMD);
-  // enough (group, chunk) waves to fill the device (4096), chunks of >= 256 slots
-  const size_t qbytes = (((size_t)x->dim + 3) & ~(size_t)3) * 4, kbytes = (size_t)((k + 63) & ~63u) * 8;
-  uint32_t qg = FILT_QG;
-  while (qg > 1 && qg * (qbytes + kbytes) > 64 * 1024) qg--;
-  const size_t lds = qg * (qbytes + kbytes);
-  if (lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered: dim %u / k %u need %zu B of LDS (> 160 KiB)", x->dim, k, lds);
-  const uint32_t groups = ceil_div(nq, qg);
-  const uint64_t A = f->allowed;
-  uint64_t nchunks = std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(4096, groups), ceil_div(A, 256)));
-  while (nchunks > 1 && (uint64_t)nq * nchunks * k * 8 > (256ull << 20)) nchunks = (nchunks + 1) / 2;   // the chunk lists' workspace
-  uint64_t chunk = (A + nchunks - 1) / nchunks;
-  chunk = (chunk + 31) & ~31ull;
-  nchunks = (A + chunk - 1) / chunk;
-  COLTT_TRY(c->w_keys.reserve((size_t)nq * nchunks * k * 8));
-  COLTT_TRY(c->w_scnt.reserve((size_t)nq * nchunks * 4));
-  GraphView gv = x->view();
-  auto scan = hnsw_filter_scan_kernel<METRIC, QUANT, false>;
-  if constexpr (QUANT != Q_F8) { if (x->r8) scan = hnsw_filter_scan_kernel<METRIC, QUANT, true>; }
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  scan<<<dim3((uint32_t)nchunks, groups), 64, lds, c->stream>>>(gv, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq, qg, f->list.as<uint32_t>(), (uint32_t)A,
-                                                                (uint32_t)chunk, k, (k + 63) & ~63u, c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), stats);
-  COLTT_HIP(hipGetLastError());
-  const size_t lds2 = kbytes;
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_filter_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-  hnsw_filter_select_kernel<<<nq, 64, lds2, c->stream>>>(c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), (uint32_t)nchunks, k, gv.ids, oi, os, oc);
-  COLTT_HIP(hipGetLastError());
-  return COLTT_OK;
-}
-
-int filter_search_common(Hnsw* x, HCtx* c, const HnswFilter* f, const float* queries, size_t nq, uint32_t k, uint32_t ef_override, int mode,
-                         uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_filter_stats* st) {
-  coltt_hnsw_filter_stats local{};
-  if (!st) st = &local;
+// The argument checks and the breadth.  ef == 0 on COLTT_OK: no queries, nothing to do.
+int filter_args(const Hnsw* x, const char* who, size_t nq, uint32_t k, uint32_t ef_override, int mode, coltt_hnsw_filter_stats* st, uint32_t& ef) {
   std::memset(st, 0, sizeof(*st));
-  if (mode != COLTT_FILTER_AUTO && mode != COLTT_FILTER_WALK && mode != COLTT_FILTER_EXACT) return fail(COLTT_E_INVALID, "hnsw_search_filtered: unknown mode %d", mode);
+  ef = 0;
+  if (mode != COLTT_FILTER_AUTO && mode != COLTT_FILTER_WALK && mode != COLTT_FILTER_EXACT) return fail(COLTT_E_INVALID, "%s: unknown mode %d", who, mode);
   if (nq == 0) return COLTT_OK;
-  if (k == 0) return fail(COLTT_E_INVALID, "hnsw_search_filtered: k must be >= 1");
-  if (nq > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered: more than 2^32-1 queries in one call");
-  const uint32_t ef = std::max<uint32_t>(ef_override ? ef_override : (uint32_t)x->cfg.ef, k);   // as Search (hnsw.go:258)
-  if (ef > FILTER_EF_MAX) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered: ef=%u > %llu", ef, (unsigned long long)FILTER_EF_MAX);
-  uint32_t ef_walk = ef;
-  const int path = filter_path(f->allowed, x->live, ef, mode, ef_walk);
-  st->path = path; st->ef_walk = path == COLTT_FILTER_WALK ? ef_walk : 0;
-  if (x->entry < 0 || f->allowed == 0) {   // empty index or empty filter: counts 0, not an error
-    std::memset(out_counts, 0, nq * 4);
-    return COLTT_OK;
-  }
-  COLTT_TRY(c->w_out_ids.reserve(nq * k * 8));
-  COLTT_TRY(c->w_out_sc.reserve(nq * k * 4));
-  COLTT_TRY(c->w_out_cnt.reserve(nq * 4));
-  uint64_t* d_oi = c->w_out_ids.as<uint64_t>(); float* d_os = c->w_out_sc.as<float>(); uint32_t* d_oc = c->w_out_cnt.as<uint32_t>();
-  SearchGeom sg{};
-  uint32_t grid = 0;
-  RegionLease lease;
-  if (path == COLTT_FILTER_WALK) {
-    if (wants_visg(ef_walk)) COLTT_TRY(ensure_visg(x));
-    sg = search_geom(x, ef_walk, false, true, k);   // the one-wave walk (hnsw_dev.hpp: search_level) over the LDS hash or the HBM byte map
-    if (sg.lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered: dim/ef/k need %zu B of LDS (> 160 KiB)", sg.lds);
-    grid = std::min<uint32_t>((uint32_t)nq, resident_waves(sg, x->quant));
-    if (sg.visg) { acquire_regions(x, grid, lease); grid = lease.count; }
-  }
-  COLTT_TRY(c->w_qraw.reserve(nq * x->dim * 4));
-  COLTT_HIP(hipMemcpyAsync(c->w_qraw.p, queries, nq * x->dim * 4, hipMemcpyHostToDevice, c->stream));
-  COLTT_TRY(c->w_misc.reserve(256));
-  COLTT_TRY(c->h_out.reserve(256));
-  uint8_t* misc = c->w_misc.as<uint8_t>();
-  uint32_t* counter = reinterpret_cast<uint32_t*>(misc);
-  unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(misc + 16);
-  COLTT_TRY(prep_queries_any(x, c, c->w_qraw.as<float>(), nq, reinterpret_cast<uint32_t*>(misc)));   // Normalize / Lower the queries as Search does; clears the counters
-  COLTT_HIP(hipEventRecord(c->ev0, c->stream));
-  int rc = COLTT_OK;
-#define COLTT_FS(Q) rc = path == COLTT_FILTER_WALK \
-    ? (x->metric == COLTT_COSINE ? launch_search_filtered<M_COS, Q>(x, c, sg, f, grid, lease.base, (uint32_t)nq, k, counter, d_oi, d_os, d_oc, d_stats) \
-                                 : launch_search_filtered<M_L2, Q>(x, c, sg, f, grid, lease.base, (uint32_t)nq, k, counter, d_oi, d_os, d_oc, d_stats)) \
-    : (x->metric == COLTT_COSINE ? launch_filter_exact<M_COS, Q>(x, c, f, (uint32_t)nq, k, d_oi, d_os, d_oc, d_stats) \
-                                 : launch_filter_exact<M_L2, Q>(x, c, f, (uint32_t)nq, k, d_oi, d_os, d_oc, d_stats))
-  COLTT_DISPATCH_QUANT(x->quant, COLTT_FS)
-#undef COLTT_FS
-  COLTT_TRY(rc);
-  COLTT_HIP(hipEventRecord(c->ev1, c->stream));
-  if (x->dense && x->dense_base) add_base_kernel<<<ceil_div(nq * k, 256), 256, 0, c->stream>>>(d_oi, nq * k, x->dense_base);
-  COLTT_HIP(hipMemcpyAsync(out_ids, d_oi, nq * k * 8, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(out_scores, d_os, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(out_counts, d_oc, nq * 4, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 48, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipStreamSynchronize(c->stream));   // the lease (destructor) outlives the kernel
-  unsigned long long h_stats[6];
-  std::memcpy(h_stats, c->h_out.p, 48);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-  x->last_ms.store(ms);
-  if (h_stats[4]) return fail(COLTT_E_DEVICE, "hnsw_search_filtered: traversal watchdog tripped (code %llu)", h_stats[4]);
-  st->n_dist = h_stats[0]; st->n_exp = h_stats[1]; st->n_hops = h_stats[2]; st->n_visit_resets = h_stats[3]; st->n_exact_rows = h_stats[5];
+  if (k == 0) return fail(COLTT_E_INVALID, "%s: k must be >= 1", who);
+  if (nq > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "%s: more than 2^32-1 queries in one call", who);
+  const uint32_t e = std::max<uint32_t>(ef_override ? ef_override : (uint32_t)x->cfg.ef, k);   // as Search (hnsw.go:258)
+  if (e > FILTER_EF_MAX) return fail(COLTT_E_UNSUPPORTED, "%s: ef=%u > %llu", who, e, (unsigned long long)FILTER_EF_MAX);
+  ef = e;
   return COLTT_OK;
 }
 
-
-// coltt_hnsw_pq_search_filtered (the entry point has checked that the index carries codes): the path is filter_path's, word for word; EXACT is filter_search_common's, WALK the walk over the quantiser's codes
-// at ef_walk (pq_search_once: the same grouping of queries, region lease, neighbourhood blocks and retry over the byte map) with the allowed set.
-int pq_filter_search_common(Hnsw* x, HCtx* c, const HnswFilter* f, const float* queries, size_t nq, uint32_t k, uint32_t ef_override, uint32_t rerank, int mode,
-                            uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_filter_stats* st) {
-  coltt_hnsw_filter_stats local{};
-  if (!st) st = &local;
-  std::memset(st, 0, sizeof(*st));
-  if (mode != COLTT_FILTER_AUTO && mode != COLTT_FILTER_WALK && mode != COLTT_FILTER_EXACT) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered: unknown mode %d", mode);
-  if (nq == 0) return COLTT_OK;
-  if (k == 0) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered: k must be >= 1");
-  if (nq > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search_filtered: more than 2^32-1 queries in one call");
-  const uint32_t ef = std::max<uint32_t>(ef_override ? ef_override : (uint32_t)x->cfg.ef, k);
-  if (ef > FILTER_EF_MAX) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search_filtered: ef=%u > %llu", ef, (unsigned long long)FILTER_EF_MAX);
-  uint32_t ef_walk = ef;
-  const int path = filter_path(f->allowed, x->live, ef, mode, ef_walk);
-  if (path == COLTT_FILTER_EXACT) return filter_search_common(x, c, f, queries, nq, k, ef_override, COLTT_FILTER_EXACT, out_ids, out_scores, out_counts, st);
-  st->path = COLTT_FILTER_WALK; st->ef_walk = ef_walk;
-  if (x->entry < 0 || f->allowed == 0) {   // empty index or empty filter: counts 0, not an error
-    std::memset(out_counts, 0, nq * 4);
-    return COLTT_OK;
+// Each query's path from its own filter's allowed count (n_live read once, under the caller's read lock).  walk_q / exact_q: the served
+// queries (a non-empty filter on a non-empty index); none served — only empty filters, or an empty index — is counts 0, not an error.
+struct FiltRoute {
+  std::vector<uint32_t> efw, walk_q, exact_q;
+  bool none() const { return walk_q.empty() && exact_q.empty(); }
+};
+void filter_route(const Hnsw* x, const std::vector<HnswFilter*>& fl, size_t nq, uint32_t ef, int mode, int32_t* out_paths, uint32_t* out_counts,
+                  coltt_hnsw_filter_stats* st, FiltRoute& r) {
+  const uint64_t n_live = x->live;
+  r.efw.resize(nq);
+  bool any_walk = false, any_exact = false;
+  for (size_t i = 0; i < nq; i++) {
+    const int path = filter_path(fl[i]->allowed, n_live, ef, mode, r.efw[i]);
+    if (out_paths) out_paths[i] = path;
+    if (path == COLTT_FILTER_WALK) { any_walk = true; st->ef_walk = std::max(st->ef_walk, r.efw[i]); }
+    else any_exact = true;
+    if (x->entry < 0 || fl[i]->allowed == 0) continue;
+    (path == COLTT_FILTER_WALK ? r.walk_q : r.exact_q).push_back((uint32_t)i);
   }
-  coltt_hnsw_stats ws{};
-  uint64_t n_exact = 0;
-  const FilterView fv{f->bits.as<uint32_t>(), f->slots};
-  COLTT_TRY(pq_search_filtered_walk(x, c, fv, queries, nq, k, ef_walk, rerank, out_ids, out_scores, out_counts, &ws, &n_exact));
-  st->n_dist = ws.n_dist; st->n_exp = ws.n_exp; st->n_hops = ws.n_hops; st->n_visit_resets = 0; st->n_exact_rows = n_exact;
-  return COLTT_OK;
+  st->path = any_walk && any_exact ? COLTT_FILTER_AUTO : any_walk ? COLTT_FILTER_WALK : COLTT_FILTER_EXACT;
+  if (r.none()) std::memset(out_counts, 0, nq * 4);
 }
 
+// The exact path of a batch with a filter per query (coltt_hnsw_search_filtered_batch, coltt_hnsw_pq_search_filtered_batch): the rows of exact_q
+// sorted by filter, groups of <= qg sharing one, chunk lists as launch_filter_exact sizes them.
+// eq / tiles: what the scan and the select read; d_eq / d_tiles: where filter_upload put them.
+struct FiltExactPlan {
+  uint32_t qg = 0; std::vector<FiltExactQ> eq; std::vector<FiltTile> tiles; uint64_t nlists = 0;
+  const FiltExactQ* d_eq = nullptr; const FiltTile* d_tiles = nullptr;
+};
+// The answer's three device buffers.
+struct FiltOut { uint64_t* oi; float* os; uint32_t* oc; };
 
-// ---- coltt_hnsw_search_filtered_batch: a filter per query.  Row i is the single-filter call on query i alone: its path from its own filter's
-// allowed count (filter_path), its walk at the geometry search_geom gives its ef_walk, its exact scan chunked by today's rules (the answer
-// is a pure top-k, so the chunking cannot change it).  One call launches at most two walks (LDS hash, HBM byte map), one scan, one select.
 template <int METRIC, int QUANT>
 int launch_search_filtered_batch(Hnsw* x, HCtx* c, bool visg, size_t lds, uint32_t grid, uint32_t region_base, uint32_t nw, uint32_t k,
                                  const FiltQuery* fq, uint32_t* counter, uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
@@ -3029,28 +2932,36 @@ int launch_search_filtered_batch(Hnsw* x, HCtx* c, bool visg, size_t lds, uint32
 }
 
 template <int METRIC, int QUANT>
-int launch_filter_exact_batch(Hnsw* x, HCtx* c, uint32_t qg, uint32_t ntiles, uint32_t nexact, uint64_t nlists, const FiltTile* tiles,
-                              const FiltExactQ* eq, uint32_t k, uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
+int launch_filter_exact_batch(Hnsw* x, HCtx* c, const FiltExactPlan& ep, uint32_t k, const FiltOut& o, unsigned long long* stats) {
   const size_t qbytes = (((size_t)x->dim + 3) & ~(size_t)3) * 4, kbytes = (size_t)((k + 63) & ~63u) * 8;
-  const size_t lds = qg * (qbytes + kbytes);
-  COLTT_TRY(c->w_keys.reserve((size_t)nlists * k * 8));
-  COLTT_TRY(c->w_scnt.reserve((size_t)nlists * 4));
+  const size_t lds = ep.qg * (qbytes + kbytes);
+  COLTT_TRY(c->w_keys.reserve((size_t)ep.nlists * k * 8));
+  COLTT_TRY(c->w_scnt.reserve((size_t)ep.nlists * 4));
   GraphView gv = x->view();
   auto scan = hnsw_filter_scan_batch_kernel<METRIC, QUANT, false>;
   if constexpr (QUANT != Q_F8) { if (x->r8) scan = hnsw_filter_scan_batch_kernel<METRIC, QUANT, true>; }
   COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  scan<<<ntiles, 64, lds, c->stream>>>(gv, c->w_qeff.as<float>(), c->w_qn.as<float>(), tiles, eq, qg, k, (k + 63) & ~63u,
-                                       c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), stats);
+  scan<<<(uint32_t)ep.tiles.size(), 64, lds, c->stream>>>(gv, c->w_qeff.as<float>(), c->w_qn.as<float>(), ep.d_tiles, ep.d_eq, ep.qg, k, (k + 63) & ~63u,
+                                                          c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), stats);
   COLTT_HIP(hipGetLastError());
   COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_filter_select_batch_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kbytes));
-  hnsw_filter_select_batch_kernel<><<<nexact, 64, kbytes, c->stream>>>(c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), eq, k, gv.ids, oi, os, oc);
+  hnsw_filter_select_batch_kernel<><<<(uint32_t)ep.eq.size(), 64, kbytes, c->stream>>>(c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), ep.d_eq, k, gv.ids,
+                                                                                       o.oi, o.os, o.oc);
   COLTT_HIP(hipGetLastError());
   return COLTT_OK;
 }
+// the exact scan and its select over the uploaded plan, if any query took the exact path
+int run_filter_exact(Hnsw* x, HCtx* c, const FiltExactPlan& ep, uint32_t k, const FiltOut& o, unsigned long long* d_stats) {
+  if (ep.eq.empty()) return COLTT_OK;
+  const bool cos = x->metric == COLTT_COSINE;
+  int rc = COLTT_OK;
+#define COLTT_FE(Q) rc = cos ? launch_filter_exact_batch<M_COS, Q>(x, c, ep, k, o, d_stats) : launch_filter_exact_batch<M_L2, Q>(x, c, ep, k, o, d_stats)
+  COLTT_DISPATCH_QUANT(x->quant, COLTT_FE)
+#undef COLTT_FE
+  return rc;
+}
 
-// The exact path of a batch with a filter per query (coltt_hnsw_search_filtered_batch, coltt_hnsw_pq_search_filtered_batch): the rows of exact_q sorted
-// by filter, groups of <= qg sharing one, chunk lists as launch_filter_exact sizes them.  eq / tiles: what launch_filter_exact_batch reads.
-struct FiltExactPlan { uint32_t qg = 0; std::vector<FiltExactQ> eq; std::vector<FiltTile> tiles; uint64_t nlists = 0; };
+// FiltExactPlan for the rows of exact_q (sorted in place)
 int plan_filter_exact_batch(Hnsw* x, const std::vector<HnswFilter*>& fl, std::vector<uint32_t>& exact_q, uint32_t k, const char* who, FiltExactPlan& out) {
   const size_t qbytes = (((size_t)x->dim + 3) & ~(size_t)3) * 4, kbytes = (size_t)((k + 63) & ~63u) * 8;
   uint32_t& qg = out.qg;
@@ -3100,73 +3011,186 @@ int plan_filter_exact_batch(Hnsw* x, const std::vector<HnswFilter*>& fl, std::ve
   return COLTT_OK;
 }
 
-int filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,
-                        int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, int32_t* out_paths, coltt_hnsw_filter_stats* st) {
+// One upload of every table of a call into w_fdesc — [walk descriptors w0 | w1][exact queries][tiles, 32-byte aligned] — then the answer's
+// buffers, the counts cleared.  blob is the caller's: the host copy outlives the transfer.  desc: the blob on the device (w0 at desc, w1 at desc + w0_bytes).
+int filter_upload(HCtx* c, const void* w0, size_t w0_bytes, const void* w1, size_t w1_bytes, FiltExactPlan& ep, size_t nq, uint32_t k,
+                  std::vector<uint8_t>& blob, uint8_t*& desc, FiltOut& o) {
+  const size_t o_eq = w0_bytes + w1_bytes;
+  const size_t o_t = (o_eq + ep.eq.size() * sizeof(FiltExactQ) + 31) & ~(size_t)31, o_end = o_t + ep.tiles.size() * sizeof(FiltTile);
+  blob.resize(o_end);
+  if (w0_bytes) std::memcpy(blob.data(), w0, w0_bytes);
+  if (w1_bytes) std::memcpy(blob.data() + w0_bytes, w1, w1_bytes);
+  if (!ep.eq.empty()) std::memcpy(blob.data() + o_eq, ep.eq.data(), ep.eq.size() * sizeof(FiltExactQ));
+  if (!ep.tiles.empty()) std::memcpy(blob.data() + o_t, ep.tiles.data(), ep.tiles.size() * sizeof(FiltTile));
+  COLTT_TRY(c->w_fdesc.reserve(o_end));
+  desc = c->w_fdesc.as<uint8_t>();
+  ep.d_eq = reinterpret_cast<const FiltExactQ*>(desc + o_eq);
+  ep.d_tiles = reinterpret_cast<const FiltTile*>(desc + o_t);
+  COLTT_HIP(hipMemcpyAsync(desc, blob.data(), o_end, hipMemcpyHostToDevice, c->stream));
+  COLTT_TRY(c->w_out_ids.reserve(nq * k * 8));
+  COLTT_TRY(c->w_out_sc.reserve(nq * k * 4));
+  COLTT_TRY(c->w_out_cnt.reserve(nq * 4));
+  o = FiltOut{c->w_out_ids.as<uint64_t>(), c->w_out_sc.as<float>(), c->w_out_cnt.as<uint32_t>()};
+  COLTT_HIP(hipMemsetAsync(o.oc, 0, nq * 4, c->stream));   // rows of empty filters stay at count 0
+  return COLTT_OK;
+}
+
+// The end of a call: the answer and (unless the caller has read them: have_stats) the six counters back to the host, the kernel time, the watchdog.
+int filter_finish(Hnsw* x, HCtx* c, const char* who, const FiltOut& o, size_t nq, uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                  const unsigned long long* d_stats, unsigned long long* h_stats, bool have_stats) {
+  COLTT_HIP(hipEventRecord(c->ev1, c->stream));
+  if (x->dense && x->dense_base) add_base_kernel<<<ceil_div(nq * k, 256), 256, 0, c->stream>>>(o.oi, nq * k, x->dense_base);
+  COLTT_HIP(hipMemcpyAsync(out_ids, o.oi, nq * k * 8, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipMemcpyAsync(out_scores, o.os, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipMemcpyAsync(out_counts, o.oc, nq * 4, hipMemcpyDeviceToHost, c->stream));
+  if (!have_stats) COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 48, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipStreamSynchronize(c->stream));   // the lease, the host tables and the callers' filters outlive the kernels
+  if (!have_stats) std::memcpy(h_stats, c->h_out.p, 48);
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+  x->last_ms.store(ms);
+  if (h_stats[4]) return fail(COLTT_E_DEVICE, "%s: traversal watchdog tripped (code %llu)", who, h_stats[4]);
+  return COLTT_OK;
+}
+
+// ---- coltt_hnsw_search_filtered: one filter for the whole call.
+template <int METRIC, int QUANT>
+int launch_search_filtered(Hnsw* x, HCtx* c, const SearchGeom& sg, const HnswFilter* f, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k,
+                           uint32_t* counter, uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
+  auto kern = sg.visg ? hnsw_search_filtered_kernel<METRIC, QUANT, true> : hnsw_search_filtered_kernel<METRIC, QUANT, false>;
+  if constexpr (QUANT != Q_F8) { if (x->r8) kern = sg.visg ? hnsw_search_filtered_kernel<METRIC, QUANT, true, true> : hnsw_search_filtered_kernel<METRIC, QUANT, false, true>; }
+  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
+  kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
+                                        k, sg.ef, sg.ef_pad, sg.hcap, counter, oi, os, oc, stats,
+                                        x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
+                                        x->w_vepoch.as<uint32_t>() + region_base, FilterView{f->bits.as<uint32_t>(), f->slots});
+  COLTT_HIP(hipGetLastError());
+  return COLTT_OK;
+}
+
+template <int METRIC, int QUANT>
+int launch_filter_exact(Hnsw* x, HCtx* c, const HnswFilter* f, uint32_t nq, uint32_t k, uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
+  // geometry: up to FILT_QG queries per wave while the wave's LDS (queries + one top-k each) stays within 64 KiB (two waves per SIMD);
+  // enough (group, chunk) waves to fill the device (4096), chunks of >= 256 slots
+  const size_t qbytes = (((size_t)x->dim + 3) & ~(size_t)3) * 4, kbytes = (size_t)((k + 63) & ~63u) * 8;
+  uint32_t qg = FILT_QG;
+  while (qg > 1 && qg * (qbytes + kbytes) > 64 * 1024) qg--;
+  const size_t lds = qg * (qbytes + kbytes);
+  if (lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered: dim %u / k %u need %zu B of LDS (> 160 KiB)", x->dim, k, lds);
+  const uint32_t groups = ceil_div(nq, qg);
+  const uint64_t A = f->allowed;
+  uint64_t nchunks = std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(4096, groups), ceil_div(A, 256)));
+  while (nchunks > 1 && (uint64_t)nq * nchunks * k * 8 > (256ull << 20)) nchunks = (nchunks + 1) / 2;   // the chunk lists' workspace
+  uint64_t chunk = (A + nchunks - 1) / nchunks;
+  chunk = (chunk + 31) & ~31ull;
+  nchunks = (A + chunk - 1) / chunk;
+  COLTT_TRY(c->w_keys.reserve((size_t)nq * nchunks * k * 8));
+  COLTT_TRY(c->w_scnt.reserve((size_t)nq * nchunks * 4));
+  GraphView gv = x->view();
+  auto scan = hnsw_filter_scan_kernel<METRIC, QUANT, false>;
+  if constexpr (QUANT != Q_F8) { if (x->r8) scan = hnsw_filter_scan_kernel<METRIC, QUANT, true>; }
+  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  scan<<<dim3((uint32_t)nchunks, groups), 64, lds, c->stream>>>(gv, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq, qg, f->list.as<uint32_t>(), (uint32_t)A,
+                                                                (uint32_t)chunk, k, (k + 63) & ~63u, c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), stats);
+  COLTT_HIP(hipGetLastError());
+  const size_t lds2 = kbytes;
+  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_filter_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+  hnsw_filter_select_kernel<<<nq, 64, lds2, c->stream>>>(c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), (uint32_t)nchunks, k, gv.ids, oi, os, oc);
+  COLTT_HIP(hipGetLastError());
+  return COLTT_OK;
+}
+
+int filter_search_common(Hnsw* x, HCtx* c, const HnswFilter* f, const float* queries, size_t nq, uint32_t k, uint32_t ef_override, int mode,
+                         uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_filter_stats* st) {
+  const char* const who = "hnsw_search_filtered";
   coltt_hnsw_filter_stats local{};
   if (!st) st = &local;
-  std::memset(st, 0, sizeof(*st));
-  if (mode != COLTT_FILTER_AUTO && mode != COLTT_FILTER_WALK && mode != COLTT_FILTER_EXACT) return fail(COLTT_E_INVALID, "hnsw_search_filtered_batch: unknown mode %d", mode);
-  if (nq == 0) return COLTT_OK;
-  if (k == 0) return fail(COLTT_E_INVALID, "hnsw_search_filtered_batch: k must be >= 1");
-  if (nq > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered_batch: more than 2^32-1 queries in one call");
-  const uint32_t ef = std::max<uint32_t>(ef_override ? ef_override : (uint32_t)x->cfg.ef, k);
-  if (ef > FILTER_EF_MAX) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered_batch: ef=%u > %llu", ef, (unsigned long long)FILTER_EF_MAX);
-  // each query's path, as its single-filter call would take it (n_live read once, under the caller's read lock)
-  const uint64_t n_live = x->live;
-  std::vector<uint32_t> efw(nq);
-  std::vector<uint32_t> walk_q, exact_q;   // the served queries (a non-empty filter on a non-empty index)
-  bool any_walk = false, any_exact = false, want_visg = false;
-  for (size_t i = 0; i < nq; i++) {
-    const int path = filter_path(fl[i]->allowed, n_live, ef, mode, efw[i]);
-    if (out_paths) out_paths[i] = path;
-    if (path == COLTT_FILTER_WALK) { any_walk = true; st->ef_walk = std::max(st->ef_walk, efw[i]); }
-    else any_exact = true;
-    if (x->entry < 0 || fl[i]->allowed == 0) continue;
-    if (path == COLTT_FILTER_WALK) { walk_q.push_back((uint32_t)i); want_visg |= wants_visg(efw[i]); }
-    else exact_q.push_back((uint32_t)i);
-  }
-  st->path = any_walk && any_exact ? COLTT_FILTER_AUTO : any_walk ? COLTT_FILTER_WALK : COLTT_FILTER_EXACT;
-  if (walk_q.empty() && exact_q.empty()) {   // only empty filters, or an empty index: counts 0, not an error
+  uint32_t ef;
+  COLTT_TRY(filter_args(x, who, nq, k, ef_override, mode, st, ef));
+  if (!ef) return COLTT_OK;
+  uint32_t ef_walk = ef;
+  const int path = filter_path(f->allowed, x->live, ef, mode, ef_walk);
+  st->path = path; st->ef_walk = path == COLTT_FILTER_WALK ? ef_walk : 0;
+  if (x->entry < 0 || f->allowed == 0) {   // empty index or empty filter: counts 0, not an error
     std::memset(out_counts, 0, nq * 4);
     return COLTT_OK;
   }
-  // the walks: each query's geometry is the single call's, search_geom(x, ef_walk, false, true, k); split by visited set
-  if (want_visg) COLTT_TRY(ensure_visg(x));
+  COLTT_TRY(c->w_out_ids.reserve(nq * k * 8));
+  COLTT_TRY(c->w_out_sc.reserve(nq * k * 4));
+  COLTT_TRY(c->w_out_cnt.reserve(nq * 4));
+  const FiltOut o{c->w_out_ids.as<uint64_t>(), c->w_out_sc.as<float>(), c->w_out_cnt.as<uint32_t>()};
+  SearchGeom sg{};
+  uint32_t grid = 0;
+  RegionLease lease;
+  if (path == COLTT_FILTER_WALK) {
+    if (wants_visg(ef_walk)) COLTT_TRY(ensure_visg(x));
+    sg = search_geom(x, ef_walk, false, true, k);   // the one-wave walk (hnsw_dev.hpp: search_level) over the LDS hash or the HBM byte map
+    if (sg.lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "%s: dim/ef/k need %zu B of LDS (> 160 KiB)", who, sg.lds);
+    grid = std::min<uint32_t>((uint32_t)nq, resident_waves(sg, x->quant));
+    if (sg.visg) { acquire_regions(x, grid, lease); grid = lease.count; }
+  }
+  COLTT_TRY(c->w_qraw.reserve(nq * x->dim * 4));
+  COLTT_HIP(hipMemcpyAsync(c->w_qraw.p, queries, nq * x->dim * 4, hipMemcpyHostToDevice, c->stream));
+  COLTT_TRY(c->w_misc.reserve(256));
+  COLTT_TRY(c->h_out.reserve(256));
+  uint8_t* misc = c->w_misc.as<uint8_t>();
+  uint32_t* counter = reinterpret_cast<uint32_t*>(misc);
+  unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(misc + 16);
+  COLTT_TRY(prep_queries_any(x, c, c->w_qraw.as<float>(), nq, reinterpret_cast<uint32_t*>(misc)));   // Normalize / Lower the queries as Search does; clears the counters
+  COLTT_HIP(hipEventRecord(c->ev0, c->stream));
+  int rc = COLTT_OK;
+#define COLTT_FS(Q) rc = path == COLTT_FILTER_WALK \
+    ? (x->metric == COLTT_COSINE ? launch_search_filtered<M_COS, Q>(x, c, sg, f, grid, lease.base, (uint32_t)nq, k, counter, o.oi, o.os, o.oc, d_stats) \
+                                 : launch_search_filtered<M_L2, Q>(x, c, sg, f, grid, lease.base, (uint32_t)nq, k, counter, o.oi, o.os, o.oc, d_stats)) \
+    : (x->metric == COLTT_COSINE ? launch_filter_exact<M_COS, Q>(x, c, f, (uint32_t)nq, k, o.oi, o.os, o.oc, d_stats) \
+                                 : launch_filter_exact<M_L2, Q>(x, c, f, (uint32_t)nq, k, o.oi, o.os, o.oc, d_stats))
+  COLTT_DISPATCH_QUANT(x->quant, COLTT_FS)
+#undef COLTT_FS
+  COLTT_TRY(rc);
+  unsigned long long h_stats[6];
+  COLTT_TRY(filter_finish(x, c, who, o, nq, k, out_ids, out_scores, out_counts, d_stats, h_stats, false));
+  st->n_dist = h_stats[0]; st->n_exp = h_stats[1]; st->n_hops = h_stats[2]; st->n_visit_resets = h_stats[3]; st->n_exact_rows = h_stats[5];
+  return COLTT_OK;
+}
+
+// ---- coltt_hnsw_search_filtered_batch: a filter per query.  Row i is the single-filter call on query i alone: its path from its own filter's
+// allowed count (filter_path), its walk at the geometry search_geom gives its ef_walk, its exact scan chunked by launch_filter_exact's rule (the
+// answer is a pure top-k, so the chunking cannot change it).  One call launches at most two walks (LDS hash, HBM byte map), one scan, one select.
+int filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,
+                        int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, int32_t* out_paths, coltt_hnsw_filter_stats* st) {
+  const char* const who = "hnsw_search_filtered_batch";
+  coltt_hnsw_filter_stats local{};
+  if (!st) st = &local;
+  uint32_t ef;
+  COLTT_TRY(filter_args(x, who, nq, k, ef_override, mode, st, ef));
+  if (!ef) return COLTT_OK;
+  FiltRoute rt;
+  filter_route(x, fl, nq, ef, mode, out_paths, out_counts, st, rt);
+  if (rt.none()) return COLTT_OK;
+  // the walks: each query's geometry is search_geom(x, ef_walk, false, true, k), the one-wave walk (hnsw_dev.hpp: search_level) over the LDS hash
+  // or the HBM byte map; split by visited set
+  for (uint32_t i : rt.walk_q)
+    if (wants_visg(rt.efw[i])) { COLTT_TRY(ensure_visg(x)); break; }
   std::map<uint32_t, SearchGeom> geoms;
   std::vector<FiltQuery> wq[2];
   SearchGeom wmax[2]{};
-  for (uint32_t i : walk_q) {
-    auto it = geoms.find(efw[i]);
-    if (it == geoms.end()) it = geoms.emplace(efw[i], search_geom(x, efw[i], false, true, k)).first;
+  for (uint32_t i : rt.walk_q) {
+    auto it = geoms.find(rt.efw[i]);
+    if (it == geoms.end()) it = geoms.emplace(rt.efw[i], search_geom(x, rt.efw[i], false, true, k)).first;
     const SearchGeom& sg = it->second;
-    if (sg.lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered_batch: dim/ef/k need %zu B of LDS (> 160 KiB)", sg.lds);
+    if (sg.lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "%s: dim/ef/k need %zu B of LDS (> 160 KiB)", who, sg.lds);
     const int v = sg.visg ? 1 : 0;
     wq[v].push_back(FiltQuery{fl[i]->bits.as<uint32_t>(), fl[i]->slots, sg.ef, sg.ef_pad, sg.hcap, i, 0u});
     if (wq[v].size() == 1 || sg.lds > wmax[v].lds) wmax[v] = sg;   // the launch's LDS: its largest query's
   }
-  // the exact path: queries sorted by filter, groups of <= qg sharing one, chunk lists as launch_filter_exact sizes them
   FiltExactPlan ep;
-  COLTT_TRY(plan_filter_exact_batch(x, fl, exact_q, k, "hnsw_search_filtered_batch", ep));
-  const uint32_t qg = ep.qg;
-  const std::vector<FiltExactQ>& eq = ep.eq;
-  const std::vector<FiltTile>& tiles = ep.tiles;
-  const uint64_t nlists = ep.nlists;
-  // one upload of every table: [walks over the LDS hash][walks over the byte map][exact queries][tiles]
-  const size_t o_w1 = wq[0].size() * sizeof(FiltQuery), o_eq = o_w1 + wq[1].size() * sizeof(FiltQuery);
-  const size_t o_t = (o_eq + eq.size() * sizeof(FiltExactQ) + 31) & ~(size_t)31, o_end = o_t + tiles.size() * sizeof(FiltTile);
-  std::vector<uint8_t> blob(o_end);
-  if (!wq[0].empty()) std::memcpy(blob.data(), wq[0].data(), wq[0].size() * sizeof(FiltQuery));
-  if (!wq[1].empty()) std::memcpy(blob.data() + o_w1, wq[1].data(), wq[1].size() * sizeof(FiltQuery));
-  if (!eq.empty()) std::memcpy(blob.data() + o_eq, eq.data(), eq.size() * sizeof(FiltExactQ));
-  if (!tiles.empty()) std::memcpy(blob.data() + o_t, tiles.data(), tiles.size() * sizeof(FiltTile));
-  COLTT_TRY(c->w_fdesc.reserve(o_end));
-  uint8_t* d_desc = c->w_fdesc.as<uint8_t>();
-  COLTT_HIP(hipMemcpyAsync(d_desc, blob.data(), o_end, hipMemcpyHostToDevice, c->stream));
-  COLTT_TRY(c->w_out_ids.reserve(nq * k * 8));
-  COLTT_TRY(c->w_out_sc.reserve(nq * k * 4));
-  COLTT_TRY(c->w_out_cnt.reserve(nq * 4));
-  uint64_t* d_oi = c->w_out_ids.as<uint64_t>(); float* d_os = c->w_out_sc.as<float>(); uint32_t* d_oc = c->w_out_cnt.as<uint32_t>();
-  COLTT_HIP(hipMemsetAsync(d_oc, 0, nq * 4, c->stream));   // rows of empty filters stay at count 0
+  COLTT_TRY(plan_filter_exact_batch(x, fl, rt.exact_q, k, who, ep));
+  // the tables: [walks over the LDS hash][walks over the byte map][exact queries][tiles]
+  std::vector<uint8_t> blob;
+  uint8_t* d_desc;
+  FiltOut o;
+  const size_t w0_bytes = wq[0].size() * sizeof(FiltQuery);
+  COLTT_TRY(filter_upload(c, wq[0].data(), w0_bytes, wq[1].data(), wq[1].size() * sizeof(FiltQuery), ep, nq, k, blob, d_desc, o));
   uint32_t grid[2] = {0, 0};
   RegionLease lease;
   for (int v = 0; v < 2; v++) if (!wq[v].empty()) grid[v] = std::min<uint32_t>((uint32_t)wq[v].size(), resident_waves(wmax[v], x->quant));
@@ -3178,43 +3202,49 @@ int filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, co
   uint8_t* misc = c->w_misc.as<uint8_t>();
   uint32_t* counters = reinterpret_cast<uint32_t*>(misc);   // [0]: the LDS-hash walk's work counter, [1]: the byte-map walk's
   unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(misc + 16);
-  COLTT_TRY(prep_queries_any(x, c, c->w_qraw.as<float>(), nq, reinterpret_cast<uint32_t*>(misc)));   // as the single call; clears the counters
+  COLTT_TRY(prep_queries_any(x, c, c->w_qraw.as<float>(), nq, reinterpret_cast<uint32_t*>(misc)));   // Normalize / Lower the queries as Search does; clears the counters
   COLTT_HIP(hipEventRecord(c->ev0, c->stream));
   int rc = COLTT_OK;
   const bool cos = x->metric == COLTT_COSINE;
   for (int v = 0; v < 2 && rc == COLTT_OK; v++) {
     if (!grid[v]) continue;
-    const FiltQuery* fq = reinterpret_cast<const FiltQuery*>(d_desc + (v ? o_w1 : 0));
+    const FiltQuery* fq = reinterpret_cast<const FiltQuery*>(d_desc + (v ? w0_bytes : 0));
     const uint32_t nw = (uint32_t)wq[v].size();
-#define COLTT_FW(Q) rc = cos ? launch_search_filtered_batch<M_COS, Q>(x, c, v == 1, wmax[v].lds, grid[v], lease.base, nw, k, fq, counters + v, d_oi, d_os, d_oc, d_stats) \
-                         : launch_search_filtered_batch<M_L2, Q>(x, c, v == 1, wmax[v].lds, grid[v], lease.base, nw, k, fq, counters + v, d_oi, d_os, d_oc, d_stats)
+#define COLTT_FW(Q) rc = cos ? launch_search_filtered_batch<M_COS, Q>(x, c, v == 1, wmax[v].lds, grid[v], lease.base, nw, k, fq, counters + v, o.oi, o.os, o.oc, d_stats) \
+                         : launch_search_filtered_batch<M_L2, Q>(x, c, v == 1, wmax[v].lds, grid[v], lease.base, nw, k, fq, counters + v, o.oi, o.os, o.oc, d_stats)
     COLTT_DISPATCH_QUANT(x->quant, COLTT_FW)
 #undef COLTT_FW
   }
   COLTT_TRY(rc);
-  if (!eq.empty()) {
-    const FiltTile* d_tiles = reinterpret_cast<const FiltTile*>(d_desc + o_t);
-    const FiltExactQ* d_eq = reinterpret_cast<const FiltExactQ*>(d_desc + o_eq);
-#define COLTT_FE(Q) rc = cos ? launch_filter_exact_batch<M_COS, Q>(x, c, qg, (uint32_t)tiles.size(), (uint32_t)eq.size(), nlists, d_tiles, d_eq, k, d_oi, d_os, d_oc, d_stats) \
-                         : launch_filter_exact_batch<M_L2, Q>(x, c, qg, (uint32_t)tiles.size(), (uint32_t)eq.size(), nlists, d_tiles, d_eq, k, d_oi, d_os, d_oc, d_stats)
-    COLTT_DISPATCH_QUANT(x->quant, COLTT_FE)
-#undef COLTT_FE
-    COLTT_TRY(rc);
-  }
-  COLTT_HIP(hipEventRecord(c->ev1, c->stream));
-  if (x->dense && x->dense_base) add_base_kernel<<<ceil_div(nq * k, 256), 256, 0, c->stream>>>(d_oi, nq * k, x->dense_base);
-  COLTT_HIP(hipMemcpyAsync(out_ids, d_oi, nq * k * 8, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(out_scores, d_os, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(out_counts, d_oc, nq * 4, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 48, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipStreamSynchronize(c->stream));   // the lease, the host tables and the callers' filters outlive the kernels
+  COLTT_TRY(run_filter_exact(x, c, ep, k, o, d_stats));
   unsigned long long h_stats[6];
-  std::memcpy(h_stats, c->h_out.p, 48);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-  x->last_ms.store(ms);
-  if (h_stats[4]) return fail(COLTT_E_DEVICE, "hnsw_search_filtered_batch: traversal watchdog tripped (code %llu)", h_stats[4]);
+  COLTT_TRY(filter_finish(x, c, who, o, nq, k, out_ids, out_scores, out_counts, d_stats, h_stats, false));
   st->n_dist = h_stats[0]; st->n_exp = h_stats[1]; st->n_hops = h_stats[2]; st->n_visit_resets = h_stats[3]; st->n_exact_rows = h_stats[5];
+  return COLTT_OK;
+}
+
+// coltt_hnsw_pq_search_filtered (the entry point has checked that the index carries codes): the path is filter_path's, word for word; EXACT is filter_search_common's, WALK the walk over the quantiser's codes
+// at ef_walk (pq_search_once: the same grouping of queries, region lease, neighbourhood blocks and retry over the byte map) with the allowed set.
+int pq_filter_search_common(Hnsw* x, HCtx* c, const HnswFilter* f, const float* queries, size_t nq, uint32_t k, uint32_t ef_override, uint32_t rerank, int mode,
+                            uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_filter_stats* st) {
+  coltt_hnsw_filter_stats local{};
+  if (!st) st = &local;
+  uint32_t ef;
+  COLTT_TRY(filter_args(x, "hnsw_pq_search_filtered", nq, k, ef_override, mode, st, ef));
+  if (!ef) return COLTT_OK;
+  uint32_t ef_walk = ef;
+  const int path = filter_path(f->allowed, x->live, ef, mode, ef_walk);
+  if (path == COLTT_FILTER_EXACT) return filter_search_common(x, c, f, queries, nq, k, ef_override, COLTT_FILTER_EXACT, out_ids, out_scores, out_counts, st);
+  st->path = COLTT_FILTER_WALK; st->ef_walk = ef_walk;
+  if (x->entry < 0 || f->allowed == 0) {   // empty index or empty filter: counts 0, not an error
+    std::memset(out_counts, 0, nq * 4);
+    return COLTT_OK;
+  }
+  coltt_hnsw_stats ws{};
+  uint64_t n_exact = 0;
+  const FilterView fv{f->bits.as<uint32_t>(), f->slots};
+  COLTT_TRY(pq_search_filtered_walk(x, c, fv, queries, nq, k, ef_walk, rerank, out_ids, out_scores, out_counts, &ws, &n_exact));
+  st->n_dist = ws.n_dist; st->n_exp = ws.n_exp; st->n_hops = ws.n_hops; st->n_visit_resets = 0; st->n_exact_rows = n_exact;
   return COLTT_OK;
 }
 
@@ -3234,36 +3264,18 @@ __global__ void pq_gather_queries_kernel(const float* __restrict__ q_eff, const 
 int pq_filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,
                            uint32_t rerank, int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, int32_t* out_paths,
                            coltt_hnsw_filter_stats* st) {
+  const char* const who = "hnsw_pq_search_filtered_batch";
   coltt_hnsw_filter_stats local{};
   if (!st) st = &local;
-  std::memset(st, 0, sizeof(*st));
-  if (mode != COLTT_FILTER_AUTO && mode != COLTT_FILTER_WALK && mode != COLTT_FILTER_EXACT) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: unknown mode %d", mode);
-  if (nq == 0) return COLTT_OK;
-  if (k == 0) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: k must be >= 1");
-  if (nq > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search_filtered_batch: more than 2^32-1 queries in one call");
-  const uint32_t ef = std::max<uint32_t>(ef_override ? ef_override : (uint32_t)x->cfg.ef, k);
-  if (ef > FILTER_EF_MAX) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search_filtered_batch: ef=%u > %llu", ef, (unsigned long long)FILTER_EF_MAX);
-  // each query's path, as its single-filter call would take it (n_live read once, under the caller's read lock)
-  const uint64_t n_live = x->live;
-  std::vector<uint32_t> efw(nq);
-  std::vector<uint32_t> walk_q, exact_q;   // the served queries (a non-empty filter on a non-empty index)
-  bool any_walk = false, any_exact = false;
-  for (size_t i = 0; i < nq; i++) {
-    const int path = filter_path(fl[i]->allowed, n_live, ef, mode, efw[i]);
-    if (out_paths) out_paths[i] = path;
-    if (path == COLTT_FILTER_WALK) { any_walk = true; st->ef_walk = std::max(st->ef_walk, efw[i]); }
-    else any_exact = true;
-    if (x->entry < 0 || fl[i]->allowed == 0) continue;
-    if (path == COLTT_FILTER_WALK) walk_q.push_back((uint32_t)i);
-    else exact_q.push_back((uint32_t)i);
-  }
-  st->path = any_walk && any_exact ? COLTT_FILTER_AUTO : any_walk ? COLTT_FILTER_WALK : COLTT_FILTER_EXACT;
-  if (walk_q.empty() && exact_q.empty()) {   // only empty filters, or an empty index: counts 0, not an error
-    std::memset(out_counts, 0, nq * 4);
-    return COLTT_OK;
-  }
-  if (!walk_q.empty() && x->pq_done != x->n)
-    return fail(COLTT_E_DEVICE, "hnsw_pq_search_filtered_batch: codes cover %llu of %llu slots", (unsigned long long)x->pq_done, (unsigned long long)x->n);
+  uint32_t ef;
+  COLTT_TRY(filter_args(x, who, nq, k, ef_override, mode, st, ef));
+  if (!ef) return COLTT_OK;
+  FiltRoute rt;
+  filter_route(x, fl, nq, ef, mode, out_paths, out_counts, st, rt);
+  if (rt.none()) return COLTT_OK;
+  const std::vector<uint32_t>& efw = rt.efw;
+  if (!rt.walk_q.empty() && x->pq_done != x->n)
+    return fail(COLTT_E_DEVICE, "%s: codes cover %llu of %llu slots", who, (unsigned long long)x->pq_done, (unsigned long long)x->n);
   // the walks: each query's geometry is the single call's for its ef_walk; split by visited set.  A launch takes the LDS of its largest query, keeps
   // as many traversals per CU as that one allows, and its survivors' rows are as long as its longest result set
   struct Launch { std::vector<PqFiltQuery> q; size_t lds = 0; uint32_t ef_pad = 0, per_cu = 0; };
@@ -3275,7 +3287,7 @@ int pq_filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl,
   };
   {
     std::map<uint32_t, PqGeom> geoms;
-    for (uint32_t i : walk_q) {
+    for (uint32_t i : rt.walk_q) {
       const uint32_t fcap = pq_filt_cap(efw[i], k, rerank);
       auto it = geoms.find(efw[i]);
       if (it == geoms.end()) {
@@ -3287,25 +3299,14 @@ int pq_filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl,
     }
   }
   FiltExactPlan ep;
-  COLTT_TRY(plan_filter_exact_batch(x, fl, exact_q, k, "hnsw_pq_search_filtered_batch", ep));
-  // one upload of every table: [walks over the LDS hash][walks over the byte map][exact queries][tiles]
+  COLTT_TRY(plan_filter_exact_batch(x, fl, rt.exact_q, k, who, ep));
+  // the tables: [walks over the LDS hash][walks over the byte map][exact queries][tiles]
   const size_t nw0 = wl[0].q.size(), nw1 = wl[1].q.size(), nw = nw0 + nw1;
-  const size_t o_eq = nw * sizeof(PqFiltQuery);
-  const size_t o_t = (o_eq + ep.eq.size() * sizeof(FiltExactQ) + 31) & ~(size_t)31, o_end = o_t + ep.tiles.size() * sizeof(FiltTile);
-  std::vector<uint8_t> blob(o_end);
-  if (nw0) std::memcpy(blob.data(), wl[0].q.data(), nw0 * sizeof(PqFiltQuery));
-  if (nw1) std::memcpy(blob.data() + nw0 * sizeof(PqFiltQuery), wl[1].q.data(), nw1 * sizeof(PqFiltQuery));
-  if (!ep.eq.empty()) std::memcpy(blob.data() + o_eq, ep.eq.data(), ep.eq.size() * sizeof(FiltExactQ));
-  if (!ep.tiles.empty()) std::memcpy(blob.data() + o_t, ep.tiles.data(), ep.tiles.size() * sizeof(FiltTile));
-  COLTT_TRY(c->w_fdesc.reserve(o_end));
-  uint8_t* d_desc = c->w_fdesc.as<uint8_t>();
+  std::vector<uint8_t> blob;
+  uint8_t* d_desc;
+  FiltOut o;
+  COLTT_TRY(filter_upload(c, wl[0].q.data(), nw0 * sizeof(PqFiltQuery), wl[1].q.data(), nw1 * sizeof(PqFiltQuery), ep, nq, k, blob, d_desc, o));
   PqFiltQuery* d_pd = reinterpret_cast<PqFiltQuery*>(d_desc);
-  COLTT_HIP(hipMemcpyAsync(d_desc, blob.data(), o_end, hipMemcpyHostToDevice, c->stream));
-  COLTT_TRY(c->w_out_ids.reserve(nq * k * 8));
-  COLTT_TRY(c->w_out_sc.reserve(nq * k * 4));
-  COLTT_TRY(c->w_out_cnt.reserve(nq * 4));
-  uint64_t* d_oi = c->w_out_ids.as<uint64_t>(); float* d_os = c->w_out_sc.as<float>(); uint32_t* d_oc = c->w_out_cnt.as<uint32_t>();
-  COLTT_HIP(hipMemsetAsync(d_oc, 0, nq * 4, c->stream));   // rows of empty filters stay at count 0
   RegionLease lease;
   bool nbr = false, nbr_known = false;
   auto byte_map_ready = [&](uint32_t want) -> int {   // one lease and one look at the neighbourhood blocks per call
@@ -3350,7 +3351,7 @@ int pq_filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl,
       COLTT_TRY(launch_pq_walk(x, c, sg, nbr, (uint32_t)std::min<size_t>(grid, gn), lease.base, c->w_pack.as<unsigned short>(), (uint32_t)gn, k, rerank, counter,
                                c->w_surv.as<uint32_t>(), c->w_scnt.as<uint32_t>(), d_stats, nullptr, 0u, pd + g0));
       int rc;
-#define COLTT_LP_ARGS x, c, sg, 0u, (uint32_t)gn, k, c->w_surv.as<uint32_t>(), c->w_scnt.as<uint32_t>(), c->w_keys.as<unsigned long long>(), d_oi, d_os, d_oc, pd + g0, cq + (j0 + g0) * dim, cn + j0 + g0
+#define COLTT_LP_ARGS x, c, sg, 0u, (uint32_t)gn, k, c->w_surv.as<uint32_t>(), c->w_scnt.as<uint32_t>(), c->w_keys.as<unsigned long long>(), o.oi, o.os, o.oc, pd + g0, cq + (j0 + g0) * dim, cn + j0 + g0
 #define COLTT_LP(Q) rc = cos ? launch_pq_rerank<M_COS, Q>(COLTT_LP_ARGS) : launch_pq_rerank<M_L2, Q>(COLTT_LP_ARGS)
       if (x->quant == COLTT_Q_NONE) { COLTT_LP(Q_NONE); } else { COLTT_LP(Q_F16); }
 #undef COLTT_LP
@@ -3361,16 +3362,7 @@ int pq_filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl,
   };
   if (nw0) COLTT_TRY(run_walks(wl[0], 0, d_pd, 0, nw0));
   if (nw1) COLTT_TRY(run_walks(wl[1], 2, d_pd + nw0, nw0, nw1));
-  if (!ep.eq.empty()) {
-    const FiltTile* d_tiles = reinterpret_cast<const FiltTile*>(d_desc + o_t);
-    const FiltExactQ* d_eq = reinterpret_cast<const FiltExactQ*>(d_desc + o_eq);
-    int rc = COLTT_OK;
-#define COLTT_FE(Q) rc = cos ? launch_filter_exact_batch<M_COS, Q>(x, c, ep.qg, (uint32_t)ep.tiles.size(), (uint32_t)ep.eq.size(), ep.nlists, d_tiles, d_eq, k, d_oi, d_os, d_oc, d_stats) \
-                         : launch_filter_exact_batch<M_L2, Q>(x, c, ep.qg, (uint32_t)ep.tiles.size(), (uint32_t)ep.eq.size(), ep.nlists, d_tiles, d_eq, k, d_oi, d_os, d_oc, d_stats)
-    COLTT_DISPATCH_QUANT(x->quant, COLTT_FE)
-#undef COLTT_FE
-    COLTT_TRY(rc);
-  }
+  COLTT_TRY(run_filter_exact(x, c, ep, k, o, d_stats));
   unsigned long long h_stats[6];
   COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 48, hipMemcpyDeviceToHost, c->stream));
   COLTT_HIP(hipStreamSynchronize(c->stream));
@@ -3399,19 +3391,7 @@ int pq_filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl,
     COLTT_HIP(hipStreamSynchronize(c->stream));
     std::memcpy(h_stats, c->h_out.p, 48);
   }
-  COLTT_HIP(hipEventRecord(c->ev1, c->stream));
-  if (h_stats[4]) {
-    COLTT_HIP(hipStreamSynchronize(c->stream));
-    return fail(COLTT_E_DEVICE, "hnsw_pq_search_filtered_batch: traversal watchdog tripped (code %llu)", h_stats[4]);
-  }
-  if (x->dense && x->dense_base) add_base_kernel<<<ceil_div(nq * k, 256), 256, 0, c->stream>>>(d_oi, nq * k, x->dense_base);
-  COLTT_HIP(hipMemcpyAsync(out_ids, d_oi, nq * k * 8, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(out_scores, d_os, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(out_counts, d_oc, nq * 4, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipStreamSynchronize(c->stream));   // the lease, the host tables and the callers' filters outlive the kernels
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-  x->last_ms.store(ms);
+  COLTT_TRY(filter_finish(x, c, who, o, nq, k, out_ids, out_scores, out_counts, d_stats, h_stats, true));
   // [3]: the members of R the walks handed to the re-rank, [5]: the rows the exact scan read
   st->n_dist = h_stats[0]; st->n_exp = h_stats[1]; st->n_hops = h_stats[2]; st->n_visit_resets = 0; st->n_exact_rows = h_stats[3] + h_stats[5];
   return COLTT_OK;
