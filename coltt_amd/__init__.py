@@ -12,6 +12,8 @@ from .flat import FlatSpace  # noqa: F401
 from .hnsw import Hnsw, HnswCfg, HnswFilter, FILTER_AUTO, FILTER_WALK, FILTER_EXACT  # noqa: F401
 from .hnsw import HnswCompactStats, compact_map_host  # noqa: F401
 from .hnsw import FOP_AND, FOP_OR, FOP_ANDNOT, FOP_NOT, FOP_ALL, filter_postfix, filter_tree, filter_prog_check  # noqa: F401
+from .hnsw import (HnswAttrColumn, AttrPred, attr_cmp_host, ATTR_I64, ATTR_F64,  # noqa: F401
+                   CMP_EQ, CMP_NE, CMP_GT, CMP_GE, CMP_LT, CMP_LE, CMP_SET)
 from .cflat import MultiVectorSpace  # noqa: F401
 from .pq import PQSpace, PQ_COSINE, PQ_EUCLIDEAN, PQ_DOT  # noqa: F401
 from . import kernels  # noqa: F401

@@ -24,6 +24,7 @@
 
 #include "hnsw_kernels.hpp"   // the search kernels (one-wave walk, large-ef walk, latency kernel, walk over PQ codes + re-rank)
 #include "filter_expr.hpp"    // filter expressions: evaluate, compact, read-back
+#include "attr_filter.hpp"    // attribute columns: predicate leaves of a filter programme, scatter, gather
 #include "hnsw_compact.hpp"   // coltt_hnsw_compact: the plan, the row movers, the adjacency re-pack
 
 using namespace coltt;
@@ -2850,6 +2851,32 @@ struct HnswFilter : Object {
   }
 };
 
+// An attribute column (coltt_hnsw_attr_*; include/coltt_gpu.h, "Attribute columns and predicates").  `rw` is the column's own lock: attr_set holds
+// it exclusive (and the index's shared), attr_get and an evaluation hold it shared.
+struct HnswAttr : Object {
+  coltt_handle_t index = 0; uint64_t gen = 0;   // as HnswFilter
+  int type = COLTT_ATTR_I64;
+  uint32_t slots = 0;            // covered: the index's slot count at the last attr_set
+  uint64_t cap = 0, n_set = 0;   // slots allocated; slots that hold a value
+  DevBuf vals;                   // [cap] 8-byte values
+  DevBuf set;                    // [ceil(cap / 32)] u32, bit s = slot s holds a value; words past the covered slots are 0
+  std::vector<uint32_t> h_set;   // its mirror
+  ~HnswAttr() override { (void)hipSetDevice(device); }
+};
+
+// id -> live slot, as coltt_hnsw_filter_create maps it (the caller holds the index's lock); false: unknown or removed
+inline bool live_slot_of(const Hnsw* x, uint64_t id, uint32_t& s) {
+  if (x->dense) {
+    if (id < x->dense_base || id - x->dense_base >= x->n) return false;
+    s = (uint32_t)(id - x->dense_base);
+    return !(x->h_del.size() > (s >> 5) && ((x->h_del[s >> 5] >> (s & 31)) & 1u));
+  }
+  auto it = x->id2slot.find(id);
+  if (it == x->id2slot.end()) return false;
+  s = it->second;
+  return true;
+}
+
 // AUTO: with A allowed vertices out of n_live, a walk at ef meets about ef * A / n_live allowed ones among its result-set-sized share of
 // the walk; ef_need raises the breadth so that about ef of them are met.  The exact scan reads A rows and has no dependent chain; the walk
 // evaluates about 32 rows per unit of ef (n_dist / ef = 4 040 / 128 on the headline collection), so the scan wins on rows read while
@@ -3400,19 +3427,23 @@ int pq_filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl,
 // coltt_hnsw_filter_eval / _eval_batch (definitions: include/coltt_gpu.h, "Filter expressions"; kernels: filter_expr.hpp).  n_out programmes
 // over one leaf table under one index state: one upload (leaf table, programme offsets, programmes), the evaluate launch, the counts back
 // (they size the lists), the list offsets up, the compact launch.  The outputs' bitmaps and lists are slices of one slab each.
+// With predicates (coltt_hnsw_filter_eval_attr / _eval_attr_batch; attr_filter.hpp) the predicate table rides in the same upload and the
+// evaluate launch is attr_filter_eval_kernel; without any, the launch is filter_eval_kernel as before.
 int filter_eval_common(coltt_handle_t h, const char* who, const int32_t* progs, const uint64_t* prog_off, size_t n_out,
-                       const coltt_handle_t* leaves, size_t n_leaves, uint64_t* out_allowed, coltt_handle_t* out) {
+                       const coltt_handle_t* leaves, size_t n_leaves, const coltt_attr_pred* preds, size_t n_preds,
+                       uint64_t* out_allowed, coltt_handle_t* out) {
   auto x = lookup<Hnsw>(h);
   if (!x) return fail(COLTT_E_NOT_FOUND, "%s: unknown index handle", who);
   if (n_out == 0) return COLTT_OK;
   if (!out) return fail(COLTT_E_INVALID, "%s: out is NULL", who);
   if (!prog_off) return fail(COLTT_E_INVALID, "%s: NULL programme offsets", who);
   if (n_leaves && !leaves) return fail(COLTT_E_INVALID, "%s: NULL leaves", who);
+  if (n_preds && !preds) return fail(COLTT_E_INVALID, "%s: NULL preds", who);
   uint64_t total = 0;
   for (size_t i = 0; i < n_out; i++) {   // every programme is checked before anything is created
     if (prog_off[i + 1] < prog_off[i]) return fail(COLTT_E_INVALID, "%s: programme %zu: its offsets descend", who, i);
     const uint64_t len = prog_off[i + 1] - prog_off[i];
-    const int rc = coltt_hnsw_filter_prog_check_host(progs ? progs + prog_off[i] : nullptr, (size_t)len, n_leaves, nullptr);
+    const int rc = coltt_hnsw_filter_prog_check_host(progs ? progs + prog_off[i] : nullptr, (size_t)len, n_leaves + n_preds, nullptr);
     if (rc != COLTT_OK) {
       const std::string why = coltt_last_error();
       return fail(rc, "%s: programme %zu: %s", who, i, why.c_str());
@@ -3433,6 +3464,27 @@ int filter_eval_common(coltt_handle_t h, const char* who, const int32_t* progs, 
     }
     lf[i] = it->second.get();
   }
+  // each distinct column: held, and locked shared until the call returns (the call sees it wholly before or wholly after a concurrent attr_set)
+  std::unordered_map<coltt_handle_t, std::shared_ptr<HnswAttr>> cheld;
+  std::vector<ReadLock> clocks;
+  std::vector<HnswAttr*> pc(n_preds);
+  for (size_t i = 0; i < n_preds; i++) {
+    const coltt_attr_pred& P = preds[i];
+    auto it = cheld.find(P.column);
+    if (it == cheld.end()) {
+      auto a = lookup<HnswAttr>(P.column);
+      if (!a) return fail(COLTT_E_NOT_FOUND, "%s: unknown column handle at predicate %zu", who, i);
+      if (a->index != h) return fail(COLTT_E_INVALID, "%s: the column at predicate %zu belongs to another index", who, i);
+      clocks.emplace_back(a->rw);
+      if (a->gen != x->gen) return fail(COLTT_E_INVALID, "%s: the column at predicate %zu is stale (the index was renumbered since it was created)", who, i);
+      it = cheld.emplace(P.column, std::move(a)).first;
+    }
+    pc[i] = it->second.get();
+    if (P.op < COLTT_CMP_EQ || P.op > COLTT_CMP_SET) return fail(COLTT_E_INVALID, "%s: unknown op %d at predicate %zu", who, (int)P.op, i);
+    if (P.reserved != 0) return fail(COLTT_E_INVALID, "%s: reserved != 0 at predicate %zu", who, i);
+    if (pc[i]->type == COLTT_ATTR_F64 && P.op != COLTT_CMP_SET && P.value.f64 != P.value.f64)
+      return fail(COLTT_E_INVALID, "%s: a NaN operand at predicate %zu", who, i);
+  }
   COLTT_DEVICE(x->device);
   const uint32_t n_slots = (uint32_t)x->n, n_words = (n_slots + 31) / 32, n_wg = ceil_div(n_words, FEX_TILE_WORDS);
   if ((uint64_t)n_out * std::max(1u, n_wg) > 0x7fffffffull || total > 0xffffffffull)
@@ -3450,8 +3502,8 @@ int filter_eval_common(coltt_handle_t h, const char* who, const int32_t* progs, 
     slab->device = x->device;
     const size_t stride = ((size_t)n_words + 63) & ~(size_t)63;   // words per output bitmap: 256-byte slices
     COLTT_TRY(slab->bits.reserve(n_out * stride * 4));
-    // one upload: [leaf table][list offsets, filled later][programme offsets][programmes]
-    const size_t o_loff = n_leaves * sizeof(FexLeaf), o_poff = o_loff + n_out * 8, o_prog = o_poff + (n_out + 1) * 4, bytes = o_prog + (size_t)total * 4;
+    // one upload: [leaf table][predicate table][list offsets, filled later][programme offsets][programmes]
+    const size_t o_pred = n_leaves * sizeof(FexLeaf), o_loff = o_pred + n_preds * sizeof(AttrPredDev), o_poff = o_loff + n_out * 8, o_prog = o_poff + (n_out + 1) * 4, bytes = o_prog + (size_t)total * 4;
     COLTT_TRY(c->h_in.reserve(bytes));
     COLTT_TRY(c->w_fdesc.reserve(bytes));
     COLTT_TRY(c->w_scnt.reserve(n_out * (size_t)n_wg * 4));
@@ -3461,6 +3513,12 @@ int filter_eval_common(coltt_handle_t h, const char* who, const int32_t* progs, 
     uint64_t* h_loff = reinterpret_cast<uint64_t*>(hb + o_loff);
     uint32_t* h_poff = reinterpret_cast<uint32_t*>(hb + o_poff);
     int32_t* h_prog = reinterpret_cast<int32_t*>(hb + o_prog);
+    AttrPredDev* h_pred = reinterpret_cast<AttrPredDev*>(hb + o_pred);
+    for (size_t i = 0; i < n_preds; i++) {
+      uint64_t operand;
+      std::memcpy(&operand, &preds[i].value, 8);
+      h_pred[i] = AttrPredDev{pc[i]->vals.as<uint64_t>(), pc[i]->set.as<uint32_t>(), operand, std::min(pc[i]->slots, n_slots), preds[i].op | (pc[i]->type << 8)};
+    }
     for (size_t i = 0; i < n_leaves; i++) h_leaf[i] = FexLeaf{lf[i]->bits.as<uint32_t>(), std::min((lf[i]->slots + 31) / 32, n_words), 0u};
     uint32_t at = 0;
     for (size_t i = 0; i < n_out; i++) {
@@ -3473,9 +3531,15 @@ int filter_eval_common(coltt_handle_t h, const char* who, const int32_t* progs, 
     uint8_t* db = c->w_fdesc.as<uint8_t>();
     COLTT_HIP(hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, c->stream));
     const uint32_t grid = (uint32_t)(n_out * n_wg);
-    filter_eval_kernel<<<grid, FEX_THREADS, 0, c->stream>>>(reinterpret_cast<const FexLeaf*>(db), reinterpret_cast<const uint32_t*>(db + o_poff),
-                                                            reinterpret_cast<const int32_t*>(db + o_prog), x->any_deleted ? x->del_bits.as<uint32_t>() : nullptr,
-                                                            n_slots, n_words, n_wg, slab->bits.as<uint32_t>(), stride, c->w_scnt.as<uint32_t>());
+    if (n_preds)
+      attr_filter_eval_kernel<<<grid, FEX_THREADS, 0, c->stream>>>(reinterpret_cast<const FexLeaf*>(db), (uint32_t)n_leaves, reinterpret_cast<const AttrPredDev*>(db + o_pred),
+                                                                   reinterpret_cast<const uint32_t*>(db + o_poff), reinterpret_cast<const int32_t*>(db + o_prog),
+                                                                   x->any_deleted ? x->del_bits.as<uint32_t>() : nullptr, n_slots, n_words, n_wg,
+                                                                   slab->bits.as<uint32_t>(), stride, c->w_scnt.as<uint32_t>());
+    else
+      filter_eval_kernel<<<grid, FEX_THREADS, 0, c->stream>>>(reinterpret_cast<const FexLeaf*>(db), reinterpret_cast<const uint32_t*>(db + o_poff),
+                                                              reinterpret_cast<const int32_t*>(db + o_prog), x->any_deleted ? x->del_bits.as<uint32_t>() : nullptr,
+                                                              n_slots, n_words, n_wg, slab->bits.as<uint32_t>(), stride, c->w_scnt.as<uint32_t>());
     COLTT_HIP(hipGetLastError());
     COLTT_HIP(hipMemcpyAsync(c->h_out.p, c->w_scnt.p, n_out * (size_t)n_wg * 4, hipMemcpyDeviceToHost, c->stream));
     COLTT_HIP(hipStreamSynchronize(c->stream));
@@ -3571,12 +3635,175 @@ int coltt_hnsw_filter_eval(coltt_handle_t h, const int32_t* prog, size_t n_prog,
                            uint64_t* out_allowed, coltt_handle_t* out) {
   if (!out) return fail(COLTT_E_INVALID, "hnsw_filter_eval: out is NULL");
   const uint64_t off[2] = {0, (uint64_t)n_prog};
-  return filter_eval_common(h, "hnsw_filter_eval", prog, off, 1, leaves, n_leaves, out_allowed, out);
+  return filter_eval_common(h, "hnsw_filter_eval", prog, off, 1, leaves, n_leaves, nullptr, 0, out_allowed, out);
 }
 
 int coltt_hnsw_filter_eval_batch(coltt_handle_t h, const int32_t* progs, const uint64_t* prog_off, size_t n_out, const coltt_handle_t* leaves,
                                  size_t n_leaves, uint64_t* out_allowed, coltt_handle_t* out) {
-  return filter_eval_common(h, "hnsw_filter_eval_batch", progs, prog_off, n_out, leaves, n_leaves, out_allowed, out);
+  return filter_eval_common(h, "hnsw_filter_eval_batch", progs, prog_off, n_out, leaves, n_leaves, nullptr, 0, out_allowed, out);
+}
+
+int coltt_hnsw_filter_eval_attr(coltt_handle_t h, const int32_t* prog, size_t n_prog, const coltt_handle_t* leaves, size_t n_leaves,
+                                const coltt_attr_pred* preds, size_t n_preds, uint64_t* out_allowed, coltt_handle_t* out) {
+  if (!lookup<Hnsw>(h)) return fail(COLTT_E_NOT_FOUND, "hnsw_filter_eval_attr: unknown index handle");
+  if (!out) return fail(COLTT_E_INVALID, "hnsw_filter_eval_attr: out is NULL");
+  const uint64_t off[2] = {0, (uint64_t)n_prog};
+  return filter_eval_common(h, "hnsw_filter_eval_attr", prog, off, 1, leaves, n_leaves, preds, n_preds, out_allowed, out);
+}
+
+int coltt_hnsw_filter_eval_attr_batch(coltt_handle_t h, const int32_t* progs, const uint64_t* prog_off, size_t n_out, const coltt_handle_t* leaves,
+                                      size_t n_leaves, const coltt_attr_pred* preds, size_t n_preds, uint64_t* out_allowed, coltt_handle_t* out) {
+  return filter_eval_common(h, "hnsw_filter_eval_attr_batch", progs, prog_off, n_out, leaves, n_leaves, preds, n_preds, out_allowed, out);
+}
+
+// ---- attribute columns (include/coltt_gpu.h, "Attribute columns and predicates"; kernels: attr_filter.hpp)
+int coltt_hnsw_attr_create(coltt_handle_t h, int type, coltt_handle_t* out) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_attr_create: unknown index handle");
+  if (!out) return fail(COLTT_E_INVALID, "hnsw_attr_create: out is NULL");
+  if (type != COLTT_ATTR_I64 && type != COLTT_ATTR_F64) return fail(COLTT_E_INVALID, "hnsw_attr_create: unknown type %d", type);
+  ReadLock g(x->rw);
+  auto a = std::make_shared<HnswAttr>();
+  a->device = x->device; a->index = h; a->gen = x->gen; a->type = type;
+  *out = Registry::get().add(a);
+  return COLTT_OK;
+}
+
+int coltt_hnsw_attr_destroy(coltt_handle_t ah) {
+  if (!lookup<HnswAttr>(ah)) return fail(COLTT_E_NOT_FOUND, "hnsw_attr_destroy: unknown column handle");
+  Registry::get().erase(ah);
+  return COLTT_OK;
+}
+
+int coltt_hnsw_attr_info(coltt_handle_t ah, coltt_handle_t* out_index, int32_t* out_type, uint64_t* out_slots, uint64_t* out_set) {
+  auto a = lookup<HnswAttr>(ah);
+  if (!a) return fail(COLTT_E_NOT_FOUND, "hnsw_attr_info: unknown column handle");
+  ReadLock ga(a->rw);
+  if (out_index) *out_index = a->index;
+  if (out_type) *out_type = a->type;
+  if (out_slots) *out_slots = a->slots;
+  if (out_set) *out_set = a->n_set;
+  return COLTT_OK;
+}
+
+int coltt_hnsw_attr_set(coltt_handle_t ah, const uint64_t* ids, const void* values, size_t n, uint64_t* out_applied) {
+  auto a = lookup<HnswAttr>(ah);
+  if (!a) return fail(COLTT_E_NOT_FOUND, "hnsw_attr_set: unknown column handle");
+  if (n && (!ids || !values)) return fail(COLTT_E_INVALID, "hnsw_attr_set: NULL ids or values");
+  if (n > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_attr_set: more than 2^32-1 values in one call");
+  auto x = lookup<Hnsw>(a->index);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_attr_set: the column's index is gone");
+  const uint64_t* v = static_cast<const uint64_t*>(values);
+  if (a->type == COLTT_ATTR_F64)   // the whole call, before anything is written
+    for (size_t i = 0; i < n; i++)
+      if (attr_is_nan(v[i])) return fail(COLTT_E_INVALID, "hnsw_attr_set: value %zu is NaN", i);
+  ReadLock g(x->rw);
+  WriteLock ga(a->rw);
+  if (a->gen != x->gen) return fail(COLTT_E_INVALID, "hnsw_attr_set: the column is stale (the index was renumbered since it was created)");
+  if (out_applied) *out_applied = 0;
+  const uint64_t n_slots = x->n;
+  if (n_slots == 0) return COLTT_OK;
+  COLTT_DEVICE(x->device);
+  CtxLease<HCtx> ctx(x->pool);
+  if (!ctx.c) return COLTT_E_DEVICE;
+  HCtx* c = ctx.c;
+  if (n_slots > a->cap) {   // grow to the index's capacity; the new set words are 0
+    const uint64_t ncap = std::max<uint64_t>(x->cap, n_slots), ow = (a->cap + 31) / 32, nw = (ncap + 31) / 32;
+    COLTT_TRY(a->vals.reserve(ncap * 8, true, c->stream));
+    COLTT_TRY(a->set.reserve(nw * 4, true, c->stream));
+    COLTT_HIP(hipMemsetAsync(a->set.as<uint32_t>() + ow, 0, (nw - ow) * 4, c->stream));
+    a->h_set.resize(nw, 0u);
+    a->cap = ncap;
+  }
+  // ids -> live slots, last value wins: walk the call backwards and keep the first sight of every slot
+  const size_t o_val = (n * 4 + 7) & ~(size_t)7;
+  COLTT_TRY(c->h_in.reserve(o_val + n * 8));
+  COLTT_TRY(c->w_fdesc.reserve(o_val + n * 8));
+  uint8_t* hb = static_cast<uint8_t*>(c->h_in.p);
+  uint32_t* h_slot = reinterpret_cast<uint32_t*>(hb);
+  uint64_t* h_val = reinterpret_cast<uint64_t*>(hb + o_val);
+  std::vector<uint32_t> seen((n_slots + 31) / 32, 0u);
+  size_t m = 0; uint64_t fresh = 0;
+  uint32_t w_lo = 0xffffffffu, w_hi = 0;
+  for (size_t i = n; i-- > 0;) {
+    uint32_t s;
+    if (!live_slot_of(x.get(), ids[i], s)) continue;
+    const uint32_t bit = 1u << (s & 31);
+    if (seen[s >> 5] & bit) continue;
+    seen[s >> 5] |= bit;
+    h_slot[m] = s; h_val[m] = v[i]; m++;
+    if (!(a->h_set[s >> 5] & bit)) { a->h_set[s >> 5] |= bit; fresh++; w_lo = std::min(w_lo, s >> 5); w_hi = std::max(w_hi, s >> 5); }
+  }
+  if (m) {
+    uint8_t* db = c->w_fdesc.as<uint8_t>();
+    COLTT_HIP(hipMemcpyAsync(db, hb, o_val + m * 8, hipMemcpyHostToDevice, c->stream));
+    attr_scatter_kernel<<<ceil_div(m, 256), 256, 0, c->stream>>>(reinterpret_cast<const uint32_t*>(db), reinterpret_cast<const uint64_t*>(db + o_val), m,
+                                                                 a->vals.as<uint64_t>());
+    COLTT_HIP(hipGetLastError());
+    if (fresh) COLTT_HIP(hipMemcpyAsync(a->set.as<uint32_t>() + w_lo, a->h_set.data() + w_lo, (size_t)(w_hi - w_lo + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  }
+  COLTT_HIP(hipStreamSynchronize(c->stream));
+  a->slots = (uint32_t)n_slots;
+  a->n_set += fresh;
+  if (out_applied) *out_applied = m;
+  return COLTT_OK;
+}
+
+int coltt_hnsw_attr_get(coltt_handle_t ah, const uint64_t* ids, size_t n, void* out_values, uint8_t* out_set) {
+  auto a = lookup<HnswAttr>(ah);
+  if (!a) return fail(COLTT_E_NOT_FOUND, "hnsw_attr_get: unknown column handle");
+  if (n && !ids) return fail(COLTT_E_INVALID, "hnsw_attr_get: NULL ids");
+  if (n > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_attr_get: more than 2^32-1 ids in one call");
+  auto x = lookup<Hnsw>(a->index);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_attr_get: the column's index is gone");
+  ReadLock g(x->rw);
+  ReadLock ga(a->rw);
+  if (a->gen != x->gen) return fail(COLTT_E_INVALID, "hnsw_attr_get: the column is stale (the index was renumbered since it was created)");
+  if (n == 0) return COLTT_OK;
+  if (a->slots == 0) {   // nothing was ever set
+    if (out_values) std::memset(out_values, 0, n * 8);
+    if (out_set) std::memset(out_set, 0, n);
+    return COLTT_OK;
+  }
+  COLTT_DEVICE(x->device);
+  CtxLease<HCtx> ctx(x->pool);
+  if (!ctx.c) return COLTT_E_DEVICE;
+  HCtx* c = ctx.c;
+  // up: [slots]; down: [values][flags]
+  COLTT_TRY(c->h_in.reserve(n * 4));
+  COLTT_TRY(c->h_out.reserve(n * 9));
+  COLTT_TRY(c->w_fdesc.reserve(n * 4));
+  COLTT_TRY(c->w_out_ids.reserve(n * 9));
+  uint32_t* h_slot = static_cast<uint32_t*>(c->h_in.p);
+  for (size_t i = 0; i < n; i++)
+    if (!live_slot_of(x.get(), ids[i], h_slot[i])) h_slot[i] = 0xffffffffu;
+  COLTT_HIP(hipMemcpyAsync(c->w_fdesc.p, h_slot, n * 4, hipMemcpyHostToDevice, c->stream));
+  uint64_t* d_val = c->w_out_ids.as<uint64_t>();
+  uint8_t* d_flag = reinterpret_cast<uint8_t*>(d_val + n);
+  attr_gather_kernel<<<ceil_div(n, 256), 256, 0, c->stream>>>(c->w_fdesc.as<uint32_t>(), n, a->vals.as<uint64_t>(), a->set.as<uint32_t>(), a->slots, d_val, d_flag);
+  COLTT_HIP(hipGetLastError());
+  COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_val, n * 9, hipMemcpyDeviceToHost, c->stream));
+  COLTT_HIP(hipStreamSynchronize(c->stream));
+  if (out_values) std::memcpy(out_values, c->h_out.p, n * 8);
+  if (out_set) std::memcpy(out_set, static_cast<const uint8_t*>(c->h_out.p) + n * 8, n);
+  return COLTT_OK;
+}
+
+int coltt_attr_cmp_host(int type, int op, const void* operand, const void* value, int is_set) {
+  if (type != COLTT_ATTR_I64 && type != COLTT_ATTR_F64) return fail(COLTT_E_INVALID, "attr_cmp_host: unknown type %d", type);
+  if (op < COLTT_CMP_EQ || op > COLTT_CMP_SET) return fail(COLTT_E_INVALID, "attr_cmp_host: unknown op %d", op);
+  uint64_t o = 0, v = 0;
+  if (op != COLTT_CMP_SET) {
+    if (!operand) return fail(COLTT_E_INVALID, "attr_cmp_host: NULL operand");
+    std::memcpy(&o, operand, 8);
+    if (type == COLTT_ATTR_F64 && attr_is_nan(o)) return fail(COLTT_E_INVALID, "attr_cmp_host: a NaN operand");
+  }
+  if (is_set) {
+    if (!value) return fail(COLTT_E_INVALID, "attr_cmp_host: NULL value");
+    std::memcpy(&v, value, 8);
+    if (type == COLTT_ATTR_F64 && attr_is_nan(v)) return fail(COLTT_E_INVALID, "attr_cmp_host: a NaN value (no column holds one)");
+  }
+  return is_set && attr_cmp(type, op, v, o) ? 1 : 0;
 }
 
 int coltt_hnsw_filter_info(coltt_handle_t fh, coltt_handle_t* out_index, uint64_t* out_allowed, uint64_t* out_slots) {

@@ -181,6 +181,98 @@ class HnswFilter:
             pass
 
 
+# attribute columns and predicates (include/coltt_gpu.h, "Attribute columns and predicates")
+ATTR_I64, ATTR_F64 = 0, 1
+CMP_EQ, CMP_NE, CMP_GT, CMP_GE, CMP_LT, CMP_LE, CMP_SET = range(7)
+_ATTR_DTYPE = {ATTR_I64: np.int64, ATTR_F64: np.float64}
+
+
+class _AttrValue(C.Union):
+    _fields_ = [("i64", C.c_int64), ("f64", C.c_double)]
+
+
+class AttrPred(C.Structure):
+    """coltt_attr_pred"""
+    _fields_ = [("column", C.c_uint64), ("op", C.c_int32), ("reserved", C.c_int32), ("value", _AttrValue)]
+
+
+def attr_cmp_host(type_, op, operand, value, is_set=True):
+    """coltt_attr_cmp_host (no device): is_set and (value OP operand) in the column type's arithmetic; raises ColttError for an unknown type or
+    op and for NaN."""
+    dt = _ATTR_DTYPE.get(int(type_), np.int64)
+    o = np.array([0 if operand is None else operand], dt); v = np.array([0 if value is None else value], dt)
+    rc = L.lib().coltt_attr_cmp_host(C.c_int(int(type_)), C.c_int(int(op)), L.vp(o), L.vp(v), C.c_int(1 if is_set else 0))
+    if rc < 0:
+        L.check(rc)
+    return bool(rc)
+
+
+class HnswAttrColumn:
+    """An attribute column beside one index (coltt_hnsw_attr_create): one int64 (ATTR_I64) or float64 (ATTR_F64) per slot and a set bitmap, on
+    the index's device.  Predicates over it are (column, op, operand) tuples for Hnsw.FilterEvalAttr."""
+
+    def __init__(self, index, type_):
+        h = C.c_uint64(0)
+        L.check(L.lib().coltt_hnsw_attr_create(index.h, C.c_int(int(type_)), C.byref(h)))
+        self.h, self.type, self.dtype = h, int(type_), _ATTR_DTYPE[int(type_)]
+
+    def set(self, ids, values):
+        """coltt_hnsw_attr_set: ids -> values (the last value of a repeated id; unknown and removed ids are ignored).  Returns the vertices set."""
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
+        v = np.ascontiguousarray(np.asarray(values, dtype=self.dtype).reshape(-1))
+        if a.size != v.size:
+            raise ValueError(f"HnswAttrColumn.set: {a.size} ids, {v.size} values")
+        n = C.c_uint64(0)
+        L.check(L.lib().coltt_hnsw_attr_set(self.h, L.vp(a), L.vp(v), C.c_size_t(a.size), C.byref(n)))
+        return n.value
+
+    def get(self, ids):
+        """coltt_hnsw_attr_get: (values in the column's dtype, bool flags: the id's vertex holds a value)"""
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
+        v = np.zeros(a.size, self.dtype); f = np.zeros(a.size, np.uint8)
+        L.check(L.lib().coltt_hnsw_attr_get(self.h, L.vp(a), C.c_size_t(a.size), L.vp(v), L.vp(f)))
+        return v, f.astype(bool)
+
+    def info(self):
+        ix = C.c_uint64(0); t = C.c_int32(0); s = C.c_uint64(0); n = C.c_uint64(0)
+        L.check(L.lib().coltt_hnsw_attr_info(self.h, C.byref(ix), C.byref(t), C.byref(s), C.byref(n)))
+        return {"index": ix.value, "type": t.value, "slots": s.value, "set": n.value}
+
+    def close(self):
+        if getattr(self, "h", None) is not None:
+            L.lib().coltt_hnsw_attr_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _pred_array(preds):
+    """(column, op, operand) tuples (or AttrPred structures) -> a coltt_attr_pred array; the column's type picks the member of the union"""
+    arr = (AttrPred * max(len(preds), 1))()
+    for i, p in enumerate(preds):
+        if isinstance(p, AttrPred):
+            arr[i] = p
+            continue
+        col, op, operand = p
+        arr[i].column = 0 if col.h is None else col.h.value
+        arr[i].op = int(op); arr[i].reserved = 0
+        if col.type == ATTR_F64:
+            arr[i].value.f64 = float(0.0 if operand is None else operand)
+        else:
+            arr[i].value.i64 = int(0 if operand is None else operand)
+    return arr
+
+
 class Hnsw:
     def __init__(self, dim, distance=L.COSINE, cfg=None, quantization=L.Q_NONE):
         self.dim, self.distance, self.quantization = int(dim), distance, quantization
@@ -322,6 +414,37 @@ class Hnsw:
         out = np.zeros(max(len(ps), 1), np.uint64); al = np.zeros(max(len(ps), 1), np.uint64)
         L.check(L.lib().coltt_hnsw_filter_eval_batch(self.h, L.vp(flat), L.vp(off), C.c_size_t(len(ps)), L.vp(lh) if lh.size else None,
                                                      C.c_size_t(lh.size), L.vp(al), L.vp(out)))
+        return [HnswFilter._from_handle(out[i], al[i]) for i in range(len(ps))]
+
+    # -- attribute columns: comparison predicates as programme leaves (include/coltt_gpu.h, "Attribute columns and predicates")
+    def AttrColumn(self, type_):
+        return HnswAttrColumn(self, type_)
+
+    def FilterEvalAttr(self, prog, leaves, preds):
+        """coltt_hnsw_filter_eval_attr: a programme over resident filters `leaves` and predicates `preds` ((column, op, operand) tuples): a value
+        v >= 0 pushes leaves[v] when v < len(leaves), predicate v - len(leaves) otherwise.  An ordinary HnswFilter."""
+        p = _prog_array(prog)
+        lh = np.array([0 if f.h is None else f.h.value for f in leaves], np.uint64)
+        pa = _pred_array(preds)
+        h = C.c_uint64(0); n = C.c_uint64(0)
+        L.check(L.lib().coltt_hnsw_filter_eval_attr(self.h, L.vp(p), C.c_size_t(p.size), L.vp(lh) if lh.size else None, C.c_size_t(lh.size),
+                                                    C.byref(pa) if len(preds) else None, C.c_size_t(len(preds)), C.byref(n), C.byref(h)))
+        return HnswFilter._from_handle(h.value, n.value)
+
+    def FilterEvalAttrBatch(self, progs, leaves, preds):
+        """coltt_hnsw_filter_eval_attr_batch: one filter per programme over the shared leaf and predicate tables, under one index state, in
+        two kernel launches.  Returns a list of HnswFilter."""
+        ps = [_prog_array(p) for p in progs]
+        off = np.zeros(len(ps) + 1, np.uint64)
+        if ps:
+            off[1:] = np.cumsum([p.size for p in ps])
+        flat = np.ascontiguousarray(np.concatenate(ps)) if ps else np.zeros(0, np.int32)
+        lh = np.array([0 if f.h is None else f.h.value for f in leaves], np.uint64)
+        pa = _pred_array(preds)
+        out = np.zeros(max(len(ps), 1), np.uint64); al = np.zeros(max(len(ps), 1), np.uint64)
+        L.check(L.lib().coltt_hnsw_filter_eval_attr_batch(self.h, L.vp(flat), L.vp(off), C.c_size_t(len(ps)), L.vp(lh) if lh.size else None,
+                                                          C.c_size_t(lh.size), C.byref(pa) if len(preds) else None, C.c_size_t(len(preds)),
+                                                          L.vp(al), L.vp(out)))
         return [HnswFilter._from_handle(out[i], al[i]) for i in range(len(ps))]
 
     def SearchFiltered(self, queries, k, flt, ef=0, mode=FILTER_AUTO, with_stats=False):

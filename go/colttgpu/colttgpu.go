@@ -22,6 +22,7 @@ import "C"
 import (
 	"errors"
 	"fmt"
+	"math"
 	"runtime"
 	"unsafe"
 )
@@ -266,6 +267,183 @@ func HnswFilterEvalBatch(h Handle, progs [][]int32, leaves []Handle) ([]Handle, 
 		return nil, nil, err
 	}
 	return out, allowed, nil
+}
+
+// Attribute columns and predicates (coltt_gpu.h, "Attribute columns and predicates"): a numeric field as one 8-byte value per slot beside
+// the index, comparisons over it as leaves of a filter programme.
+const (
+	AttrI64 = 0 // COLTT_ATTR_I64: int64 values
+	AttrF64 = 1 // COLTT_ATTR_F64: float64 values
+)
+
+// Comparison operators (COLTT_CMP_*), in the order of the reference's FilterOp (pkg/inverted/filter.go:24-31).
+const (
+	CmpEq  int32 = 0
+	CmpNe  int32 = 1
+	CmpGt  int32 = 2
+	CmpGe  int32 = 3
+	CmpLt  int32 = 4
+	CmpLe  int32 = 5
+	CmpSet int32 = 6 // the slot has a value; the operand is ignored
+)
+
+// AttrPred mirrors coltt_attr_pred; Bits holds the operand's 8 bytes in the column's type (AttrPredI64 / AttrPredF64 fill it).
+type AttrPred struct {
+	Column Handle
+	Op     int32
+	Bits   uint64
+}
+
+func AttrPredI64(column Handle, op int32, operand int64) AttrPred {
+	return AttrPred{Column: column, Op: op, Bits: uint64(operand)}
+}
+func AttrPredF64(column Handle, op int32, operand float64) AttrPred {
+	return AttrPred{Column: column, Op: op, Bits: math.Float64bits(operand)}
+}
+
+func cpreds(preds []AttrPred) []C.coltt_attr_pred {
+	out := make([]C.coltt_attr_pred, len(preds))
+	for i, p := range preds {
+		out[i].column = p.Column
+		out[i].op = C.int32_t(p.Op)
+		out[i].reserved = 0
+		*(*uint64)(unsafe.Pointer(&out[i].value)) = p.Bits // the union: 8 bytes either way
+	}
+	return out
+}
+
+// HnswAttrCreate: an empty column of type AttrI64 / AttrF64 beside index h (coltt_hnsw_attr_create).  Release it with HnswAttrDestroy.
+func HnswAttrCreate(h Handle, typ int) (Handle, error) {
+	var c Handle
+	err := call(func() C.int { return C.coltt_hnsw_attr_create(h, C.int(typ), &c) })
+	return c, err
+}
+func HnswAttrDestroy(c Handle) error {
+	return call(func() C.int { return C.coltt_hnsw_attr_destroy(c) })
+}
+
+// HnswAttrSetI64 / HnswAttrSetF64: ids -> values (coltt_hnsw_attr_set).  Unknown and removed ids are ignored, an id repeated takes its last
+// value, a NaN refuses the whole call.  Returns the vertices set.
+func HnswAttrSetI64(c Handle, ids []uint64, values []int64) (uint64, error) {
+	if len(ids) != len(values) {
+		return 0, fmt.Errorf("HnswAttrSetI64: %d ids, %d values", len(ids), len(values))
+	}
+	if len(ids) == 0 {
+		return 0, nil
+	}
+	return attrSet(c, ids, unsafe.Pointer(&values[0]))
+}
+func HnswAttrSetF64(c Handle, ids []uint64, values []float64) (uint64, error) {
+	if len(ids) != len(values) {
+		return 0, fmt.Errorf("HnswAttrSetF64: %d ids, %d values", len(ids), len(values))
+	}
+	if len(ids) == 0 {
+		return 0, nil
+	}
+	return attrSet(c, ids, unsafe.Pointer(&values[0]))
+}
+func attrSet(c Handle, ids []uint64, values unsafe.Pointer) (uint64, error) {
+	var applied C.uint64_t
+	err := call(func() C.int { return C.coltt_hnsw_attr_set(c, uptr(ids), values, C.size_t(len(ids)), &applied) })
+	return uint64(applied), err
+}
+
+// HnswAttrGet: the raw 8-byte values of ids and whether each vertex holds one (coltt_hnsw_attr_get); math.Float64frombits for an F64 column.
+func HnswAttrGet(c Handle, ids []uint64) ([]uint64, []bool, error) {
+	if len(ids) == 0 {
+		return nil, nil, nil
+	}
+	vals := make([]uint64, len(ids))
+	flags := make([]uint8, len(ids))
+	err := call(func() C.int {
+		return C.coltt_hnsw_attr_get(c, uptr(ids), C.size_t(len(ids)), unsafe.Pointer(&vals[0]), (*C.uint8_t)(unsafe.Pointer(&flags[0])))
+	})
+	if err != nil {
+		return nil, nil, err
+	}
+	set := make([]bool, len(ids))
+	for i, f := range flags {
+		set[i] = f != 0
+	}
+	return vals, set, nil
+}
+
+// HnswAttrInfo: the column's index, type, the slots it covers and the slots that hold a value (coltt_hnsw_attr_info).
+func HnswAttrInfo(c Handle) (index Handle, typ int, slots, set uint64, err error) {
+	var t C.int32_t
+	var s, n C.uint64_t
+	err = call(func() C.int { return C.coltt_hnsw_attr_info(c, &index, &t, &s, &n) })
+	return index, int(t), uint64(s), uint64(n), err
+}
+
+// HnswFilterEvalAttr: HnswFilterEval over leaves and predicates (coltt_hnsw_filter_eval_attr): a value v >= 0 of the programme pushes
+// leaves[v] when v < len(leaves) and preds[v - len(leaves)] otherwise.
+func HnswFilterEvalAttr(h Handle, prog []int32, leaves []Handle, preds []AttrPred) (Handle, uint64, error) {
+	var f Handle
+	var allowed C.uint64_t
+	cp := cpreds(preds)
+	err := call(func() C.int {
+		var p *C.int32_t
+		if len(prog) > 0 {
+			p = (*C.int32_t)(unsafe.Pointer(&prog[0]))
+		}
+		var pp *C.coltt_attr_pred
+		if len(cp) > 0 {
+			pp = &cp[0]
+		}
+		return C.coltt_hnsw_filter_eval_attr(h, p, C.size_t(len(prog)), hptr(leaves), C.size_t(len(leaves)), pp, C.size_t(len(cp)), &allowed, &f)
+	})
+	return f, uint64(allowed), err
+}
+
+// HnswFilterEvalAttrBatch: one filter per programme over shared leaf and predicate tables (coltt_hnsw_filter_eval_attr_batch).
+func HnswFilterEvalAttrBatch(h Handle, progs [][]int32, leaves []Handle, preds []AttrPred) ([]Handle, []uint64, error) {
+	n := len(progs)
+	if n == 0 {
+		return nil, nil, nil
+	}
+	off := make([]uint64, n+1)
+	var flat []int32
+	for i, p := range progs {
+		flat = append(flat, p...)
+		off[i+1] = uint64(len(flat))
+	}
+	out := make([]Handle, n)
+	allowed := make([]uint64, n)
+	cp := cpreds(preds)
+	err := call(func() C.int {
+		var p *C.int32_t
+		if len(flat) > 0 {
+			p = (*C.int32_t)(unsafe.Pointer(&flat[0]))
+		}
+		var pp *C.coltt_attr_pred
+		if len(cp) > 0 {
+			pp = &cp[0]
+		}
+		return C.coltt_hnsw_filter_eval_attr_batch(h, p, (*C.uint64_t)(unsafe.Pointer(&off[0])), C.size_t(n), hptr(leaves), C.size_t(len(leaves)),
+			pp, C.size_t(len(cp)), (*C.uint64_t)(unsafe.Pointer(&allowed[0])), &out[0])
+	})
+	if err != nil {
+		return nil, nil, err
+	}
+	return out, allowed, nil
+}
+
+// AttrCmpHost: the comparison itself with no device (coltt_attr_cmp_host): isSet && value OP operand, both as the column type's 8 bytes.
+func AttrCmpHost(typ int, op int32, operand, value uint64, isSet bool) (bool, error) {
+	s := C.int(0)
+	if isSet {
+		s = 1
+	}
+	var rc C.int
+	err := call(func() C.int {
+		rc = C.coltt_attr_cmp_host(C.int(typ), C.int(op), unsafe.Pointer(&operand), unsafe.Pointer(&value), s)
+		if rc > 0 {
+			return C.COLTT_OK
+		}
+		return rc
+	})
+	return rc == 1, err
 }
 
 // HnswFilterIds: the ids filter f allows, in ascending slot order, at most limit of them (coltt_hnsw_filter_ids; gathered on the device).

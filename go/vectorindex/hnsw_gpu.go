@@ -421,11 +421,15 @@ func (f *HnswFilter) Close() error {
 // evaluateCompositeFilter): a leaf is Leaf(i) = the i-th filter of the table given to EvalFilter, inner nodes are And / Or / AndNot / Not,
 // All() is every live vertex.  Postfix() is the programme the library evaluates on the device.
 type FilterExpr struct {
-	op   int32 // >= 0: leaf index; otherwise a colttgpu.Fop*
+	op   int32 // >= 0: leaf index (pred: predicate index); otherwise a colttgpu.Fop*
+	pred bool  // op counts in the predicate table of EvalFilterAttr, which follows the leaf table in the programme's numbering
 	args []FilterExpr
 }
 
 func Leaf(i int) FilterExpr { return FilterExpr{op: int32(i)} }
+
+// Pred(i) = the i-th predicate of the table given to EvalFilterAttr: a comparison over an attribute column, standing wherever a Leaf can.
+func Pred(i int) FilterExpr { return FilterExpr{op: int32(i), pred: true} }
 func All() FilterExpr       { return FilterExpr{op: colttgpu.FopAll} }
 func Not(a FilterExpr) FilterExpr {
 	return FilterExpr{op: colttgpu.FopNot, args: []FilterExpr{a}}
@@ -442,17 +446,23 @@ func Or(a, b FilterExpr, more ...FilterExpr) FilterExpr {
 	return FilterExpr{op: colttgpu.FopOr, args: append([]FilterExpr{a, b}, more...)}
 }
 
-func (e FilterExpr) Postfix() []int32 { return e.postfix(nil) }
-func (e FilterExpr) postfix(out []int32) []int32 {
+func (e FilterExpr) Postfix() []int32 { return e.postfix(nil, 0) }
+
+// PostfixAttr: the programme of EvalFilterAttr over nLeaves leaves: Pred(i) is the value nLeaves + i.
+func (e FilterExpr) PostfixAttr(nLeaves int) []int32 { return e.postfix(nil, int32(nLeaves)) }
+func (e FilterExpr) postfix(out []int32, nLeaves int32) []int32 {
+	if e.op >= 0 && e.pred {
+		return append(out, nLeaves+e.op)
+	}
 	if e.op >= 0 || e.op == colttgpu.FopAll {
 		return append(out, e.op)
 	}
-	out = e.args[0].postfix(out)
+	out = e.args[0].postfix(out, nLeaves)
 	if e.op == colttgpu.FopNot {
 		return append(out, e.op)
 	}
 	for _, a := range e.args[1:] {
-		out = a.postfix(out)
+		out = a.postfix(out, nLeaves)
 		out = append(out, e.op)
 	}
 	return out
@@ -506,6 +516,112 @@ func (xx *Hnsw) EvalFilters(exprs []FilterExpr, leaves ...*HnswFilter) ([]*HnswF
 		out[i] = &HnswFilter{h: hs[i], index: xx, Allowed: ns[i]}
 	}
 	return out, nil
+}
+
+// AttrColumn — a numeric field beside the index: one int64 (colttgpu.AttrI64) or float64 (colttgpu.AttrF64) per vertex on the device
+// (coltt_gpu.h, "Attribute columns and predicates").  NOT reference behaviour: the reference keeps a bitmap per distinct value of a field
+// and, for every operator but OpEqual, walks all of them per request (pkg/inverted/search.go:36-45).  A vertex never set — or inserted after
+// the last Set, or re-inserted by Update, which is Remove + Insert — holds no value and satisfies no comparison.  Load / Compact make the
+// column stale: build a new one by ids.  Close releases its device memory.
+type AttrColumn struct {
+	h     colttgpu.Handle
+	index *Hnsw
+	Type  int
+}
+
+func (xx *Hnsw) NewAttrColumn(typ int) (*AttrColumn, error) {
+	if xx.err != nil {
+		return nil, xx.err
+	}
+	c, err := colttgpu.HnswAttrCreate(xx.h, typ)
+	if err != nil {
+		return nil, err
+	}
+	return &AttrColumn{h: c, index: xx, Type: typ}, nil
+}
+
+func (c *AttrColumn) Handle() colttgpu.Handle { return c.h }
+
+// SetI64 / SetF64: ids -> values; unknown and removed ids are ignored, an id repeated takes its last value; returns the vertices set.
+func (c *AttrColumn) SetI64(ids []uint64, values []int64) (uint64, error) {
+	if c.Type != colttgpu.AttrI64 {
+		return 0, errors.New("AttrColumn.SetI64: the column holds float64 values")
+	}
+	return colttgpu.HnswAttrSetI64(c.h, ids, values)
+}
+func (c *AttrColumn) SetF64(ids []uint64, values []float64) (uint64, error) {
+	if c.Type != colttgpu.AttrF64 {
+		return 0, errors.New("AttrColumn.SetF64: the column holds int64 values")
+	}
+	return colttgpu.HnswAttrSetF64(c.h, ids, values)
+}
+
+// Get: the raw 8-byte values of ids (math.Float64frombits for a float64 column) and whether each vertex holds one.
+func (c *AttrColumn) Get(ids []uint64) ([]uint64, []bool, error) { return colttgpu.HnswAttrGet(c.h, ids) }
+
+func (c *AttrColumn) Close() error {
+	if c.h == 0 {
+		return nil
+	}
+	err := colttgpu.HnswAttrDestroy(c.h)
+	c.h = 0
+	return err
+}
+
+// PredFromFilter translates one comparison of the reference's filter language — inverted.Filter{IndexName, Op, Value}
+// (pkg/inverted/filter.go:40-44); op is the FilterOp, whose order colttgpu.Cmp* keeps — into a predicate over the column registered under
+// IndexName.  An int / int64 value goes to an int64 column, a float32 / float64 value to a float64 column; anything else, and a value whose
+// kind is not the column's, is an error (mixed comparison is the caller's conversion).
+func PredFromFilter(columns map[string]*AttrColumn, indexName string, op int, value interface{}) (colttgpu.AttrPred, error) {
+	c, ok := columns[indexName]
+	if !ok || c == nil {
+		return colttgpu.AttrPred{}, fmt.Errorf("PredFromFilter: no attribute column for index %q", indexName)
+	}
+	if op < int(colttgpu.CmpEq) || op > int(colttgpu.CmpLe) {
+		return colttgpu.AttrPred{}, fmt.Errorf("PredFromFilter: unknown FilterOp %d", op)
+	}
+	switch v := value.(type) {
+	case int:
+		if c.Type == colttgpu.AttrI64 {
+			return colttgpu.AttrPredI64(c.h, int32(op), int64(v)), nil
+		}
+	case int64:
+		if c.Type == colttgpu.AttrI64 {
+			return colttgpu.AttrPredI64(c.h, int32(op), v), nil
+		}
+	case float32:
+		if c.Type == colttgpu.AttrF64 {
+			return colttgpu.AttrPredF64(c.h, int32(op), float64(v)), nil
+		}
+	case float64:
+		if c.Type == colttgpu.AttrF64 {
+			return colttgpu.AttrPredF64(c.h, int32(op), v), nil
+		}
+	default:
+		return colttgpu.AttrPred{}, fmt.Errorf("PredFromFilter: a %T value is neither an integer nor a float", value)
+	}
+	return colttgpu.AttrPred{}, fmt.Errorf("PredFromFilter: a %T value against column %q of the other type", value, indexName)
+}
+
+// EvalFilterAttr evaluates expr over resident filters and predicates on the device (coltt_hnsw_filter_eval_attr): Leaf(i) is leaves[i],
+// Pred(i) is preds[i].  The result is an ordinary HnswFilter, exactly NewFilter over the ids the expression allows; Not and All see
+// vertices without a value and newer vertices, a bare predicate does not.
+func (xx *Hnsw) EvalFilterAttr(expr FilterExpr, leaves []*HnswFilter, preds []colttgpu.AttrPred) (*HnswFilter, error) {
+	if xx.err != nil {
+		return nil, xx.err
+	}
+	lh := make([]colttgpu.Handle, len(leaves))
+	for i, l := range leaves {
+		if l == nil {
+			return nil, fmt.Errorf("EvalFilterAttr: no filter at leaf %d", i)
+		}
+		lh[i] = l.h
+	}
+	f, n, err := colttgpu.HnswFilterEvalAttr(xx.h, expr.PostfixAttr(len(leaves)), lh, preds)
+	if err != nil {
+		return nil, err
+	}
+	return &HnswFilter{h: f, index: xx, Allowed: n}, nil
 }
 
 // Ids: the ids the filter allows, in ascending slot order (gathered on the device)

@@ -399,6 +399,76 @@ int coltt_hnsw_filter_ids(coltt_handle_t filter, uint64_t* out_ids, uint64_t cap
 int coltt_hnsw_filter_info(coltt_handle_t filter, coltt_handle_t* out_index, uint64_t* out_allowed, uint64_t* out_slots);
 int coltt_hnsw_filter_prog_check_host(const int32_t* prog, size_t n_prog, size_t n_leaves, uint32_t* out_depth);   /* no device */
 
+/* ATTRIBUTE COLUMNS AND PREDICATES: comparison leaves produced on the device (coltt_hnsw_attr_set, coltt_hnsw_filter_eval_attr).  The
+ * reference's filter language has six comparison operators (pkg/inverted/filter.go:24-31); for every one but OpEqual it walks every distinct
+ * value of the field and ORs that value's bitmap (pkg/inverted/search.go:36-45).  A predicate such as price < 37.5 on a high-cardinality
+ * field has no hot term to keep resident as a leaf; here a numeric field is a COLUMN beside the index, one value per slot, and a comparison
+ * over it stands in a filter programme wherever a resident filter can.
+ * Column.  Belongs to one index and lives on that index's device: an 8-byte value per slot (COLTT_ATTR_I64: int64_t, COLTT_ATTR_F64: double),
+ * a "set" bitmap of one bit per slot, and the slots it covers = the index's slot count at the last coltt_hnsw_attr_set.  A slot never set, and
+ * a slot at or past the coverage (a vertex inserted after the last attr_set), is UNSET; an unset slot satisfies no comparison, as a vertex
+ * without the field is in no bitmap of that field in the reference.
+ * coltt_hnsw_attr_set maps ids to live slots exactly as coltt_hnsw_filter_create does (dense ids and explicit ids); unknown and removed ids
+ * are ignored, *out_applied (may be NULL) = the vertices set.  An id repeated within one call takes its LAST value.  A NaN value in an F64
+ * column is COLTT_E_INVALID, checked for the whole call before anything is written (a departure from the reference, whose compareValues calls
+ * NaN equal to everything).  The call grows the column to the index's capacity when the index has outgrown it.  Update in place: the
+ * reference's Core.Update is Remove + Insert under the same id, which gives the vertex a NEW slot: that slot is unset until the caller sets
+ * the id again.  coltt_hnsw_attr_get: out_values[i] (8 bytes each) and out_set[i] (1 / 0; either may be NULL) for ids[i]; an unknown or
+ * removed id and an unset slot give value 0, flag 0.  coltt_hnsw_attr_info (every out may be NULL): the index, the type, the slots covered
+ * and the slots that hold a value (those of vertices removed since included).
+ * Staleness.  A column records the index's generation as a filter does: after coltt_hnsw_load, coltt_hnsw_bulk_load or a coltt_hnsw_compact
+ * that renumbered the slots it is stale and every use but info and destroy is COLTT_E_INVALID; the caller sets it again by ids.
+ * Locking.  attr_set takes the index's lock shared and the column's own lock exclusive and returns after its device work is complete;
+ * attr_get and an evaluation hold the columns they read shared, so an evaluation sees a column wholly before or wholly after a concurrent
+ * attr_set.  Destroying a column an evaluation holds is safe.
+ * Predicate.  { column, op, reserved = 0, value }: the column's type decides which member of value is read (mixed int / float comparison
+ * is the caller's conversion).  Predicate P over column C has bit s = set_C(s) and cmp(value_C[s], operand) when s is below C's covered slots,
+ * else 0 — the rule a leaf has for the slots it does not cover.  I64 compares as signed 64-bit integers, never through a double; F64 as IEEE
+ * doubles (-0.0 == +0.0, infinities ordered as usual).  COLTT_CMP_SET: the slot has a value; the operand is ignored.
+ * Programme.  The language of "Filter expressions" above: a value v >= 0 pushes leaves[v] when v < n_leaves and predicate v - n_leaves
+ * otherwise; the operators are COLTT_FOP_*; the rules are coltt_hnsw_filter_prog_check_host over n_leaves + n_preds leaves (the calls use
+ * it).  Everything else is the definition above word for word: the result allows { s < n_slots : expr(s) and live(s) } and is an ordinary
+ * filter, indistinguishable from coltt_hnsw_filter_create over the ids of that set — the same allowed count, bitmap words and ascending slot
+ * list, so the same filter_ids, filter_info and every search answer, path and stat.  NOT and ALL see unset slots and newer vertices, a bare
+ * predicate does not.  _eval_attr_batch: output i equals _eval_attr of programme i over the shared leaf and predicate tables under one index
+ * state.  One call launches two kernels and makes one host round trip whatever n_out and n_preds are.
+ * Errors, all before anything is created (the codes of coltt_hnsw_filter_eval where they overlap; coltt_last_error names the first bad
+ * predicate or programme position).  Unknown index, leaf or column handle: COLTT_E_NOT_FOUND.  A column of another index, a stale column,
+ * an unknown op, reserved != 0, a NaN operand of an F64 column (unless the op is COLTT_CMP_SET), NULL preds with n_preds > 0:
+ * COLTT_E_INVALID.  Not errors: n_out == 0; n_preds == 0 (the call equals coltt_hnsw_filter_eval / _eval_batch); an empty index; an empty
+ * result; a repeated column or predicate.  Host pointers only.
+ * coltt_attr_cmp_host (no device) is the comparison itself, the function the kernel compiles: 1 or 0 for is_set && cmp(*value, *operand), or
+ * COLTT_E_INVALID for an unknown type or op, a NaN operand or value of type F64, or a NULL operand / value where one is read (operand: every
+ * op but SET; value: is_set != 0).
+ * Not carried through coltt_hnsw_compact, Commit / Load (columns go stale, as filters do); no string columns (dictionary-encode to I64). */
+#define COLTT_ATTR_I64 0
+#define COLTT_ATTR_F64 1
+#define COLTT_CMP_EQ 0   /* the order of the reference's FilterOp, pkg/inverted/filter.go:24-31 */
+#define COLTT_CMP_NE 1
+#define COLTT_CMP_GT 2
+#define COLTT_CMP_GE 3
+#define COLTT_CMP_LT 4
+#define COLTT_CMP_LE 5
+#define COLTT_CMP_SET 6  /* the slot has a value; the operand is ignored */
+typedef struct coltt_attr_pred {
+  coltt_handle_t column;
+  int32_t op;            /* COLTT_CMP_* */
+  int32_t reserved;      /* 0 */
+  union { int64_t i64; double f64; } value;   /* the operand, in the column's type */
+} coltt_attr_pred;
+int coltt_hnsw_attr_create(coltt_handle_t hnsw, int type, coltt_handle_t* out);
+int coltt_hnsw_attr_destroy(coltt_handle_t column);
+int coltt_hnsw_attr_set(coltt_handle_t column, const uint64_t* ids, const void* values /* n x 8 bytes, the column's type */, size_t n,
+                        uint64_t* out_applied);
+int coltt_hnsw_attr_get(coltt_handle_t column, const uint64_t* ids, size_t n, void* out_values, uint8_t* out_set);
+int coltt_hnsw_attr_info(coltt_handle_t column, coltt_handle_t* out_index, int32_t* out_type, uint64_t* out_slots, uint64_t* out_set);
+int coltt_hnsw_filter_eval_attr(coltt_handle_t hnsw, const int32_t* prog, size_t n_prog, const coltt_handle_t* leaves, size_t n_leaves,
+                                const coltt_attr_pred* preds, size_t n_preds, uint64_t* out_allowed, coltt_handle_t* out);
+int coltt_hnsw_filter_eval_attr_batch(coltt_handle_t hnsw, const int32_t* progs, const uint64_t* prog_off /*[n_out+1]*/, size_t n_out,
+                                      const coltt_handle_t* leaves, size_t n_leaves, const coltt_attr_pred* preds, size_t n_preds,
+                                      uint64_t* out_allowed /*[n_out], may be NULL*/, coltt_handle_t* out /*[n_out]*/);
+int coltt_attr_cmp_host(int type, int op, const void* operand, const void* value, int is_set);   /* no device: 1, 0, or a negative error */
+
 /* Capacity for n_slots vertices (and n_upper_rows upper-level adjacency rows; 0 = the expectation for this index's M) in ONE allocation per
  * array, before the inserts.  Optional — Insert grows the arrays by half their size when they are full — but an index whose final size is
  * known should reserve it: growth copies every array (30 GB of rows at 10 M x 768 f32), and arrays allocated once from an empty heap get the

@@ -252,6 +252,60 @@ class Hnsw {
     for (size_t i = 0; i < progs.size(); i++) out.emplace_back(new Filter(hs[i], al[i]));
     return out;
   }
+  // Attribute columns (coltt_gpu.h, "Attribute columns and predicates"): one int64_t (COLTT_ATTR_I64) or double (COLTT_ATTR_F64) per slot beside
+  // the index; comparisons over them are leaves of a filter programme.  Stale after Load / BulkLoad / a Compact that renumbered: set again by ids.
+  class AttrColumn {
+   public:
+    AttrColumn(const Hnsw& index, int type) : type_(type) { check(coltt_hnsw_attr_create(index.h_, type, &h_)); }
+    ~AttrColumn() { if (h_) coltt_hnsw_attr_destroy(h_); }
+    AttrColumn(const AttrColumn&) = delete;
+    AttrColumn& operator=(const AttrColumn&) = delete;
+    coltt_handle_t handle() const { return h_; }
+    int Type() const { return type_; }
+    // ids -> values (an id repeated takes its last value; unknown and removed ids are ignored); returns the vertices set
+    uint64_t Set(const std::vector<uint64_t>& ids, const std::vector<int64_t>& values) { return set(COLTT_ATTR_I64, ids, values.data(), values.size()); }
+    uint64_t Set(const std::vector<uint64_t>& ids, const std::vector<double>& values) { return set(COLTT_ATTR_F64, ids, values.data(), values.size()); }
+    // the raw 8-byte values of ids and whether each has one
+    void Get(const std::vector<uint64_t>& ids, std::vector<uint64_t>* raw_values, std::vector<uint8_t>* is_set) const {
+      if (raw_values) raw_values->assign(ids.size(), 0);
+      if (is_set) is_set->assign(ids.size(), 0);
+      check(coltt_hnsw_attr_get(h_, ids.data(), ids.size(), raw_values ? raw_values->data() : nullptr, is_set ? is_set->data() : nullptr));
+    }
+    uint64_t Slots() const { uint64_t s = 0; check(coltt_hnsw_attr_info(h_, nullptr, nullptr, &s, nullptr)); return s; }
+    uint64_t SetCount() const { uint64_t s = 0; check(coltt_hnsw_attr_info(h_, nullptr, nullptr, nullptr, &s)); return s; }
+    // a predicate over this column for FilterEvalAttr: op = COLTT_CMP_*
+    coltt_attr_pred Pred(int op, int64_t operand) const { coltt_attr_pred p{}; p.column = h_; p.op = op; p.value.i64 = operand; return p; }
+    coltt_attr_pred Pred(int op, double operand) const { coltt_attr_pred p{}; p.column = h_; p.op = op; p.value.f64 = operand; return p; }
+   private:
+    uint64_t set(int type, const std::vector<uint64_t>& ids, const void* values, size_t n) {
+      if (type != type_ || n != ids.size()) throw std::invalid_argument("AttrColumn::Set: values of the wrong type or length");
+      uint64_t applied = 0;
+      check(coltt_hnsw_attr_set(h_, ids.data(), values, n, &applied));
+      return applied;
+    }
+    coltt_handle_t h_ = 0; int type_ = COLTT_ATTR_I64;
+  };
+  // a programme over leaves and predicates: a value v >= 0 pushes leaves[v] when v < leaves.size(), predicate v - leaves.size() otherwise
+  std::unique_ptr<Filter> FilterEvalAttr(const std::vector<int32_t>& prog, const std::vector<const Filter*>& leaves,
+                                         const std::vector<coltt_attr_pred>& preds) const {
+    std::vector<coltt_handle_t> lh(leaves.size());
+    for (size_t i = 0; i < leaves.size(); i++) lh[i] = leaves[i] ? leaves[i]->handle() : 0;
+    coltt_handle_t h = 0; uint64_t allowed = 0;
+    check(coltt_hnsw_filter_eval_attr(h_, prog.data(), prog.size(), lh.data(), lh.size(), preds.data(), preds.size(), &allowed, &h));
+    return std::unique_ptr<Filter>(new Filter(h, allowed));
+  }
+  std::vector<std::unique_ptr<Filter>> FilterEvalAttrBatch(const std::vector<std::vector<int32_t>>& progs, const std::vector<const Filter*>& leaves,
+                                                           const std::vector<coltt_attr_pred>& preds) const {
+    std::vector<coltt_handle_t> lh(leaves.size());
+    for (size_t i = 0; i < leaves.size(); i++) lh[i] = leaves[i] ? leaves[i]->handle() : 0;
+    std::vector<int32_t> flat; std::vector<uint64_t> off(progs.size() + 1, 0);
+    for (size_t i = 0; i < progs.size(); i++) { flat.insert(flat.end(), progs[i].begin(), progs[i].end()); off[i + 1] = flat.size(); }
+    std::vector<coltt_handle_t> hs(progs.size(), 0); std::vector<uint64_t> al(progs.size(), 0);
+    check(coltt_hnsw_filter_eval_attr_batch(h_, flat.data(), off.data(), progs.size(), lh.data(), lh.size(), preds.data(), preds.size(), al.data(), hs.data()));
+    std::vector<std::unique_ptr<Filter>> out;
+    for (size_t i = 0; i < progs.size(); i++) out.emplace_back(new Filter(hs[i], al[i]));
+    return out;
+  }
   SearchResult SearchFiltered(const Vector& query, unsigned k, const Filter& f, unsigned ef = 0, int mode = COLTT_FILTER_AUTO,
                               coltt_hnsw_filter_stats* stats = nullptr) const {
     std::vector<uint64_t> ids(k); std::vector<float> sc(k); uint32_t n = 0;
