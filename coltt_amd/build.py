@@ -101,6 +101,14 @@ def verify(out=None):
     return m
 
 
+def _workers():
+    """Compile jobs at a time: MAX_JOBS if set, clamped to 1..16, else 4.  Never the CPU count: a shared machine shows all of its CPUs."""
+    try:
+        return min(16, max(1, int(os.environ["MAX_JOBS"])))
+    except (KeyError, ValueError):
+        return 4
+
+
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     want = source_keys()
@@ -111,6 +119,7 @@ def build(force=False, verbose=False):
         obj = os.path.join(OBJ, s[:-4] + ".o")
         if force or not os.path.exists(obj) or have.get(s[:-4] + ".o") != want[s[:-4] + ".o"]:
             jobs.append((src, obj))
+    jobs.sort(key=lambda j: -os.path.getsize(j[0]))   # largest source first: the longest compile does not start last
     t0 = time.time()
 
     def cc(job):
@@ -119,7 +128,7 @@ def build(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
 
-    with ThreadPoolExecutor(max_workers=4) as ex:
+    with ThreadPoolExecutor(max_workers=_workers()) as ex:
         list(ex.map(cc, jobs))
     objs = [os.path.join(OBJ, s[:-4] + ".o") for s in sources()]
     if force or jobs or not os.path.exists(OUT) or read_manifest().get("library_sha256") != _sha(OUT):

@@ -1,6 +1,6 @@
 // filter_expr.hpp — filter expressions on the device (coltt_hnsw_filter_eval / _eval_batch / _ids; include/coltt_gpu.h, "Filter expressions").
 //
-// A filter is a slot bitmap and the ascending list of its set slots (hnsw.hip: HnswFilter).  An expression over resident filters is a
+// A filter is a slot bitmap and the ascending list of its set slots (hnsw_index.hpp: HnswFilter).  An expression over resident filters is a
 // postfix programme; its result is built here in two launches with one host round trip between them (the counts that size the lists):
 //   filter_eval_kernel     one pass over the bitmap words: the stack machine runs per word, the result word is masked with the live slots
 //                          and written, every workgroup writes the popcount of its FEX_TILE_WORDS words;

@@ -15,12 +15,14 @@
 #include <map>
 
 #include "common.hpp"
+#include "hnsw_index.hpp"   // HCtx, Hnsw and what hnsw_search2.hip / hnsw_filter.hip share with this file
 #include "exact.hpp"
 #include "hnsw_dev.hpp"
 #include "hnsw_walk2.hpp"
 #include "hnsw_lat.hpp"
 #include "hnsw_pq.hpp"
 #include "prep.hpp"
+#include "rows8_ingest.hpp"   // the kernels that write the row-filter shadows
 
 #include "hnsw_kernels.hpp"   // the search kernels (one-wave walk, large-ef walk, latency kernel, walk over PQ codes + re-rank)
 #include "filter_expr.hpp"    // filter expressions: evaluate, compact, read-back
@@ -30,6 +32,7 @@
 using namespace coltt;
 using namespace coltt::dev;
 using namespace coltt::kern;
+using namespace coltt::hnsw;
 
 namespace {
 
@@ -404,148 +407,6 @@ __global__ void add_base_kernel(uint64_t* ids, size_t n, uint64_t base) {
   if (i < n) ids[i] += base;
 }
 
-// Per-call search context: searches hold the index lock shared and run concurrently, each on its own stream and workspaces.
-struct HCtx {
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  DevBuf w_qraw, w_qeff, w_qn, w_out_ids, w_out_sc, w_out_cnt, w_misc, w_pack;
-  DevBuf w_surv, w_scnt, w_keys;   // product-quantised walk: survivors (slots), their count, their exact keys
-  DevBuf w_mbox;                   // latency kernel: the walking workgroups' hint mailboxes (hnsw_lat.hpp: cache-warming helper workgroups)
-  DevBuf w_fdesc;                  // filtered batch: the walks' per-query descriptors, the exact path's queries and tiles
-  PinnedBuf h_in, h_out;   // small calls: see PinnedBuf
-  bool flt_launch = false;   // launch_search2 took the row-filter twin for the call in flight
-  bool v16_launch = false;   // ... and that twin walks over the 16-bit visited set (vis16.hpp)
-  const void* occ_kern = nullptr; size_t occ_lds = 0; int occ_per_cu = 0;   // the runtime's occupancy answer for the last (kernel, LDS) asked about
-  int init() {  // the caller has selected the index's device
-    COLTT_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    COLTT_HIP(hipEventCreate(&ev0));
-    COLTT_HIP(hipEventCreate(&ev1));
-    return COLTT_OK;
-  }
-  ~HCtx() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-struct Hnsw : Object {
-  uint32_t dim = 0; int metric = 0, quant = 0; size_t stride = 0;
-  coltt_hnsw_cfg cfg{};
-  uint64_t n = 0 /*slots*/, live = 0, cap = 0, n_upper = 0, ucap = 0;
-  int32_t entry = -1, entry_level = 0;
-  bool any_deleted = false;
-  DevBuf rows, norms, ids, adj0, adj0_d, adj0_n, upper_off, adjU, adjU_d, del_bits;
-  // rows8.hpp (round 5: ONE row array).  r8: `rows` itself is stored LINE-TRANSPOSED — every 128-byte line rewritten so that its 16-byte chunk r
-  // holds residue r's consecutive AVX steps — for the shapes the eight-lanes-per-row core covers (f32 / 2-byte rows whose byte length is a
-  // multiple of 128, dim >= 256 unless COLTT_ROWS8=2; never with COLTT_ROWS8=0).  Every reader knows the layout: the eight-lane core reads whole
-  // lines, the pair-owned core reads its four chunks of a line (exact.hpp: pair_distance_r8 — same values, same order, same bits), the builder,
-  // Commit / Get / fetch and the quantiser's Encode un-permute element indices (r8_index).  Writers go through a natural-order staging block.
-  bool r8 = false;
-  DevBuf w_stage;   // natural-order rows of the batch being ingested (r8 indexes)
-  std::atomic<uint64_t> ev8_launches{0};   // search launches whose level-0 distances came from rows8
-  // The level-0 row filter (row_filter.hpp, rows8.hpp): rows_h = one binary16 value per stored element of a line-transposed f32 cosine index, dim * 2 bytes
-  // per slot — DERIVED data, written wherever `rows` is written (prep_rows_any), grown with it, never part of a stream or a read-back.  shadow: the index
-  // keeps one (decided at create: shape, COLTT_ROW_SHADOW; dropped for good when its allocation fails — the index then works without the filter).
-  bool shadow = false;
-  DevBuf rows_h;
-  // The 8-bit shadow (row_filter8.hpp, rows8.hpp): rows_b = one code byte per stored element, rows_m = (scale, error norm) per slot, adj0_m = rows_m of every
-  // level-0 edge's target, written wherever adj0_n is.  Derived data like rows_h: written and grown with `rows`, dropped for good when an allocation fails.
-  // Which of the two an index keeps is decided at create (COLTT_ROW_SHADOW_BITS; default: this one).
-  bool shadow8 = false;
-  DevBuf rows_b, rows_m, adj0_m;
-  void drop_shadow8() {
-    shadow8 = false;
-    for (DevBuf* b : {&rows_b, &rows_m, &adj0_m}) if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
-    (void)hipGetLastError();
-  }
-  bool has_shadow8() const { return shadow8 && rows_b.p && rows_m.p && adj0_m.p; }
-  bool has_shadow16() const { return shadow && rows_h.p; }
-  std::atomic<uint64_t> flt_launches{0}, flt_rejected{0}, flt_f32_rows{0}, flt_shadow_rows{0};   // filtered launches whose call completed; evaluations the filter rejected; f32 rows / shadow rows they read at level 0
-  // the visited set of the last search launch (coltt_hnsw_visited_stats): 0 HBM byte map, 32 the LDS hash of 32-bit slots, 16 the 16-bit one (vis16.hpp); the
-  // traversals that launch kept resident per CU, its grid and, if it ran on the 16-bit table, the fullest stash and the most vertices one of its traversals
-  // visited; v16_launches: launches on the 16-bit table so far (one that overflowed and was re-run included)
-  std::atomic<int32_t> last_vis_kind{-1}; std::atomic<uint32_t> last_per_cu{0}, last_grid{0};
-  std::atomic<uint64_t> v16_launches{0}, last_stash_max{0}, last_visited_max{0};
-  void drop_shadow() { shadow = false; if (rows_h.p) { (void)hipFree(rows_h.p); rows_h.p = nullptr; rows_h.cap = 0; } (void)hipGetLastError(); }
-  // hnsw_pq.hpp: a snapshot of a trained product quantiser and one row-major code per slot (derived data, maintained like rows8:
-  // writers encode the slots they added before they release the exclusive lock)
-  bool pq_on = false; PqShape pq_shape; uint32_t pq_row = 0 /* bytes per code row: m rounded up to 16 */; uint64_t pq_done = 0;
-  DevBuf pq_cb, pq_codes, pq_stage;
-  // Neighbourhood blocks of the product-quantised walk (hnsw_pq.hpp: AdcEval<.., NBR>): pq_nbr[slot][p][pq_row] = pq_codes[adj0[slot][p]] (zeros for an
-  // empty position) — derived from the level-0 rows and the codes.  Built whole by the first product-quantised search that finds them stale (searches hold
-  // the lock shared and settle the build among themselves under pq_nbr_mu), then MAINTAINED by the writers like adj0_n: Insert / InsertBatchDevice / Remove
-  // raise pq_nbr_stale before their first device write and, if the blocks were current, re-gather the blocks of exactly the level-0 rows they rewrote
-  // (PqNbrPatch below) and lower it again before they release the exclusive lock — a call that does not reach its end leaves them stale.  Load / BulkLoad /
-  // PqAttach (everything renumbered or re-coded) and a grown slot capacity leave them stale: the next walk that reads them rebuilds.
-  DevBuf pq_nbr; bool pq_nbr_ok = false; std::atomic<bool> pq_nbr_stale{true}; std::mutex pq_nbr_mu;
-  bool pq_nbr_built = false;   // pq_nbr has held a whole build (a stale array is then state 2, not 0)
-  DevBuf pq_dirty;             // [0] = level-0 rows the link kernels of the mutation in flight rewrote, [2 ..] their slots (PqNbrPatch)
-  std::atomic<uint64_t> pq_nbr_builds{0}, pq_nbr_patches{0}, pq_nbr_patched_rows{0};
-  bool dense = true; uint64_t dense_base = 0;
-  std::unordered_map<uint64_t, uint32_t> id2slot;
-  std::vector<uint64_t> h_ids;       // !dense
-  std::vector<int32_t> h_levels;     // per slot
-  std::vector<uint32_t> h_upper_off; // per slot
-  std::vector<uint32_t> h_del;       // bitmap mirror
-  hipStream_t stream = nullptr;        // mutations (exclusive lock); searches use their context's stream
-  std::atomic<float> last_ms{0.f};     // kernel time of the most recently finished search call
-  CtxPool<HCtx> pool;
-  DevBuf w_raw, w_misc;
-  DevBuf b_head, b_req, b_levels; uint64_t head_cap = 0;  // builder scratch
-  // HBM visited set (hnsw_dev.hpp, VISG): vis_regions regions of vis_stride bytes; concurrent searches lease disjoint
-  // contiguous runs of regions (vis_busy), the builder (exclusive lock) uses all of them.
-  DevBuf w_visg, w_vepoch; uint64_t vis_stride = 0; uint32_t vis_regions = 0, vis_want = 0;
-  std::mutex vis_mu; std::condition_variable vis_cv; std::vector<uint8_t> vis_busy;
-  coltt_hnsw_stats build_stats{};
-  uint64_t gen = 0;   // bumped whenever the slots are renumbered (Load / bulk_load, a failed install): filters built before are stale
-  ~Hnsw() override {
-    (void)hipSetDevice(device);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-  GraphView view() const {
-    GraphView g;
-    g.rows = rows.as<uint8_t>(); g.stride = stride; g.norms = norms.as<float>();
-    g.rows8 = r8 ? rows.as<uint8_t>() : nullptr;   // the same array: which core reads it is the kernel's choice
-    g.ids = dense ? nullptr : ids.as<uint64_t>();
-    g.adj0 = adj0.as<uint32_t>(); g.adj0_d = adj0_d.as<float>(); g.upper_off = upper_off.as<uint32_t>();
-    g.adj0_n = metric == COLTT_COSINE ? adj0_n.as<float>() : nullptr;
-    g.adjU = adjU.as<uint32_t>(); g.adjU_d = adjU_d.as<float>();
-    g.del_bits = any_deleted ? del_bits.as<uint32_t>() : nullptr;
-    g.mMax = (uint32_t)cfg.m_max; g.mMax0 = (uint32_t)cfg.m_max0; g.dim = (int)dim;
-    g.rows_h = shadow ? rows_h.as<uint8_t>() : nullptr;
-    g.rows_b = shadow8 ? rows_b.as<uint8_t>() : nullptr;
-    g.rows_m = shadow8 ? rows_m.as<float2>() : nullptr;
-    g.adj0_m = shadow8 ? adj0_m.as<float2>() : nullptr;
-    return g;
-  }
-  int reserve(uint64_t slots, uint64_t upper_rows) {
-    if (slots > cap) {
-      uint64_t nc = std::max<uint64_t>({slots, cap + cap / 2, 1024});
-      COLTT_TRY(rows.reserve(nc * stride, true, stream));
-      if (shadow && rows_h.reserve(nc * (size_t)dim * 2, true, stream) != COLTT_OK) drop_shadow();   // not an error: no shadow, no filter
-      if (shadow8 && (rows_b.reserve(nc * (size_t)dim, true, stream) != COLTT_OK || rows_m.reserve(nc * 8, true, stream) != COLTT_OK ||
-                      adj0_m.reserve(nc * cfg.m_max0 * 8, true, stream) != COLTT_OK)) drop_shadow8();
-      COLTT_TRY(norms.reserve(nc * 4, true, stream));
-      if (!dense) COLTT_TRY(ids.reserve(nc * 8, true, stream));
-      COLTT_TRY(adj0.reserve(nc * cfg.m_max0 * 4, true, stream));
-      COLTT_TRY(adj0_d.reserve(nc * cfg.m_max0 * 4, true, stream));
-      if (metric == COLTT_COSINE) COLTT_TRY(adj0_n.reserve(nc * cfg.m_max0 * 4, true, stream));
-      COLTT_TRY(upper_off.reserve(nc * 4, true, stream));
-      size_t old_words = (cap + 31) / 32, new_words = (nc + 31) / 32;
-      COLTT_TRY(del_bits.reserve(new_words * 4, true, stream));
-      if (new_words > old_words) COLTT_HIP(hipMemsetAsync(del_bits.as<uint32_t>() + old_words, 0, (new_words - old_words) * 4, stream));
-      cap = nc;
-    }
-    if (upper_rows > ucap) {
-      uint64_t nc = std::max<uint64_t>({upper_rows, ucap + ucap / 2, 256});
-      COLTT_TRY(adjU.reserve(nc * cfg.m_max * 4, true, stream));
-      COLTT_TRY(adjU_d.reserve(nc * cfg.m_max * 4, true, stream));
-      ucap = nc;
-    }
-    return COLTT_OK;
-  }
-};
 
 int prep_rows_any(Hnsw* x, const float* d_raw, uint64_t n, uint64_t slot_base, bool normalize) {
   if (n == 0) return COLTT_OK;
@@ -589,8 +450,6 @@ int prep_rows_any(Hnsw* x, const float* d_raw, uint64_t n, uint64_t slot_base, b
   return COLTT_OK;
 }
 
-// derived per-slot data of the slots a writer added (the product quantiser's codes); completes on the device before it returns
-int sync_pq(Hnsw* x);
 // stored rows [first, first + m) -> the f32 values the index's distance sees (what the quantiser encodes), packed [m][dim]
 template <int QUANT, bool R8>
 __global__ void rows_to_f32_kernel(const uint8_t* __restrict__ rows, size_t stride, uint64_t first, uint64_t m, int dim, float* __restrict__ out) {
@@ -647,7 +506,11 @@ bool rows8_shape(uint32_t dim, int quant) {
   return ((size_t)dim * quant_bytes(quant)) % 128 == 0;
 }
 
-int prep_queries_any(Hnsw* x, HCtx* c, const float* d_qraw, size_t nq, uint32_t* zero64 = nullptr) {
+}  // namespace
+
+namespace coltt {
+namespace hnsw {
+int prep_queries_any(Hnsw* x, HCtx* c, const float* d_qraw, size_t nq, uint32_t* zero64) {
   COLTT_TRY(c->w_qeff.reserve(nq * x->dim * 4));
   COLTT_TRY(c->w_qn.reserve(nq * 4));
   int norm = x->metric == COLTT_COSINE;
@@ -658,11 +521,12 @@ int prep_queries_any(Hnsw* x, HCtx* c, const float* d_qraw, size_t nq, uint32_t*
   COLTT_HIP(hipGetLastError());
   return COLTT_OK;
 }
+void add_base(hipStream_t stream, uint64_t* ids, size_t n, uint64_t base) { add_base_kernel<<<ceil_div(n, 256), 256, 0, stream>>>(ids, n, base); }
+}  // namespace hnsw
+}  // namespace coltt
 
+namespace {
 uint32_t next_pow2(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
-
-struct SearchGeom { uint32_t ef, ef_pad, hcap; size_t lds; bool visg; uint32_t max_grid; int w2 = -1; uint32_t bloom_words = 0; bool w2_lds = false; bool ev8 = false; bool qd8i = false;
-                    bool vis16 = false; uint32_t v16_bits = 0, v16_limit = 0; };   // vis16: the LDS visited set at 16 bits per entry (vis16.hpp): log2 of its bucket count, the capacity rule's limit  // w2: hnsw_walk2.hpp variant (OPT bits | 8 = deep profile), -1 = hnsw_dev.hpp:search_level
 
 #ifndef COLTT_VISG_MIN_EF
 #define COLTT_VISG_MIN_EF 128
@@ -670,6 +534,10 @@ struct SearchGeom { uint32_t ef, ef_pad, hcap; size_t lds; bool visg; uint32_t m
 constexpr uint32_t VIS_MAX_REGIONS = 3072;  // 12 waves on each of 256 CUs: the product-quantised walk (3 per SIMD)
 constexpr uint32_t VIS_ROW_REGIONS = 2048;  // 8 waves per CU: the row walks and the builder
 
+}  // namespace
+
+namespace coltt {
+namespace hnsw {
 // (Re)allocate the HBM visited set for the current slot capacity: one byte per slot and workgroup, zeroed, epochs reset.
 // Sized against a quarter of the device memory; if that buys fewer than one region per CU the LDS hash is used instead.
 int ensure_visg(Hnsw* x) {
@@ -708,16 +576,6 @@ int ensure_visg(Hnsw* x) {
   return COLTT_OK;
 }
 
-// Lease a contiguous run of visited-set regions for one search launch: `want` if a free run that long exists, else the
-// longest free run; blocks while every region is out.  Released by the RegionLease destructor.
-struct RegionLease {
-  Hnsw* x = nullptr; uint32_t base = 0, count = 0;
-  ~RegionLease() {
-    if (!x || !count) return;
-    { std::lock_guard<std::mutex> g(x->vis_mu); for (uint32_t i = 0; i < count; i++) x->vis_busy[base + i] = 0; }
-    x->vis_cv.notify_all();
-  }
-};
 void acquire_regions(Hnsw* x, uint32_t want, RegionLease& out) {
   std::unique_lock<std::mutex> lk(x->vis_mu);
   const uint32_t R = (uint32_t)x->vis_busy.size();
@@ -739,17 +597,28 @@ void acquire_regions(Hnsw* x, uint32_t want, RegionLease& out) {
     x->vis_cv.wait(lk);
   }
 }
+}  // namespace hnsw
+}  // namespace coltt
 
+namespace {
 // COLTT_VISG=0 / 1 forces the LDS hash / the HBM byte map (measurement and test knob, read at every call); default: the
 // byte map above ef 128.  Measured on 10 M x 768 f16 (lowrank:32), queries/s LDS hash -> byte map: ef 128 728 k -> 724 k,
 // ef 256 246 k -> 404 k, ef 512 62 k -> 212 k, ef 1024 25 k -> 105 k; build (efConstruction 200) 36 s -> 22 s.
 int visg_policy() { return policy().visg; }
 
+}  // namespace
+
+namespace coltt {
+namespace hnsw {
 // does this ef want the HBM visited set (policy only; whether the workspace could be had is vis_regions > 0)
 bool wants_visg(uint32_t ef) {
   const int pol = visg_policy();
   return pol < 0 ? ef > COLTT_VISG_MIN_EF : pol != 0;
 }
+}  // namespace hnsw
+}  // namespace coltt
+
+namespace {
 
 // Which level-0 walk serves the HBM-visited searches.  COLTT_WALK2=off: hnsw_dev.hpp:search_level (the round-2 kernel);
 // COLTT_WALK2=<n>: hnsw_walk2.hpp with OPT = n (1 Bloom, 2 delta result set, 4 adjacency-carried norms); the library carries 6 and 7.
@@ -770,17 +639,22 @@ int walk2_policy() { const int v = policy().walk2; return v == 7 ? COLTT_WALK2_D
 #endif
 int walk2_lds_policy() { const int v = policy().walk2_lds; return v == 4 ? COLTT_WALK2_LDS_DEFAULT : v; }
 
-// resident waves per CU of the walk2 profiles: see waves_per_cu_cap
-size_t waves_per_cu_cap(int quant);
+// Resident waves per CU.  2-byte rows want all 8 (two per SIMD); f32 rows are faster with 4: eight 3-KB-per-row streams per
+// CU measured slower both in search (ef 256: 160 k vs 197 k q/s) and in the 10 M build (61 s vs 50 s).  COLTT_WAVES_PER_CU
+// overrides (measurement knob).
+size_t waves_per_cu_cap(int quant) {
+  if (policy().waves_per_cu > 0) return (size_t)policy().waves_per_cu;
+  return quant == Q_NONE ? 4 : 8;
+}
 
 // COLTT_EV8=0: level-0 distances from the pair-owned rows even when the index carries the line-transposed copy (A/B and test knob)
 bool ev8_policy() { return policy().ev8; }
 
-int row_filter_bits(const Hnsw* x);
-bool row_filter_on(const Hnsw* x, bool vis_hbm);
+}  // namespace
 
-// filt_k > 0: the filtered walk's allowed set (k rounded up to 64 entries) sits beside the result set (hnsw_kernels.hpp: search_one_wave)
-SearchGeom search_geom(Hnsw* x, uint32_t ef, bool for_search = false, bool no_w2_lds = false, uint32_t filt_k = 0) {
+namespace coltt {
+namespace hnsw {
+SearchGeom search_geom(Hnsw* x, uint32_t ef, bool for_search, bool no_w2_lds, uint32_t filt_k) {
   SearchGeom s;
   s.ef = ef;
   s.ef_pad = (ef + 63) & ~63u;
@@ -839,14 +713,6 @@ SearchGeom search_geom(Hnsw* x, uint32_t ef, bool for_search = false, bool no_w2
   return s;
 }
 
-// Resident waves per CU.  2-byte rows want all 8 (two per SIMD); f32 rows are faster with 4: eight 3-KB-per-row streams per
-// CU measured slower both in search (ef 256: 160 k vs 197 k q/s) and in the 10 M build (61 s vs 50 s).  COLTT_WAVES_PER_CU
-// overrides (measurement knob).
-size_t waves_per_cu_cap(int quant) {
-  if (policy().waves_per_cu > 0) return (size_t)policy().waves_per_cu;
-  return quant == Q_NONE ? 4 : 8;
-}
-
 // The walk over the 16-bit visited set is compiled for two waves per SIMD and its LDS fits seven times: all seven (COLTT_WAVES_PER_CU overrides here too).
 #ifndef COLTT_VIS16_WAVES_PER_CU
 #define COLTT_VIS16_WAVES_PER_CU 7
@@ -896,90 +762,11 @@ bool rows_nt(const Hnsw* x) {
   if (dbg) fprintf(stderr, "[rows_nt] slots=%llu stride=%zu row bytes=%llu threshold=%llu knob=%d -> %s\n", (unsigned long long)x->n, (size_t)x->stride, bytes, least, p.rows_nt, on ? "nt" : "default");
   return on;
 }
+}  // namespace hnsw
+}  // namespace coltt
 
-// hnsw_walk2.hpp kernels: the shipped variant (and its Bloom-less twin for geometries whose LDS has no room for the filter).
-template <int METRIC, int QUANT>
-int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
-                   uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
-  typedef void (*kern_t)(GraphView, int32_t, int32_t, const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*,
-                         uint64_t*, float*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*);
-  kern_t kern = nullptr;
-  const bool nt = rows_nt(x);   // non-temporal row loads (eight-lane kernels): see exact.hpp: row_ld
-  bool flt = false;             // the row-filter twin (row_filter_on)
-  bool v16 = false;             // ... over the 16-bit visited set (search_geom: vis16)
-#define COLTT_W2(V, PROF, OPT) case V: kern = hnsw_search2_kernel<METRIC, QUANT, PROF, OPT>; break;
-  if (sg.w2_lds) {
-    switch (sg.w2) {
-      case 4:
-        kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 4, VIS_LDS>;
-        if constexpr (QUANT != Q_F8) {
-          if (sg.ev8) kern = nt ? hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 4, VIS_LDS, false, true, false, true> : hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 4, VIS_LDS, false, true>;
-          else if (x->r8) kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 4, VIS_LDS, false, false, true>;   // the pair-owned core over the line-transposed rows
-        }
-        if constexpr (METRIC == M_COS && QUANT == Q_NONE) {   // the row-filter twin of the eight-lane instance just chosen
-          if (sg.ev8 && row_filter_on(x, false)) {
-            const int fb = row_filter_bits(x);
-            if (fb == ROW_FILTER_8I && sg.qd8i && sg.vis16) { kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS16, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS16, false, ROW_FILTER_8I>; v16 = true; }
-            else if (fb == ROW_FILTER_8I && sg.qd8i) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, ROW_FILTER_8I>;   // (sg.qd8i: search_geom made room for the digit planes)
-            else if (fb == 8 || fb == ROW_FILTER_8I) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, 8>;
-            else kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false>;
-            flt = true;
-          }
-        }
-        break;   // (adjacency prefetch for f32 rows in small batches: measured, no gain — 1 M x 128, ef 20, one query 105 vs 111 us)
-      default: break;
-    }
-  } else
-  {
-    switch (sg.w2) {
-      COLTT_W2(6, PROF_SEARCH_HBM, 6) COLTT_W2(7, PROF_SEARCH_HBM, 7)
-      default: break;
-    }
-    if constexpr (METRIC == M_COS && QUANT == Q_NONE) {   // W2_ADJN: both shipped HBM-visited variants carry the neighbours' norms
-      if (sg.ev8 && row_filter_on(x, true) && (sg.w2 == 6 || sg.w2 == 7)) flt = true;
-      if (flt && sg.w2 == 6) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false>;
-      if (flt && sg.w2 == 7) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false>;
-      const int fb = flt ? row_filter_bits(x) : 0;
-      if (fb == ROW_FILTER_8I && sg.qd8i) {
-        if (sg.w2 == 6) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false, ROW_FILTER_8I>;
-        if (sg.w2 == 7) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false, ROW_FILTER_8I>;
-      } else if (fb == 8 || fb == ROW_FILTER_8I) {
-        if (sg.w2 == 6) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false, 8>;
-        if (sg.w2 == 7) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false, 8>;
-      }
-    }
-    if constexpr (QUANT != Q_F8) { if (!flt) {
-      if (sg.ev8 && sg.w2 == 6) kern = nt ? hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 6, VIS_HBM, false, true, false, true> : hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 6, VIS_HBM, false, true>;
-      if (sg.ev8 && sg.w2 == 7) kern = nt ? hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 7, VIS_HBM, false, true, false, true> : hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 7, VIS_HBM, false, true>;
-      if (!sg.ev8 && x->r8 && sg.w2 == 6) kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 6, VIS_HBM, false, false, true>;
-      if (!sg.ev8 && x->r8 && sg.w2 == 7) kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 7, VIS_HBM, false, false, true>;
-    } }
-  }
-#undef COLTT_W2
-  if (!kern) return fail(COLTT_E_UNSUPPORTED, "hnsw_search: walk variant %d is not compiled into this build (COLTT_WALK2)", sg.w2);
-  if (x->r8 && !sg.ev8 && !(sg.w2_lds ? sg.w2 == 4 : (sg.w2 == 6 || sg.w2 == 7)))
-    return fail(COLTT_E_UNSUPPORTED, "hnsw_search: walk variant %d has no instance for line-transposed rows (create the index with COLTT_ROWS8=0 for this experiment)", sg.w2);
-  if (sg.ev8) x->ev8_launches.fetch_add(1);
-  if (sg.vis16 && !v16) return fail(COLTT_E_DEVICE, "hnsw_search: the launch's LDS was sized for the 16-bit visited set, but the walk chosen does not use it");
-  c->flt_launch = flt; c->v16_launch = v16;
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
-  static const bool dbg_occ = [] { const char* e = getenv("COLTT_DEBUG_OCCUPANCY"); return e && *e == '1'; }();   // diagnostics: the waves the runtime keeps resident per CU at this launch's LDS
-  if (dbg_occ || v16) {   // (the 16-bit launches report it through coltt_hnsw_visited_stats: asked once per (kernel, LDS) and context)
-    if (c->occ_kern != reinterpret_cast<const void*>(kern) || c->occ_lds != sg.lds) {
-      int per_cu = 0;
-      COLTT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64, sg.lds));
-      c->occ_kern = reinterpret_cast<const void*>(kern); c->occ_lds = sg.lds; c->occ_per_cu = per_cu;
-    }
-    if (dbg_occ) fprintf(stderr, "[occupancy] walk variant %d%s filter %d (8i planes %d) visited set %s: %zu B of LDS per wave, %d waves resident per CU, grid %u\n", sg.w2, sg.w2_lds ? " (LDS hash)" : "", flt ? 1 : 0, sg.qd8i ? 1 : 0,
-                         v16 ? "16-bit LDS table" : (sg.w2_lds ? "32-bit LDS table" : "HBM byte map"), sg.lds, c->occ_per_cu, grid);
-  }
-  kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
-                                        k, sg.ef, sg.ef_pad, sg.w2_lds ? (v16 ? ((sg.v16_limit << 8) | sg.v16_bits) : sg.hcap) : sg.bloom_words, counter, oi, os, oc, stats,
-                                        x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
-                                        x->w_vepoch.as<uint32_t>() + region_base);
-  COLTT_HIP(hipGetLastError());
-  return COLTT_OK;
-}
+namespace {
+// hnsw_walk2.hpp kernels: hnsw_search2.hip (launch_search2).
 
 template <int METRIC, int QUANT>
 int launch_search(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
@@ -1124,7 +911,7 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
   int rc;
 #define COLTT_LS_ARGS x, c, sg, grid, lease.base, (uint32_t)nq, k, counter, d_oi, d_os, d_oc, d_stats
 #define COLTT_LS(Q) rc = mw ? (x->metric == COLTT_COSINE ? launch_search_lat<M_COS, Q>(COLTT_LS_ARGS) : launch_search_lat<M_L2, Q>(COLTT_LS_ARGS)) \
-                     : sg.w2 >= 0 ? (x->metric == COLTT_COSINE ? launch_search2<M_COS, Q>(COLTT_LS_ARGS) : launch_search2<M_L2, Q>(COLTT_LS_ARGS)) \
+                     : sg.w2 >= 0 ? launch_search2(COLTT_LS_ARGS) /* hnsw_search2.hip: the same dispatch over its own kernels */ \
                             : (x->metric == COLTT_COSINE ? launch_search<M_COS, Q>(COLTT_LS_ARGS) : launch_search<M_L2, Q>(COLTT_LS_ARGS))
   COLTT_DISPATCH_QUANT(x->quant, COLTT_LS)
 #undef COLTT_LS
@@ -1200,6 +987,10 @@ __global__ void pq_nbr_build_kernel(const uint32_t* __restrict__ adj0, const uin
   if (nb != NBR_NONE) v = *reinterpret_cast<const u32x4v*>(codes + (size_t)nb * row_bytes + (size_t)pc * 16);
   *reinterpret_cast<u32x4v*>(nbr + e * row_bytes + (size_t)pc * 16) = v;
 }
+}  // namespace
+
+namespace coltt {
+namespace hnsw {
 // Called by a search (shared lock held).  *use: the blocks are there and current.  They cost n x mMax0 x pq_row bytes (20.5 GB at 10 M x 32 x 64): an index
 // that cannot afford them (less than twice that free) keeps gathering by neighbour slot.
 int ensure_pq_nbr(Hnsw* x, hipStream_t stream, bool* use) {
@@ -1229,6 +1020,10 @@ int ensure_pq_nbr(Hnsw* x, hipStream_t stream, bool* use) {
   *use = true;
   return COLTT_OK;
 }
+}  // namespace hnsw
+}  // namespace coltt
+
+namespace {
 // ---- the writers' side of the neighbourhood blocks: re-gather the blocks of the level-0 rows a mutation rewrote -------------------------------------
 // the blocks of the listed slots, as pq_nbr_build_kernel writes them: one thread per 16-byte piece of nbr[slots[i]][p][row_bytes].  count (may be NULL: all
 // `cap` entries) = the device counter the link kernels appended under; a slot or a neighbour outside [0, n_slots) is skipped (never the case).
@@ -1293,8 +1088,6 @@ int pq_nbr_patch_end(Hnsw* x, const PqNbrPatch& t, uint64_t first_new, uint64_t 
   x->pq_nbr_stale.store(false);
   return COLTT_OK;
 }
-// log2 of a table row in LDS: the centroid count rounded up to a power of two, at least 16 (codes >= C never occur)
-uint32_t pq_lut_shift(const Hnsw* x) { uint32_t sh = 4; while ((1u << sh) < x->pq_shape.C) sh++; return sh; }
 // Resident traversals per CU of the product-quantised walk (120 VGPRs: four waves per SIMD would fit; the LDS decides below that — 16 instead of 12
 // measured nothing, profiles/r05s_pq_ab.md).
 // The walk over the byte map carries NO Bloom filter (the row walks do, hnsw_walk2.hpp): the probe of the byte map is one wave-wide load that is
@@ -1303,7 +1096,6 @@ uint32_t pq_lut_shift(const Hnsw* x) { uint32_t sh = 4; while ((1u << sh) < x->p
 // front of every probe plus 2-4 KiB of LDS per traversal (one resident wave per CU at ef 1 408).  Same box, 10 M x 768 f16, 64 x 32 quantiser
 // (profiles/r05s_pq_ab.md): ef 1 024 410 -> 440 k queries/s, ef 1 408 277 -> 316 k.
 constexpr size_t PQ_WAVES_CAP = 12;
-struct PqGeom { uint32_t ef, ef_pad, vis_words; size_t lds; int variant; /* 0: LDS hash | 2: byte map + delta result set */ uint32_t per_cu; };
 // filt_cap: the capacity of the allowed set R of a filtered walk (coltt_hnsw_pq_search_filtered), 0 = no filter
 bool pq_geom(Hnsw* x, uint32_t ef, bool force_hbm, PqGeom& out, uint32_t filt_cap = 0) {
   PqGeom s{};
@@ -1329,9 +1121,13 @@ bool pq_geom(Hnsw* x, uint32_t ef, bool force_hbm, PqGeom& out, uint32_t filt_ca
   return true;
 }
 
+}  // namespace
+
+namespace coltt {
+namespace hnsw {
 int launch_pq_walk(Hnsw* x, HCtx* c, const PqGeom& sg, bool nbr, uint32_t grid, uint32_t region_base, const unsigned short* lut, uint32_t nq, uint32_t k,
-                   uint32_t rerank, uint32_t* counter, uint32_t* surv, uint32_t* surv_cnt, unsigned long long* stats, const FilterView* fv = nullptr, uint32_t fcap = 0,
-                   const PqFiltQuery* pd = nullptr) {
+                   uint32_t rerank, uint32_t* counter, uint32_t* surv, uint32_t* surv_cnt, unsigned long long* stats, const FilterView* fv, uint32_t fcap,
+                   const PqFiltQuery* pd) {
   const uint32_t sh = pq_lut_shift(x);
   // table row length x code-row pieces as compile-time constants for the common quantisers: 64 sub-vectors x 16 / 32 centroids (LS 4 / 5, 4 pieces),
   // 32 x 256 — the reference's shape, playground/hnswpq_verification.go:69-73 — (LS 8, 2 pieces), 96 x 256 (LS 8, 6 pieces); anything else runs the
@@ -1363,8 +1159,48 @@ int launch_pq_walk(Hnsw* x, HCtx* c, const PqGeom& sg, bool nbr, uint32_t grid, 
   COLTT_HIP(hipGetLastError());
   return COLTT_OK;
 }
+}  // namespace hnsw
+}  // namespace coltt
+
+namespace {
+}  // namespace
+
+// (not a template: it stands in the one translation unit that launches it)
+namespace coltt {
+namespace kern {
+// step 2: the k smallest keys of a query — (exact score bits, slot) order — by k rounds of a wave minimum over the keys staged in LDS
+__global__ __launch_bounds__(64) void hnsw_pq_select_kernel(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ surv_cnt, uint32_t ef_pad, uint32_t k,
+                                                            const uint64_t* __restrict__ ids, uint64_t* __restrict__ out_ids, float* __restrict__ out_scores,
+                                                            uint32_t* __restrict__ out_counts, const PqFiltQuery* __restrict__ pd = nullptr) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  unsigned long long* const res = reinterpret_cast<unsigned long long*>(smem);
+  const uint32_t qi = blockIdx.x, r = surv_cnt[qi];
+  const uint32_t row = pd ? pd[qi].row : qi;   // pd (coltt_hnsw_pq_search_filtered_batch): query qi of the launch answers batch row pd[qi].row
+  const int lane_in = threadIdx.x;
+  for (uint32_t i = (uint32_t)lane_in; i < r; i += 64) res[i] = keys[(size_t)qi * ef_pad + i];
+  wave_sync();
+  const uint32_t n = r < k ? r : k;
+  for (uint32_t t = 0; t < n; t++) {
+    const int lane = opaque_lane(lane_in);
+    unsigned long long best = ~0ull; uint32_t bi = 0;
+    for (uint32_t i = (uint32_t)lane; i < r; i += 64) { const unsigned long long e = res[i]; if (e < best) { best = e; bi = i; } }
+    const unsigned long long km = wave_min_u64(best);
+    if (best == km && km != ~0ull) {   // keys are distinct (a slot appears once): exactly one lane
+      const uint32_t slot = (uint32_t)km >> 1;
+      out_ids[(size_t)row * k + t] = ids ? ids[slot] : (uint64_t)slot;
+      out_scores[(size_t)row * k + t] = __uint_as_float((uint32_t)(km >> 32));
+      res[bi] = ~0ull;
+    }
+    wave_sync();
+  }
+  if (lane_in == 0) out_counts[row] = n;
+}
+}  // namespace kern
+}  // namespace coltt
+
+namespace {
 template <int METRIC, int QUANT>
-int launch_pq_rerank(Hnsw* x, HCtx* c, const PqGeom& sg, uint32_t q0, uint32_t nq, uint32_t k, const uint32_t* surv, const uint32_t* surv_cnt,
+int launch_pq_rerank_for(Hnsw* x, HCtx* c, const PqGeom& sg, uint32_t q0, uint32_t nq, uint32_t k, const uint32_t* surv, const uint32_t* surv_cnt,
                      unsigned long long* keys, uint64_t* oi, float* os, uint32_t* oc, const PqFiltQuery* pd = nullptr, const float* pd_qe = nullptr,
                      const float* pd_qn = nullptr) {
   const dim3 grid(ceil_div(sg.ef_pad, 32), nq);
@@ -1379,6 +1215,21 @@ int launch_pq_rerank(Hnsw* x, HCtx* c, const PqGeom& sg, uint32_t q0, uint32_t n
   COLTT_HIP(hipGetLastError());
   return COLTT_OK;
 }
+}  // namespace
+
+namespace coltt {
+namespace hnsw {
+// the re-rank for the index's metric and row format (attach refuses "f8" rows)
+int launch_pq_rerank(Hnsw* x, HCtx* c, const PqGeom& sg, uint32_t q0, uint32_t nq, uint32_t k, const uint32_t* surv, const uint32_t* surv_cnt,
+                     unsigned long long* keys, uint64_t* oi, float* os, uint32_t* oc, const PqFiltQuery* pd, const float* pd_qe, const float* pd_qn) {
+  int rc;
+#define COLTT_LP_ARGS x, c, sg, q0, nq, k, surv, surv_cnt, keys, oi, os, oc, pd, pd_qe, pd_qn
+#define COLTT_LP(Q) rc = x->metric == COLTT_COSINE ? launch_pq_rerank_for<M_COS, Q>(COLTT_LP_ARGS) : launch_pq_rerank_for<M_L2, Q>(COLTT_LP_ARGS)
+  if (x->quant == COLTT_Q_NONE) { COLTT_LP(Q_NONE); } else { COLTT_LP(Q_F16); }
+#undef COLTT_LP
+#undef COLTT_LP_ARGS
+  return rc;
+}
 
 // the geometry of one walk at ef, as every entry point decides it: the LDS hash unless the policy, the caller (force_hbm) or the table's size says the byte map
 int pq_walk_geom(Hnsw* x, uint32_t ef, bool force_hbm, uint32_t fcap, PqGeom& sg) {
@@ -1388,8 +1239,10 @@ int pq_walk_geom(Hnsw* x, uint32_t ef, bool force_hbm, uint32_t fcap, PqGeom& sg
   if (!have) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search: dim %u / ef %u / %u sub-vectors need more than the CU's 160 KiB of LDS", x->dim, ef, x->pq_shape.m);
   return COLTT_OK;
 }
-// the capacity of a filtered walk's allowed set R: what the re-rank may read
-inline uint32_t pq_filt_cap(uint32_t ef, uint32_t k, uint32_t rerank) { return rerank == 0 ? ef : std::min(std::max(rerank, k), ef); }
+}  // namespace hnsw
+}  // namespace coltt
+
+namespace {
 
 // one attempt; *retry_hbm: the LDS hash would have needed its reset path — the caller runs the same call over the byte map
 // fv (coltt_hnsw_pq_search_filtered, WALK): the walk also keeps the allowed set R and the re-rank is over R; ef_override is then ef_walk (>= k)
@@ -1453,13 +1306,7 @@ int pq_search_once(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_
     if (q0) COLTT_HIP(hipMemsetAsync(counter, 0, 4, c->stream));
     COLTT_TRY(launch_pq_walk(x, c, sg, nbr, (uint32_t)std::min<size_t>(grid, gn), lease.base, c->w_pack.as<unsigned short>(), (uint32_t)gn, k, rerank, counter, c->w_surv.as<uint32_t>(),
                              c->w_scnt.as<uint32_t>(), d_stats, fv, fcap));
-    int rc;
-#define COLTT_LP_ARGS x, c, sg, (uint32_t)q0, (uint32_t)gn, k, c->w_surv.as<uint32_t>(), c->w_scnt.as<uint32_t>(), c->w_keys.as<unsigned long long>(), d_oi, d_os, d_oc
-#define COLTT_LP(Q) rc = x->metric == COLTT_COSINE ? launch_pq_rerank<M_COS, Q>(COLTT_LP_ARGS) : launch_pq_rerank<M_L2, Q>(COLTT_LP_ARGS)
-    if (x->quant == COLTT_Q_NONE) { COLTT_LP(Q_NONE); } else { COLTT_LP(Q_F16); }
-#undef COLTT_LP
-#undef COLTT_LP_ARGS
-    COLTT_TRY(rc);
+    COLTT_TRY(launch_pq_rerank(x, c, sg, (uint32_t)q0, (uint32_t)gn, k, c->w_surv.as<uint32_t>(), c->w_scnt.as<uint32_t>(), c->w_keys.as<unsigned long long>(), d_oi, d_os, d_oc));
   }
   COLTT_HIP(hipEventRecord(c->ev1, c->stream));
   if (x->dense && x->dense_base) add_base_kernel<<<ceil_div(nq * k, 256), 256, 0, c->stream>>>(d_oi, nq * k, x->dense_base);
@@ -1500,6 +1347,10 @@ int pq_search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, siz
   if (retry) COLTT_TRY(pq_search_once(x, c, queries, on_device, nq, k, ef_override, rerank, out_ids, out_scores, out_counts, stats, out_n_exact, true, &retry));
   return COLTT_OK;
 }
+}  // namespace
+
+namespace coltt {
+namespace hnsw {
 // coltt_hnsw_pq_search_filtered, WALK: pq_search_common at ef_walk with the allowed set
 int pq_search_filtered_walk(Hnsw* x, HCtx* c, const FilterView& fv, const float* queries, size_t nq, uint32_t k, uint32_t ef_walk, uint32_t rerank,
                             uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_stats* stats, uint64_t* out_n_exact) {
@@ -1508,6 +1359,10 @@ int pq_search_filtered_walk(Hnsw* x, HCtx* c, const FilterView& fv, const float*
   if (retry) COLTT_TRY(pq_search_once(x, c, queries, false, nq, k, ef_walk, rerank, out_ids, out_scores, out_counts, stats, out_n_exact, true, &retry, &fv));
   return COLTT_OK;
 }
+}  // namespace hnsw
+}  // namespace coltt
+
+namespace {
 
 // pruneNeighbors as Remove calls it (hnsw.go:234-236): rebuild the row from its non-deleted entries (<= width, so
 // nothing is trimmed).  One thread per (neighbour, level) row.
@@ -2713,18 +2568,6 @@ int coltt_hnsw_rows8_searches(coltt_handle_t h, uint64_t* out_launches, int32_t*
   return COLTT_OK;
 }
 
-int coltt_hnsw_row_filter_stats(coltt_handle_t h, uint64_t* out_rejected, uint64_t* out_f32_rows, uint64_t* out_shadow_rows, uint64_t* out_launches, int32_t* out_has_shadow) {
-  auto x = lookup<Hnsw>(h);
-  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_row_filter_stats: unknown handle");
-  ReadLock g(x->rw);
-  if (out_rejected) *out_rejected = x->flt_rejected.load();
-  if (out_f32_rows) *out_f32_rows = x->flt_f32_rows.load();
-  if (out_launches) *out_launches = x->flt_launches.load();
-  if (out_shadow_rows) *out_shadow_rows = x->flt_shadow_rows.load();
-  if (out_has_shadow) *out_has_shadow = (x->has_shadow16() ? 16 : 0) | (x->has_shadow8() ? 8 : 0);   // non-zero: some shadow is kept; bit 3 / bit 4: which
-  return COLTT_OK;
-}
-
 int coltt_hnsw_visited_stats(coltt_handle_t h, int32_t* out_kind, uint32_t* out_waves_per_cu, uint32_t* out_grid, uint64_t* out_launches16, uint64_t* out_stash_max, uint64_t* out_visited_max) {
   auto x = lookup<Hnsw>(h);
   if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_visited_stats: unknown handle");
@@ -2735,87 +2578,6 @@ int coltt_hnsw_visited_stats(coltt_handle_t h, int32_t* out_kind, uint32_t* out_
   if (out_launches16) *out_launches16 = x->v16_launches.load();
   if (out_stash_max) *out_stash_max = x->last_stash_max.load();
   if (out_visited_max) *out_visited_max = x->last_visited_max.load();
-  return COLTT_OK;
-}
-
-int coltt_hnsw_fetch_shadow8(coltt_handle_t h, uint64_t first_slot, uint64_t n, int8_t* out_codes, float* out_meta, float* out_adj_meta) {
-  auto x = lookup<Hnsw>(h);
-  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_fetch_shadow8: unknown handle");
-  ReadLock g(x->rw);
-  if (!x->has_shadow8()) return fail(COLTT_E_UNSUPPORTED, "hnsw_fetch_shadow8: the index keeps no 8-bit shadow");
-  if (first_slot > x->n || n > x->n - first_slot) return fail(COLTT_E_INVALID, "hnsw_fetch_shadow8: range outside [0,%llu)", (unsigned long long)x->n);
-  if (n == 0) return COLTT_OK;
-  COLTT_DEVICE(x->device);
-  const size_t dim = x->dim, w = x->cfg.m_max0;
-  if (out_codes) {   // rows8.hpp's layout -> natural element order, on the host (a read-back for tests and tools)
-    std::vector<uint8_t> raw(n * dim);
-    COLTT_HIP(hipMemcpy(raw.data(), x->rows_b.as<uint8_t>() + first_slot * dim, n * dim, hipMemcpyDeviceToHost));
-    for (uint64_t i = 0; i < n; i++)
-      for (size_t e = 0; e < dim; e++) {
-        const size_t r = e & 7, step = e >> 3, l = step >> 2, t_ = step & 3;
-        out_codes[i * dim + e] = (int8_t)raw[i * dim + ((l >> 2) * 8 + r) * 16 + (l & 3) * 4 + t_];
-      }
-  }
-  if (out_meta) COLTT_HIP(hipMemcpy(out_meta, x->rows_m.as<uint8_t>() + first_slot * 8, n * 8, hipMemcpyDeviceToHost));
-  if (out_adj_meta) COLTT_HIP(hipMemcpy(out_adj_meta, x->adj0_m.as<uint8_t>() + first_slot * w * 8, n * w * 8, hipMemcpyDeviceToHost));
-  return COLTT_OK;
-}
-
-int coltt_hnsw_row_filter_probe(coltt_handle_t h, const float* queries, size_t nq, const uint32_t* slots, const float* lower_bound, int bits, int nt,
-                                int full_at_pop, float* out_r, float* out_qnorm, float* out_rnorm, uint32_t* out_counts) {
-  if (bits != 8 && bits != 16) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: bits must be 8 or 16");
-  return coltt_hnsw_row_filter_probe_ex(h, queries, nq, slots, lower_bound, bits, nt, full_at_pop, out_r, out_qnorm, out_rnorm, out_counts, nullptr, nullptr);
-}
-
-int coltt_hnsw_row_filter_probe_ex(coltt_handle_t h, const float* queries, size_t nq, const uint32_t* slots, const float* lower_bound, int bits, int nt,
-                                   int full_at_pop, float* out_r, float* out_qnorm, float* out_rnorm, uint32_t* out_counts, int64_t* out_isum, float* out_qte) {
-  auto x = lookup<Hnsw>(h);
-  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_row_filter_probe: unknown handle");
-  if (bits != 8 && bits != 16 && bits != ROW_FILTER_8I) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: bits must be 8, 16 or 80 (8i)");
-  const bool k8i = bits == ROW_FILTER_8I;
-  if (nq && (!queries || !slots || !lower_bound || !out_r || !out_qnorm || !out_rnorm || !out_counts)) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: NULL buffer");
-  if (nq > 0x7fffffffu / 32) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: too many queries");
-  ReadLock g(x->rw);
-  if (!x->r8 || (bits != 16 ? !x->has_shadow8() : !x->has_shadow16())) return fail(COLTT_E_UNSUPPORTED, "hnsw_row_filter_probe: the index keeps no %d-bit shadow", bits == 16 ? 16 : 8);
-  if (nq == 0) return COLTT_OK;
-  for (size_t i = 0; i < nq * 32; i++)
-    if (slots[i] != NBR_NONE && slots[i] >= x->n) return fail(COLTT_E_INVALID, "hnsw_row_filter_probe: slot %u outside [0,%llu)", slots[i], (unsigned long long)x->n);
-  COLTT_DEVICE(x->device);
-  CtxLease<HCtx> ctx(x->pool);
-  if (!ctx.c) return COLTT_E_DEVICE;
-  HCtx* c = ctx.c;
-  const size_t dim = x->dim;
-  COLTT_TRY(c->w_qraw.reserve(nq * dim * 4));
-  COLTT_TRY(c->w_misc.reserve(256));
-  // one block of inputs and outputs: slots [nq][32] | lower_bound [nq] | out_r [nq][32] | out_rnorm [nq][32] | out_counts [nq][3]
-  // (8i: | pad to 8 bytes | out_isum [nq][32] i64 | out_qte [nq][2])
-  COLTT_TRY(c->w_out_ids.reserve(nq * (32 * 3 + 1 + 3) * 4 + 8 + nq * (32 * 8 + 2 * 4)));
-  uint32_t* d_slots = c->w_out_ids.as<uint32_t>();
-  float* d_lb = reinterpret_cast<float*>(d_slots + nq * 32);
-  float* d_r = d_lb + nq; float* d_rn = d_r + nq * 32;
-  uint32_t* d_cnt = reinterpret_cast<uint32_t*>(d_rn + nq * 32);
-  COLTT_HIP(hipMemcpyAsync(c->w_qraw.p, queries, nq * dim * 4, hipMemcpyHostToDevice, c->stream));
-  COLTT_HIP(hipMemcpyAsync(d_slots, slots, nq * 32 * 4, hipMemcpyHostToDevice, c->stream));
-  COLTT_HIP(hipMemcpyAsync(d_lb, lower_bound, nq * 4, hipMemcpyHostToDevice, c->stream));
-  COLTT_TRY(prep_queries_any(x.get(), c, c->w_qraw.as<float>(), nq, c->w_misc.as<uint32_t>()));   // Normalize the queries as Search does
-  long long* d_isum = reinterpret_cast<long long*>((reinterpret_cast<uintptr_t>(d_cnt + nq * 3) + 7) & ~(uintptr_t)7);
-  float* d_qte = reinterpret_cast<float*>(d_isum + nq * 32);
-  if (k8i) COLTT_HIP(hipMemsetAsync(d_isum, 0, nq * (32 * 8 + 2 * 4), c->stream));
-  const size_t lds = ((dim * 4 + 15) & ~(size_t)15) + 96 * 4 + (k8i ? dim * 2 : 0);   // 8i: the digit planes behind the scratch
-  auto kern = k8i ? (nt ? hnsw_row_filter_probe_kernel<true, ROW_FILTER_8I> : hnsw_row_filter_probe_kernel<false, ROW_FILTER_8I>)
-            : bits == 8 ? (nt ? hnsw_row_filter_probe_kernel<true, 8> : hnsw_row_filter_probe_kernel<false, 8>)
-                        : (nt ? hnsw_row_filter_probe_kernel<true, 16> : hnsw_row_filter_probe_kernel<false, 16>);
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kern<<<(uint32_t)nq, 64, lds, c->stream>>>(x->view(), c->w_qeff.as<float>(), c->w_qn.as<float>(), d_slots, d_lb, full_at_pop ? 1 : 0, d_r, d_rn, d_cnt,
-                                             k8i ? d_isum : nullptr, k8i ? d_qte : nullptr);
-  COLTT_HIP(hipGetLastError());
-  if (k8i && out_isum) COLTT_HIP(hipMemcpyAsync(out_isum, d_isum, nq * 32 * 8, hipMemcpyDeviceToHost, c->stream));
-  if (k8i && out_qte) COLTT_HIP(hipMemcpyAsync(out_qte, d_qte, nq * 2 * 4, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(out_r, d_r, nq * 32 * 4, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(out_rnorm, d_rn, nq * 32 * 4, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(out_counts, d_cnt, nq * 3 * 4, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(out_qnorm, c->w_qn.p, nq * 4, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipStreamSynchronize(c->stream));
   return COLTT_OK;
 }
 
@@ -2830,26 +2592,6 @@ int coltt_last_kernel_ms(coltt_handle_t h, float* out_ms) {
 // ---- Filtered search: an allow-list of ids against one index (coltt_hnsw_filter_*, coltt_hnsw_search_filtered) ----------------------
 // An extension the reference does not have (its Core.HybridSearch post-filters an unfiltered search): definitions in include/coltt_gpu.h.
 namespace {
-
-// The two device allocations the outputs of one coltt_hnsw_filter_eval(_batch) call share (filter_expr.hpp): freed when the last output goes.
-struct FilterSlab {
-  int device = 0;
-  DevBuf bits, lists;
-  ~FilterSlab() { (void)hipSetDevice(device); }
-};
-
-struct HnswFilter : Object {
-  coltt_handle_t index = 0; uint64_t gen = 0;   // built against this index at this generation (Hnsw::gen)
-  uint32_t slots = 0;                           // the index's slots when the filter was built: the bitmap covers [0, slots)
-  uint64_t allowed = 0;
-  DevBuf bits;   // [ceil(slots / 32)] u32, bit s = slot s allowed
-  DevBuf list;   // [allowed] u32, the allowed slots ascending (the exact path's gather list)
-  std::shared_ptr<FilterSlab> slab;   // set: bits and list point into the slab and are not this filter's to free
-  ~HnswFilter() override {
-    (void)hipSetDevice(device);
-    if (slab) { bits.p = nullptr; list.p = nullptr; }
-  }
-};
 
 // An attribute column (coltt_hnsw_attr_*; include/coltt_gpu.h, "Attribute columns and predicates").  `rw` is the column's own lock: attr_set holds
 // it exclusive (and the index's shared), attr_get and an evaluation hold it shared.
@@ -2877,552 +2619,6 @@ inline bool live_slot_of(const Hnsw* x, uint64_t id, uint32_t& s) {
   return true;
 }
 
-// AUTO: with A allowed vertices out of n_live, a walk at ef meets about ef * A / n_live allowed ones among its result-set-sized share of
-// the walk; ef_need raises the breadth so that about ef of them are met.  The exact scan reads A rows and has no dependent chain; the walk
-// evaluates about 32 rows per unit of ef (n_dist / ef = 4 040 / 128 on the headline collection), so the scan wins on rows read while
-// A <= FILTER_ROWS_PER_EF * ef_walk.
-constexpr uint64_t FILTER_EF_MAX = 4096;
-#ifndef COLTT_FILTER_ROWS_PER_EF
-#define COLTT_FILTER_ROWS_PER_EF 32
-#endif
-int filter_path(uint64_t allowed, uint64_t n_live, uint32_t ef, int mode, uint32_t& ef_walk) {
-  ef_walk = ef;
-  if (mode == COLTT_FILTER_WALK) return COLTT_FILTER_WALK;
-  if (mode == COLTT_FILTER_EXACT || allowed == 0) return COLTT_FILTER_EXACT;
-  const uint64_t ef_need = ((uint64_t)ef * n_live + allowed - 1) / allowed;
-  ef_walk = (uint32_t)std::min<uint64_t>(FILTER_EF_MAX, std::max<uint64_t>(ef, ef_need));
-  if (ef_need > FILTER_EF_MAX || allowed <= (uint64_t)COLTT_FILTER_ROWS_PER_EF * ef_walk) return COLTT_FILTER_EXACT;
-  return COLTT_FILTER_WALK;
-}
-
-// ---- What the filtered drivers share (filter_search_common, filter_batch_common, pq_filter_search_common, pq_filter_batch_common); `who` is the entry
-// point's name in the messages.
-
-// The argument checks and the breadth.  ef == 0 on COLTT_OK: no queries, nothing to do.
-int filter_args(const Hnsw* x, const char* who, size_t nq, uint32_t k, uint32_t ef_override, int mode, coltt_hnsw_filter_stats* st, uint32_t& ef) {
-  std::memset(st, 0, sizeof(*st));
-  ef = 0;
-  if (mode != COLTT_FILTER_AUTO && mode != COLTT_FILTER_WALK && mode != COLTT_FILTER_EXACT) return fail(COLTT_E_INVALID, "%s: unknown mode %d", who, mode);
-  if (nq == 0) return COLTT_OK;
-  if (k == 0) return fail(COLTT_E_INVALID, "%s: k must be >= 1", who);
-  if (nq > 0xffffffffull) return fail(COLTT_E_UNSUPPORTED, "%s: more than 2^32-1 queries in one call", who);
-  const uint32_t e = std::max<uint32_t>(ef_override ? ef_override : (uint32_t)x->cfg.ef, k);   // as Search (hnsw.go:258)
-  if (e > FILTER_EF_MAX) return fail(COLTT_E_UNSUPPORTED, "%s: ef=%u > %llu", who, e, (unsigned long long)FILTER_EF_MAX);
-  ef = e;
-  return COLTT_OK;
-}
-
-// Each query's path from its own filter's allowed count (n_live read once, under the caller's read lock).  walk_q / exact_q: the served
-// queries (a non-empty filter on a non-empty index); none served — only empty filters, or an empty index — is counts 0, not an error.
-struct FiltRoute {
-  std::vector<uint32_t> efw, walk_q, exact_q;
-  bool none() const { return walk_q.empty() && exact_q.empty(); }
-};
-void filter_route(const Hnsw* x, const std::vector<HnswFilter*>& fl, size_t nq, uint32_t ef, int mode, int32_t* out_paths, uint32_t* out_counts,
-                  coltt_hnsw_filter_stats* st, FiltRoute& r) {
-  const uint64_t n_live = x->live;
-  r.efw.resize(nq);
-  bool any_walk = false, any_exact = false;
-  for (size_t i = 0; i < nq; i++) {
-    const int path = filter_path(fl[i]->allowed, n_live, ef, mode, r.efw[i]);
-    if (out_paths) out_paths[i] = path;
-    if (path == COLTT_FILTER_WALK) { any_walk = true; st->ef_walk = std::max(st->ef_walk, r.efw[i]); }
-    else any_exact = true;
-    if (x->entry < 0 || fl[i]->allowed == 0) continue;
-    (path == COLTT_FILTER_WALK ? r.walk_q : r.exact_q).push_back((uint32_t)i);
-  }
-  st->path = any_walk && any_exact ? COLTT_FILTER_AUTO : any_walk ? COLTT_FILTER_WALK : COLTT_FILTER_EXACT;
-  if (r.none()) std::memset(out_counts, 0, nq * 4);
-}
-
-// The exact path of a batch with a filter per query (coltt_hnsw_search_filtered_batch, coltt_hnsw_pq_search_filtered_batch): the rows of exact_q
-// sorted by filter, groups of <= qg sharing one, chunk lists as launch_filter_exact sizes them.
-// eq / tiles: what the scan and the select read; d_eq / d_tiles: where filter_upload put them.
-struct FiltExactPlan {
-  uint32_t qg = 0; std::vector<FiltExactQ> eq; std::vector<FiltTile> tiles; uint64_t nlists = 0;
-  const FiltExactQ* d_eq = nullptr; const FiltTile* d_tiles = nullptr;
-};
-// The answer's three device buffers.
-struct FiltOut { uint64_t* oi; float* os; uint32_t* oc; };
-
-template <int METRIC, int QUANT>
-int launch_search_filtered_batch(Hnsw* x, HCtx* c, bool visg, size_t lds, uint32_t grid, uint32_t region_base, uint32_t nw, uint32_t k,
-                                 const FiltQuery* fq, uint32_t* counter, uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
-  auto kern = visg ? hnsw_search_filtered_batch_kernel<METRIC, QUANT, true> : hnsw_search_filtered_batch_kernel<METRIC, QUANT, false>;
-  if constexpr (QUANT != Q_F8) { if (x->r8) kern = visg ? hnsw_search_filtered_batch_kernel<METRIC, QUANT, true, true> : hnsw_search_filtered_batch_kernel<METRIC, QUANT, false, true>; }
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kern<<<grid, 64, lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nw, k, fq, counter, oi, os, oc, stats,
-                                     x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
-                                     x->w_vepoch.as<uint32_t>() + region_base);
-  COLTT_HIP(hipGetLastError());
-  return COLTT_OK;
-}
-
-template <int METRIC, int QUANT>
-int launch_filter_exact_batch(Hnsw* x, HCtx* c, const FiltExactPlan& ep, uint32_t k, const FiltOut& o, unsigned long long* stats) {
-  const size_t qbytes = (((size_t)x->dim + 3) & ~(size_t)3) * 4, kbytes = (size_t)((k + 63) & ~63u) * 8;
-  const size_t lds = ep.qg * (qbytes + kbytes);
-  COLTT_TRY(c->w_keys.reserve((size_t)ep.nlists * k * 8));
-  COLTT_TRY(c->w_scnt.reserve((size_t)ep.nlists * 4));
-  GraphView gv = x->view();
-  auto scan = hnsw_filter_scan_batch_kernel<METRIC, QUANT, false>;
-  if constexpr (QUANT != Q_F8) { if (x->r8) scan = hnsw_filter_scan_batch_kernel<METRIC, QUANT, true>; }
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  scan<<<(uint32_t)ep.tiles.size(), 64, lds, c->stream>>>(gv, c->w_qeff.as<float>(), c->w_qn.as<float>(), ep.d_tiles, ep.d_eq, ep.qg, k, (k + 63) & ~63u,
-                                                          c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), stats);
-  COLTT_HIP(hipGetLastError());
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_filter_select_batch_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kbytes));
-  hnsw_filter_select_batch_kernel<><<<(uint32_t)ep.eq.size(), 64, kbytes, c->stream>>>(c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), ep.d_eq, k, gv.ids,
-                                                                                       o.oi, o.os, o.oc);
-  COLTT_HIP(hipGetLastError());
-  return COLTT_OK;
-}
-// the exact scan and its select over the uploaded plan, if any query took the exact path
-int run_filter_exact(Hnsw* x, HCtx* c, const FiltExactPlan& ep, uint32_t k, const FiltOut& o, unsigned long long* d_stats) {
-  if (ep.eq.empty()) return COLTT_OK;
-  const bool cos = x->metric == COLTT_COSINE;
-  int rc = COLTT_OK;
-#define COLTT_FE(Q) rc = cos ? launch_filter_exact_batch<M_COS, Q>(x, c, ep, k, o, d_stats) : launch_filter_exact_batch<M_L2, Q>(x, c, ep, k, o, d_stats)
-  COLTT_DISPATCH_QUANT(x->quant, COLTT_FE)
-#undef COLTT_FE
-  return rc;
-}
-
-// FiltExactPlan for the rows of exact_q (sorted in place)
-int plan_filter_exact_batch(Hnsw* x, const std::vector<HnswFilter*>& fl, std::vector<uint32_t>& exact_q, uint32_t k, const char* who, FiltExactPlan& out) {
-  const size_t qbytes = (((size_t)x->dim + 3) & ~(size_t)3) * 4, kbytes = (size_t)((k + 63) & ~63u) * 8;
-  uint32_t& qg = out.qg;
-  qg = FILT_QG;
-  while (qg > 1 && qg * (qbytes + kbytes) > 64 * 1024) qg--;
-  std::vector<FiltExactQ>& eq = out.eq;
-  std::vector<FiltTile>& tiles = out.tiles;
-  uint64_t& nlists = out.nlists;
-  eq.clear(); tiles.clear(); nlists = 0;
-  if (!exact_q.empty()) {
-    if (qg * (qbytes + kbytes) > 160 * 1024)
-      return fail(COLTT_E_UNSUPPORTED, "%s: dim %u / k %u need %zu B of LDS (> 160 KiB)", who, x->dim, k, qg * (qbytes + kbytes));
-    std::stable_sort(exact_q.begin(), exact_q.end(), [&](uint32_t a, uint32_t b) { return std::less<const HnswFilter*>()(fl[a], fl[b]); });
-    struct Run { size_t first, len; uint64_t nch, chunk; };
-    std::vector<Run> runs;
-    uint64_t groups = 0;
-    for (size_t a = 0; a < exact_q.size();) {
-      size_t b = a;
-      while (b < exact_q.size() && fl[exact_q[b]] == fl[exact_q[a]]) b++;
-      runs.push_back(Run{a, b - a, 0, 0});
-      groups += ceil_div(b - a, qg);
-      a = b;
-    }
-    for (Run& r : runs) r.nch = std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(4096, groups), ceil_div(fl[exact_q[r.first]]->allowed, 256)));
-    auto lists = [&] { uint64_t t = 0; for (const Run& r : runs) t += r.len * r.nch; return t; };
-    while (lists() * k * 8 > (256ull << 20)) {   // the chunk lists' workspace
-      bool any = false;
-      for (Run& r : runs) if (r.nch > 1) { r.nch = (r.nch + 1) / 2; any = true; }
-      if (!any) break;
-    }
-    for (Run& r : runs) {
-      const HnswFilter* f = fl[exact_q[r.first]];
-      const uint64_t A = f->allowed;
-      r.chunk = (((A + r.nch - 1) / r.nch) + 31) & ~31ull;
-      r.nch = (A + r.chunk - 1) / r.chunk;
-      for (size_t j = 0; j < r.len; j++) {
-        eq.push_back(FiltExactQ{exact_q[r.first + j], (uint32_t)nlists, (uint32_t)r.nch, 0u});
-        nlists += r.nch;
-      }
-      for (size_t g0 = 0; g0 < r.len; g0 += qg)
-        for (uint64_t ch = 0; ch < r.nch; ch++)
-          tiles.push_back(FiltTile{f->list.as<uint32_t>(), (uint32_t)(ch * r.chunk), (uint32_t)std::min<uint64_t>(A, (ch + 1) * r.chunk),
-                                   (uint32_t)(r.first + g0), (uint32_t)std::min<size_t>(qg, r.len - g0), (uint32_t)ch, 0u});
-    }
-    if (nlists > 0xffffffffull || tiles.size() > 0x7fffffffull) return fail(COLTT_E_UNSUPPORTED, "%s: too many exact-path chunk lists", who);
-  }
-  return COLTT_OK;
-}
-
-// One upload of every table of a call into w_fdesc — [walk descriptors w0 | w1][exact queries][tiles, 32-byte aligned] — then the answer's
-// buffers, the counts cleared.  blob is the caller's: the host copy outlives the transfer.  desc: the blob on the device (w0 at desc, w1 at desc + w0_bytes).
-int filter_upload(HCtx* c, const void* w0, size_t w0_bytes, const void* w1, size_t w1_bytes, FiltExactPlan& ep, size_t nq, uint32_t k,
-                  std::vector<uint8_t>& blob, uint8_t*& desc, FiltOut& o) {
-  const size_t o_eq = w0_bytes + w1_bytes;
-  const size_t o_t = (o_eq + ep.eq.size() * sizeof(FiltExactQ) + 31) & ~(size_t)31, o_end = o_t + ep.tiles.size() * sizeof(FiltTile);
-  blob.resize(o_end);
-  if (w0_bytes) std::memcpy(blob.data(), w0, w0_bytes);
-  if (w1_bytes) std::memcpy(blob.data() + w0_bytes, w1, w1_bytes);
-  if (!ep.eq.empty()) std::memcpy(blob.data() + o_eq, ep.eq.data(), ep.eq.size() * sizeof(FiltExactQ));
-  if (!ep.tiles.empty()) std::memcpy(blob.data() + o_t, ep.tiles.data(), ep.tiles.size() * sizeof(FiltTile));
-  COLTT_TRY(c->w_fdesc.reserve(o_end));
-  desc = c->w_fdesc.as<uint8_t>();
-  ep.d_eq = reinterpret_cast<const FiltExactQ*>(desc + o_eq);
-  ep.d_tiles = reinterpret_cast<const FiltTile*>(desc + o_t);
-  COLTT_HIP(hipMemcpyAsync(desc, blob.data(), o_end, hipMemcpyHostToDevice, c->stream));
-  COLTT_TRY(c->w_out_ids.reserve(nq * k * 8));
-  COLTT_TRY(c->w_out_sc.reserve(nq * k * 4));
-  COLTT_TRY(c->w_out_cnt.reserve(nq * 4));
-  o = FiltOut{c->w_out_ids.as<uint64_t>(), c->w_out_sc.as<float>(), c->w_out_cnt.as<uint32_t>()};
-  COLTT_HIP(hipMemsetAsync(o.oc, 0, nq * 4, c->stream));   // rows of empty filters stay at count 0
-  return COLTT_OK;
-}
-
-// The end of a call: the answer and (unless the caller has read them: have_stats) the six counters back to the host, the kernel time, the watchdog.
-int filter_finish(Hnsw* x, HCtx* c, const char* who, const FiltOut& o, size_t nq, uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
-                  const unsigned long long* d_stats, unsigned long long* h_stats, bool have_stats) {
-  COLTT_HIP(hipEventRecord(c->ev1, c->stream));
-  if (x->dense && x->dense_base) add_base_kernel<<<ceil_div(nq * k, 256), 256, 0, c->stream>>>(o.oi, nq * k, x->dense_base);
-  COLTT_HIP(hipMemcpyAsync(out_ids, o.oi, nq * k * 8, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(out_scores, o.os, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipMemcpyAsync(out_counts, o.oc, nq * 4, hipMemcpyDeviceToHost, c->stream));
-  if (!have_stats) COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 48, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipStreamSynchronize(c->stream));   // the lease, the host tables and the callers' filters outlive the kernels
-  if (!have_stats) std::memcpy(h_stats, c->h_out.p, 48);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-  x->last_ms.store(ms);
-  if (h_stats[4]) return fail(COLTT_E_DEVICE, "%s: traversal watchdog tripped (code %llu)", who, h_stats[4]);
-  return COLTT_OK;
-}
-
-// ---- coltt_hnsw_search_filtered: one filter for the whole call.
-template <int METRIC, int QUANT>
-int launch_search_filtered(Hnsw* x, HCtx* c, const SearchGeom& sg, const HnswFilter* f, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k,
-                           uint32_t* counter, uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
-  auto kern = sg.visg ? hnsw_search_filtered_kernel<METRIC, QUANT, true> : hnsw_search_filtered_kernel<METRIC, QUANT, false>;
-  if constexpr (QUANT != Q_F8) { if (x->r8) kern = sg.visg ? hnsw_search_filtered_kernel<METRIC, QUANT, true, true> : hnsw_search_filtered_kernel<METRIC, QUANT, false, true>; }
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
-  kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
-                                        k, sg.ef, sg.ef_pad, sg.hcap, counter, oi, os, oc, stats,
-                                        x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
-                                        x->w_vepoch.as<uint32_t>() + region_base, FilterView{f->bits.as<uint32_t>(), f->slots});
-  COLTT_HIP(hipGetLastError());
-  return COLTT_OK;
-}
-
-template <int METRIC, int QUANT>
-int launch_filter_exact(Hnsw* x, HCtx* c, const HnswFilter* f, uint32_t nq, uint32_t k, uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
-  // geometry: up to FILT_QG queries per wave while the wave's LDS (queries + one top-k each) stays within 64 KiB (two waves per SIMD);
-  // enough (group, chunk) waves to fill the device (4096), chunks of >= 256 slots
-  const size_t qbytes = (((size_t)x->dim + 3) & ~(size_t)3) * 4, kbytes = (size_t)((k + 63) & ~63u) * 8;
-  uint32_t qg = FILT_QG;
-  while (qg > 1 && qg * (qbytes + kbytes) > 64 * 1024) qg--;
-  const size_t lds = qg * (qbytes + kbytes);
-  if (lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "hnsw_search_filtered: dim %u / k %u need %zu B of LDS (> 160 KiB)", x->dim, k, lds);
-  const uint32_t groups = ceil_div(nq, qg);
-  const uint64_t A = f->allowed;
-  uint64_t nchunks = std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(4096, groups), ceil_div(A, 256)));
-  while (nchunks > 1 && (uint64_t)nq * nchunks * k * 8 > (256ull << 20)) nchunks = (nchunks + 1) / 2;   // the chunk lists' workspace
-  uint64_t chunk = (A + nchunks - 1) / nchunks;
-  chunk = (chunk + 31) & ~31ull;
-  nchunks = (A + chunk - 1) / chunk;
-  COLTT_TRY(c->w_keys.reserve((size_t)nq * nchunks * k * 8));
-  COLTT_TRY(c->w_scnt.reserve((size_t)nq * nchunks * 4));
-  GraphView gv = x->view();
-  auto scan = hnsw_filter_scan_kernel<METRIC, QUANT, false>;
-  if constexpr (QUANT != Q_F8) { if (x->r8) scan = hnsw_filter_scan_kernel<METRIC, QUANT, true>; }
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  scan<<<dim3((uint32_t)nchunks, groups), 64, lds, c->stream>>>(gv, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq, qg, f->list.as<uint32_t>(), (uint32_t)A,
-                                                                (uint32_t)chunk, k, (k + 63) & ~63u, c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), stats);
-  COLTT_HIP(hipGetLastError());
-  const size_t lds2 = kbytes;
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(hnsw_filter_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-  hnsw_filter_select_kernel<<<nq, 64, lds2, c->stream>>>(c->w_keys.as<unsigned long long>(), c->w_scnt.as<uint32_t>(), (uint32_t)nchunks, k, gv.ids, oi, os, oc);
-  COLTT_HIP(hipGetLastError());
-  return COLTT_OK;
-}
-
-int filter_search_common(Hnsw* x, HCtx* c, const HnswFilter* f, const float* queries, size_t nq, uint32_t k, uint32_t ef_override, int mode,
-                         uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_filter_stats* st) {
-  const char* const who = "hnsw_search_filtered";
-  coltt_hnsw_filter_stats local{};
-  if (!st) st = &local;
-  uint32_t ef;
-  COLTT_TRY(filter_args(x, who, nq, k, ef_override, mode, st, ef));
-  if (!ef) return COLTT_OK;
-  uint32_t ef_walk = ef;
-  const int path = filter_path(f->allowed, x->live, ef, mode, ef_walk);
-  st->path = path; st->ef_walk = path == COLTT_FILTER_WALK ? ef_walk : 0;
-  if (x->entry < 0 || f->allowed == 0) {   // empty index or empty filter: counts 0, not an error
-    std::memset(out_counts, 0, nq * 4);
-    return COLTT_OK;
-  }
-  COLTT_TRY(c->w_out_ids.reserve(nq * k * 8));
-  COLTT_TRY(c->w_out_sc.reserve(nq * k * 4));
-  COLTT_TRY(c->w_out_cnt.reserve(nq * 4));
-  const FiltOut o{c->w_out_ids.as<uint64_t>(), c->w_out_sc.as<float>(), c->w_out_cnt.as<uint32_t>()};
-  SearchGeom sg{};
-  uint32_t grid = 0;
-  RegionLease lease;
-  if (path == COLTT_FILTER_WALK) {
-    if (wants_visg(ef_walk)) COLTT_TRY(ensure_visg(x));
-    sg = search_geom(x, ef_walk, false, true, k);   // the one-wave walk (hnsw_dev.hpp: search_level) over the LDS hash or the HBM byte map
-    if (sg.lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "%s: dim/ef/k need %zu B of LDS (> 160 KiB)", who, sg.lds);
-    grid = std::min<uint32_t>((uint32_t)nq, resident_waves(sg, x->quant));
-    if (sg.visg) { acquire_regions(x, grid, lease); grid = lease.count; }
-  }
-  COLTT_TRY(c->w_qraw.reserve(nq * x->dim * 4));
-  COLTT_HIP(hipMemcpyAsync(c->w_qraw.p, queries, nq * x->dim * 4, hipMemcpyHostToDevice, c->stream));
-  COLTT_TRY(c->w_misc.reserve(256));
-  COLTT_TRY(c->h_out.reserve(256));
-  uint8_t* misc = c->w_misc.as<uint8_t>();
-  uint32_t* counter = reinterpret_cast<uint32_t*>(misc);
-  unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(misc + 16);
-  COLTT_TRY(prep_queries_any(x, c, c->w_qraw.as<float>(), nq, reinterpret_cast<uint32_t*>(misc)));   // Normalize / Lower the queries as Search does; clears the counters
-  COLTT_HIP(hipEventRecord(c->ev0, c->stream));
-  int rc = COLTT_OK;
-#define COLTT_FS(Q) rc = path == COLTT_FILTER_WALK \
-    ? (x->metric == COLTT_COSINE ? launch_search_filtered<M_COS, Q>(x, c, sg, f, grid, lease.base, (uint32_t)nq, k, counter, o.oi, o.os, o.oc, d_stats) \
-                                 : launch_search_filtered<M_L2, Q>(x, c, sg, f, grid, lease.base, (uint32_t)nq, k, counter, o.oi, o.os, o.oc, d_stats)) \
-    : (x->metric == COLTT_COSINE ? launch_filter_exact<M_COS, Q>(x, c, f, (uint32_t)nq, k, o.oi, o.os, o.oc, d_stats) \
-                                 : launch_filter_exact<M_L2, Q>(x, c, f, (uint32_t)nq, k, o.oi, o.os, o.oc, d_stats))
-  COLTT_DISPATCH_QUANT(x->quant, COLTT_FS)
-#undef COLTT_FS
-  COLTT_TRY(rc);
-  unsigned long long h_stats[6];
-  COLTT_TRY(filter_finish(x, c, who, o, nq, k, out_ids, out_scores, out_counts, d_stats, h_stats, false));
-  st->n_dist = h_stats[0]; st->n_exp = h_stats[1]; st->n_hops = h_stats[2]; st->n_visit_resets = h_stats[3]; st->n_exact_rows = h_stats[5];
-  return COLTT_OK;
-}
-
-// ---- coltt_hnsw_search_filtered_batch: a filter per query.  Row i is the single-filter call on query i alone: its path from its own filter's
-// allowed count (filter_path), its walk at the geometry search_geom gives its ef_walk, its exact scan chunked by launch_filter_exact's rule (the
-// answer is a pure top-k, so the chunking cannot change it).  One call launches at most two walks (LDS hash, HBM byte map), one scan, one select.
-int filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,
-                        int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, int32_t* out_paths, coltt_hnsw_filter_stats* st) {
-  const char* const who = "hnsw_search_filtered_batch";
-  coltt_hnsw_filter_stats local{};
-  if (!st) st = &local;
-  uint32_t ef;
-  COLTT_TRY(filter_args(x, who, nq, k, ef_override, mode, st, ef));
-  if (!ef) return COLTT_OK;
-  FiltRoute rt;
-  filter_route(x, fl, nq, ef, mode, out_paths, out_counts, st, rt);
-  if (rt.none()) return COLTT_OK;
-  // the walks: each query's geometry is search_geom(x, ef_walk, false, true, k), the one-wave walk (hnsw_dev.hpp: search_level) over the LDS hash
-  // or the HBM byte map; split by visited set
-  for (uint32_t i : rt.walk_q)
-    if (wants_visg(rt.efw[i])) { COLTT_TRY(ensure_visg(x)); break; }
-  std::map<uint32_t, SearchGeom> geoms;
-  std::vector<FiltQuery> wq[2];
-  SearchGeom wmax[2]{};
-  for (uint32_t i : rt.walk_q) {
-    auto it = geoms.find(rt.efw[i]);
-    if (it == geoms.end()) it = geoms.emplace(rt.efw[i], search_geom(x, rt.efw[i], false, true, k)).first;
-    const SearchGeom& sg = it->second;
-    if (sg.lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "%s: dim/ef/k need %zu B of LDS (> 160 KiB)", who, sg.lds);
-    const int v = sg.visg ? 1 : 0;
-    wq[v].push_back(FiltQuery{fl[i]->bits.as<uint32_t>(), fl[i]->slots, sg.ef, sg.ef_pad, sg.hcap, i, 0u});
-    if (wq[v].size() == 1 || sg.lds > wmax[v].lds) wmax[v] = sg;   // the launch's LDS: its largest query's
-  }
-  FiltExactPlan ep;
-  COLTT_TRY(plan_filter_exact_batch(x, fl, rt.exact_q, k, who, ep));
-  // the tables: [walks over the LDS hash][walks over the byte map][exact queries][tiles]
-  std::vector<uint8_t> blob;
-  uint8_t* d_desc;
-  FiltOut o;
-  const size_t w0_bytes = wq[0].size() * sizeof(FiltQuery);
-  COLTT_TRY(filter_upload(c, wq[0].data(), w0_bytes, wq[1].data(), wq[1].size() * sizeof(FiltQuery), ep, nq, k, blob, d_desc, o));
-  uint32_t grid[2] = {0, 0};
-  RegionLease lease;
-  for (int v = 0; v < 2; v++) if (!wq[v].empty()) grid[v] = std::min<uint32_t>((uint32_t)wq[v].size(), resident_waves(wmax[v], x->quant));
-  if (grid[1]) { acquire_regions(x, grid[1], lease); grid[1] = lease.count; }
-  COLTT_TRY(c->w_qraw.reserve(nq * x->dim * 4));
-  COLTT_HIP(hipMemcpyAsync(c->w_qraw.p, queries, nq * x->dim * 4, hipMemcpyHostToDevice, c->stream));
-  COLTT_TRY(c->w_misc.reserve(256));
-  COLTT_TRY(c->h_out.reserve(256));
-  uint8_t* misc = c->w_misc.as<uint8_t>();
-  uint32_t* counters = reinterpret_cast<uint32_t*>(misc);   // [0]: the LDS-hash walk's work counter, [1]: the byte-map walk's
-  unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(misc + 16);
-  COLTT_TRY(prep_queries_any(x, c, c->w_qraw.as<float>(), nq, reinterpret_cast<uint32_t*>(misc)));   // Normalize / Lower the queries as Search does; clears the counters
-  COLTT_HIP(hipEventRecord(c->ev0, c->stream));
-  int rc = COLTT_OK;
-  const bool cos = x->metric == COLTT_COSINE;
-  for (int v = 0; v < 2 && rc == COLTT_OK; v++) {
-    if (!grid[v]) continue;
-    const FiltQuery* fq = reinterpret_cast<const FiltQuery*>(d_desc + (v ? w0_bytes : 0));
-    const uint32_t nw = (uint32_t)wq[v].size();
-#define COLTT_FW(Q) rc = cos ? launch_search_filtered_batch<M_COS, Q>(x, c, v == 1, wmax[v].lds, grid[v], lease.base, nw, k, fq, counters + v, o.oi, o.os, o.oc, d_stats) \
-                         : launch_search_filtered_batch<M_L2, Q>(x, c, v == 1, wmax[v].lds, grid[v], lease.base, nw, k, fq, counters + v, o.oi, o.os, o.oc, d_stats)
-    COLTT_DISPATCH_QUANT(x->quant, COLTT_FW)
-#undef COLTT_FW
-  }
-  COLTT_TRY(rc);
-  COLTT_TRY(run_filter_exact(x, c, ep, k, o, d_stats));
-  unsigned long long h_stats[6];
-  COLTT_TRY(filter_finish(x, c, who, o, nq, k, out_ids, out_scores, out_counts, d_stats, h_stats, false));
-  st->n_dist = h_stats[0]; st->n_exp = h_stats[1]; st->n_hops = h_stats[2]; st->n_visit_resets = h_stats[3]; st->n_exact_rows = h_stats[5];
-  return COLTT_OK;
-}
-
-// coltt_hnsw_pq_search_filtered (the entry point has checked that the index carries codes): the path is filter_path's, word for word; EXACT is filter_search_common's, WALK the walk over the quantiser's codes
-// at ef_walk (pq_search_once: the same grouping of queries, region lease, neighbourhood blocks and retry over the byte map) with the allowed set.
-int pq_filter_search_common(Hnsw* x, HCtx* c, const HnswFilter* f, const float* queries, size_t nq, uint32_t k, uint32_t ef_override, uint32_t rerank, int mode,
-                            uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_filter_stats* st) {
-  coltt_hnsw_filter_stats local{};
-  if (!st) st = &local;
-  uint32_t ef;
-  COLTT_TRY(filter_args(x, "hnsw_pq_search_filtered", nq, k, ef_override, mode, st, ef));
-  if (!ef) return COLTT_OK;
-  uint32_t ef_walk = ef;
-  const int path = filter_path(f->allowed, x->live, ef, mode, ef_walk);
-  if (path == COLTT_FILTER_EXACT) return filter_search_common(x, c, f, queries, nq, k, ef_override, COLTT_FILTER_EXACT, out_ids, out_scores, out_counts, st);
-  st->path = COLTT_FILTER_WALK; st->ef_walk = ef_walk;
-  if (x->entry < 0 || f->allowed == 0) {   // empty index or empty filter: counts 0, not an error
-    std::memset(out_counts, 0, nq * 4);
-    return COLTT_OK;
-  }
-  coltt_hnsw_stats ws{};
-  uint64_t n_exact = 0;
-  const FilterView fv{f->bits.as<uint32_t>(), f->slots};
-  COLTT_TRY(pq_search_filtered_walk(x, c, fv, queries, nq, k, ef_walk, rerank, out_ids, out_scores, out_counts, &ws, &n_exact));
-  st->n_dist = ws.n_dist; st->n_exp = ws.n_exp; st->n_hops = ws.n_hops; st->n_visit_resets = 0; st->n_exact_rows = n_exact;
-  return COLTT_OK;
-}
-
-// ---- coltt_hnsw_pq_search_filtered_batch: a filter per query over the walk on the quantiser's codes.  Row i is coltt_hnsw_pq_search_filtered on query i
-// alone: its path from its own filter (filter_path), its walk at ef_walk with the geometry and the capacity of R the single call gives it (pq_walk_geom,
-// pq_filt_cap), EXACT rows through the row batch's exact scan.  The walking queries are compacted (their prepared vectors gathered side by side: the
-// tables, survivors and keys are addressed by position in the launch) and run as at most two walk launches per group of queries — LDS hash, byte map — each
-// followed by the re-rank over its survivors; the select kernel answers the batch row of each.  A query whose LDS-hash walk reports the reset code runs
-// once more over the byte map, as the single call re-runs itself, and is counted once.
-__global__ void pq_gather_queries_kernel(const float* __restrict__ q_eff, const float* __restrict__ qnorms, const PqFiltQuery* __restrict__ pd, uint32_t dim,
-                                         float* __restrict__ out_q, float* __restrict__ out_n) {
-  const uint32_t j = blockIdx.x, row = pd[j].row;
-  for (uint32_t e = threadIdx.x; e < dim; e += blockDim.x) out_q[(size_t)j * dim + e] = q_eff[(size_t)row * dim + e];
-  if (threadIdx.x == 0) out_n[j] = qnorms[row];
-}
-
-int pq_filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,
-                           uint32_t rerank, int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, int32_t* out_paths,
-                           coltt_hnsw_filter_stats* st) {
-  const char* const who = "hnsw_pq_search_filtered_batch";
-  coltt_hnsw_filter_stats local{};
-  if (!st) st = &local;
-  uint32_t ef;
-  COLTT_TRY(filter_args(x, who, nq, k, ef_override, mode, st, ef));
-  if (!ef) return COLTT_OK;
-  FiltRoute rt;
-  filter_route(x, fl, nq, ef, mode, out_paths, out_counts, st, rt);
-  if (rt.none()) return COLTT_OK;
-  const std::vector<uint32_t>& efw = rt.efw;
-  if (!rt.walk_q.empty() && x->pq_done != x->n)
-    return fail(COLTT_E_DEVICE, "%s: codes cover %llu of %llu slots", who, (unsigned long long)x->pq_done, (unsigned long long)x->n);
-  // the walks: each query's geometry is the single call's for its ef_walk; split by visited set.  A launch takes the LDS of its largest query, keeps
-  // as many traversals per CU as that one allows, and its survivors' rows are as long as its longest result set
-  struct Launch { std::vector<PqFiltQuery> q; size_t lds = 0; uint32_t ef_pad = 0, per_cu = 0; };
-  Launch wl[2];
-  auto add_walk = [&](Launch& l, const PqGeom& sg, uint32_t fcap, uint32_t i) {
-    l.q.push_back(PqFiltQuery{fl[i]->bits.as<uint32_t>(), fl[i]->slots, sg.ef, sg.ef_pad, sg.vis_words, fcap, i, 0u, 0u});
-    if (l.q.size() == 1 || sg.lds > l.lds) { l.lds = sg.lds; l.per_cu = sg.per_cu; }
-    l.ef_pad = std::max(l.ef_pad, sg.ef_pad);
-  };
-  {
-    std::map<uint32_t, PqGeom> geoms;
-    for (uint32_t i : rt.walk_q) {
-      const uint32_t fcap = pq_filt_cap(efw[i], k, rerank);
-      auto it = geoms.find(efw[i]);
-      if (it == geoms.end()) {
-        PqGeom sg;
-        COLTT_TRY(pq_walk_geom(x, efw[i], false, fcap, sg));
-        it = geoms.emplace(efw[i], sg).first;
-      }
-      add_walk(wl[it->second.variant != 0 ? 1 : 0], it->second, fcap, i);
-    }
-  }
-  FiltExactPlan ep;
-  COLTT_TRY(plan_filter_exact_batch(x, fl, rt.exact_q, k, who, ep));
-  // the tables: [walks over the LDS hash][walks over the byte map][exact queries][tiles]
-  const size_t nw0 = wl[0].q.size(), nw1 = wl[1].q.size(), nw = nw0 + nw1;
-  std::vector<uint8_t> blob;
-  uint8_t* d_desc;
-  FiltOut o;
-  COLTT_TRY(filter_upload(c, wl[0].q.data(), nw0 * sizeof(PqFiltQuery), wl[1].q.data(), nw1 * sizeof(PqFiltQuery), ep, nq, k, blob, d_desc, o));
-  PqFiltQuery* d_pd = reinterpret_cast<PqFiltQuery*>(d_desc);
-  RegionLease lease;
-  bool nbr = false, nbr_known = false;
-  auto byte_map_ready = [&](uint32_t want) -> int {   // one lease and one look at the neighbourhood blocks per call
-    if (!lease.count) acquire_regions(x, want, lease);
-    if (!nbr_known) { COLTT_TRY(ensure_pq_nbr(x, c->stream, &nbr)); nbr_known = true; }
-    return COLTT_OK;
-  };
-  if (nw1) COLTT_TRY(byte_map_ready((uint32_t)std::min<size_t>(nw1, (size_t)256 * wl[1].per_cu)));
-  // the queries: all of them prepared as Search prepares them, the walking ones' then gathered into [nw][dim] | [nw] behind the raw batch
-  const size_t dim = x->dim;
-  COLTT_TRY(c->w_qraw.reserve(nq * dim * 4 + nw * dim * 4 + nw * 4));
-  COLTT_HIP(hipMemcpyAsync(c->w_qraw.p, queries, nq * dim * 4, hipMemcpyHostToDevice, c->stream));
-  COLTT_TRY(c->w_misc.reserve(256));
-  COLTT_TRY(c->h_out.reserve(256));
-  uint8_t* misc = c->w_misc.as<uint8_t>();
-  uint32_t* counter = reinterpret_cast<uint32_t*>(misc);
-  unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(misc + 16);
-  COLTT_TRY(prep_queries_any(x, c, c->w_qraw.as<float>(), nq, reinterpret_cast<uint32_t*>(misc)));   // as the single call; clears the counters
-  float* cq = c->w_qraw.as<float>() + nq * dim; float* cn = cq + nw * dim;
-  COLTT_HIP(hipEventRecord(c->ev0, c->stream));
-  const bool cos = x->metric == COLTT_COSINE;
-  const uint32_t lsh = pq_lut_shift(x);
-  const size_t lut_q = ((size_t)x->pq_row << lsh) * 2;
-  bool first_launch = true;
-  // the n walks whose descriptors are pd[0..n) (position j of the compacted queries = pd[j]): groups of queries under the workspaces' 256 MiB, as pq_search_once
-  auto run_walks = [&](const Launch& l, int variant, const PqFiltQuery* pd, size_t j0, size_t n) -> int {
-    pq_gather_queries_kernel<<<(uint32_t)n, 64, 0, c->stream>>>(c->w_qeff.as<float>(), c->w_qn.as<float>(), pd, (uint32_t)dim, cq + j0 * dim, cn + j0);
-    COLTT_HIP(hipGetLastError());
-    PqGeom sg{};
-    sg.variant = variant; sg.lds = l.lds; sg.ef_pad = l.ef_pad; sg.per_cu = l.per_cu;
-    uint32_t grid = (uint32_t)std::min<size_t>(n, (size_t)256 * l.per_cu);
-    if (variant != 0) grid = std::min(grid, lease.count);
-    const size_t group = std::max<size_t>(1, std::min<size_t>({n, (256ull << 20) / lut_q, (256ull << 20) / ((size_t)l.ef_pad * 12), (size_t)32768}));
-    COLTT_TRY(c->w_pack.reserve(group * lut_q + group * 4));
-    COLTT_TRY(c->w_surv.reserve(group * l.ef_pad * 4)); COLTT_TRY(c->w_scnt.reserve(group * 4)); COLTT_TRY(c->w_keys.reserve(group * l.ef_pad * 8));
-    for (size_t g0 = 0; g0 < n; g0 += group) {
-      const size_t gn = std::min(group, n - g0);
-      COLTT_TRY(pq_lut16_batch(c->stream, x->pq_cb.as<float>(), x->pq_shape, cq + (j0 + g0) * dim, gn, x->pq_row, lsh,
-                               reinterpret_cast<uint32_t*>(c->w_pack.as<uint8_t>() + group * lut_q), c->w_pack.as<unsigned short>()));
-      if (!first_launch) COLTT_HIP(hipMemsetAsync(counter, 0, 4, c->stream));
-      first_launch = false;
-      COLTT_TRY(launch_pq_walk(x, c, sg, nbr, (uint32_t)std::min<size_t>(grid, gn), lease.base, c->w_pack.as<unsigned short>(), (uint32_t)gn, k, rerank, counter,
-                               c->w_surv.as<uint32_t>(), c->w_scnt.as<uint32_t>(), d_stats, nullptr, 0u, pd + g0));
-      int rc;
-#define COLTT_LP_ARGS x, c, sg, 0u, (uint32_t)gn, k, c->w_surv.as<uint32_t>(), c->w_scnt.as<uint32_t>(), c->w_keys.as<unsigned long long>(), o.oi, o.os, o.oc, pd + g0, cq + (j0 + g0) * dim, cn + j0 + g0
-#define COLTT_LP(Q) rc = cos ? launch_pq_rerank<M_COS, Q>(COLTT_LP_ARGS) : launch_pq_rerank<M_L2, Q>(COLTT_LP_ARGS)
-      if (x->quant == COLTT_Q_NONE) { COLTT_LP(Q_NONE); } else { COLTT_LP(Q_F16); }
-#undef COLTT_LP
-#undef COLTT_LP_ARGS
-      COLTT_TRY(rc);
-    }
-    return COLTT_OK;
-  };
-  if (nw0) COLTT_TRY(run_walks(wl[0], 0, d_pd, 0, nw0));
-  if (nw1) COLTT_TRY(run_walks(wl[1], 2, d_pd + nw0, nw0, nw1));
-  COLTT_TRY(run_filter_exact(x, c, ep, k, o, d_stats));
-  unsigned long long h_stats[6];
-  COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 48, hipMemcpyDeviceToHost, c->stream));
-  COLTT_HIP(hipStreamSynchronize(c->stream));
-  std::memcpy(h_stats, c->h_out.p, 48);
-  if (nw0 && (h_stats[4] & 8ull) && !(h_stats[4] & ~8ull)) {   // some LDS-hash walks gave up (they added nothing to the sums): those queries over the byte map
-    std::vector<PqFiltQuery> back(nw0);
-    COLTT_HIP(hipMemcpy(back.data(), d_pd, nw0 * sizeof(PqFiltQuery), hipMemcpyDeviceToHost));
-    Launch rl;
-    std::map<uint32_t, PqGeom> geoms;
-    for (const PqFiltQuery& q : back) {
-      if (!(q.err & 8u)) continue;
-      auto it = geoms.find(q.ef);
-      if (it == geoms.end()) {
-        PqGeom sg;
-        COLTT_TRY(pq_walk_geom(x, q.ef, true, q.fcap, sg));
-        it = geoms.emplace(q.ef, sg).first;
-      }
-      add_walk(rl, it->second, q.fcap, q.row);
-    }
-    const size_t nr = rl.q.size();   // <= nw0: their descriptors and gathered queries take the places of the LDS-hash launch's
-    COLTT_TRY(byte_map_ready((uint32_t)std::min<size_t>(nr, (size_t)256 * rl.per_cu)));
-    COLTT_HIP(hipMemcpyAsync(d_pd, rl.q.data(), nr * sizeof(PqFiltQuery), hipMemcpyHostToDevice, c->stream));
-    COLTT_HIP(hipMemsetAsync(d_stats + 4, 0, 8, c->stream));
-    COLTT_TRY(run_walks(rl, 2, d_pd, 0, nr));
-    COLTT_HIP(hipMemcpyAsync(c->h_out.p, d_stats, 48, hipMemcpyDeviceToHost, c->stream));
-    COLTT_HIP(hipStreamSynchronize(c->stream));
-    std::memcpy(h_stats, c->h_out.p, 48);
-  }
-  COLTT_TRY(filter_finish(x, c, who, o, nq, k, out_ids, out_scores, out_counts, d_stats, h_stats, true));
-  // [3]: the members of R the walks handed to the re-rank, [5]: the rows the exact scan read
-  st->n_dist = h_stats[0]; st->n_exp = h_stats[1]; st->n_hops = h_stats[2]; st->n_visit_resets = 0; st->n_exact_rows = h_stats[3] + h_stats[5];
-  return COLTT_OK;
-}
 
 // coltt_hnsw_filter_eval / _eval_batch (definitions: include/coltt_gpu.h, "Filter expressions"; kernels: filter_expr.hpp).  n_out programmes
 // over one leaf table under one index state: one upload (leaf table, programme offsets, programmes), the evaluate launch, the counts back
@@ -3837,102 +3033,6 @@ int coltt_hnsw_filter_ids(coltt_handle_t fh, uint64_t* out_ids, uint64_t cap, ui
   COLTT_HIP(hipMemcpyAsync(out_ids, c->w_out_ids.p, m * 8, hipMemcpyDeviceToHost, c->stream));
   COLTT_HIP(hipStreamSynchronize(c->stream));
   return COLTT_OK;
-}
-
-int coltt_hnsw_search_filtered(coltt_handle_t h, coltt_handle_t fh, const float* queries, size_t nq, uint32_t k, uint32_t ef_override, int mode,
-                               uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_filter_stats* stats) {
-  auto x = lookup<Hnsw>(h);
-  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_search_filtered: unknown index handle");
-  auto f = lookup<HnswFilter>(fh);
-  if (!f) return fail(COLTT_E_NOT_FOUND, "hnsw_search_filtered: unknown filter handle");
-  if (nq && (!queries || !out_ids || !out_scores || !out_counts)) return fail(COLTT_E_INVALID, "hnsw_search_filtered: NULL buffer");
-  if (f->index != h) return fail(COLTT_E_INVALID, "hnsw_search_filtered: the filter was built for another index");
-  ReadLock g(x->rw);
-  if (f->gen != x->gen) return fail(COLTT_E_INVALID, "hnsw_search_filtered: the filter is stale (the index was loaded since it was built)");
-  COLTT_DEVICE(x->device);
-  CtxLease<HCtx> ctx(x->pool);
-  if (!ctx.c) return COLTT_E_DEVICE;
-  return filter_search_common(x.get(), ctx.c, f.get(), queries, nq, k, ef_override, mode, out_ids, out_scores, out_counts, stats);
-}
-
-int coltt_hnsw_pq_search_filtered(coltt_handle_t h, coltt_handle_t fh, const float* queries, size_t nq, uint32_t k, uint32_t ef_override, uint32_t rerank, int mode,
-                                  uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_filter_stats* stats) {
-  auto x = lookup<Hnsw>(h);
-  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_pq_search_filtered: unknown index handle");
-  {   // no codes attached: checked first, for every mode
-    ReadLock g0(x->rw);
-    if (!x->pq_on) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered: the index carries no product-quantiser codes (coltt_hnsw_pq_attach)");
-  }
-  auto f = lookup<HnswFilter>(fh);   // held until the call returns: a concurrent destroy only unregisters it
-  if (!f) return fail(COLTT_E_NOT_FOUND, "hnsw_pq_search_filtered: unknown filter handle");
-  if (nq && (!queries || !out_ids || !out_scores || !out_counts)) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered: NULL buffer");
-  if (f->index != h) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered: the filter was built for another index");
-  ReadLock g(x->rw);
-  if (f->gen != x->gen) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered: the filter is stale (the index was loaded since it was built)");
-  COLTT_DEVICE(x->device);
-  CtxLease<HCtx> ctx(x->pool);
-  if (!ctx.c) return COLTT_E_DEVICE;
-  return pq_filter_search_common(x.get(), ctx.c, f.get(), queries, nq, k, ef_override, rerank, mode, out_ids, out_scores, out_counts, stats);
-}
-
-int coltt_hnsw_search_filtered_batch(coltt_handle_t h, const coltt_handle_t* filters, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,
-                                     int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, int32_t* out_paths,
-                                     coltt_hnsw_filter_stats* stats) {
-  auto x = lookup<Hnsw>(h);
-  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_search_filtered_batch: unknown index handle");
-  if (nq && !filters) return fail(COLTT_E_INVALID, "hnsw_search_filtered_batch: NULL filters");
-  if (nq && (!queries || !out_ids || !out_scores || !out_counts)) return fail(COLTT_E_INVALID, "hnsw_search_filtered_batch: NULL buffer");
-  ReadLock g(x->rw);
-  // every handle is checked before anything is launched; each distinct filter is held until the call returns (a concurrent destroy
-  // only unregisters it)
-  std::unordered_map<coltt_handle_t, std::shared_ptr<HnswFilter>> held;
-  std::vector<HnswFilter*> fl(nq);
-  for (size_t i = 0; i < nq; i++) {
-    auto it = held.find(filters[i]);
-    if (it == held.end()) {
-      auto f = lookup<HnswFilter>(filters[i]);
-      if (!f) return fail(COLTT_E_NOT_FOUND, "hnsw_search_filtered_batch: unknown filter handle at position %zu", i);
-      if (f->index != h) return fail(COLTT_E_INVALID, "hnsw_search_filtered_batch: the filter at position %zu was built for another index", i);
-      if (f->gen != x->gen) return fail(COLTT_E_INVALID, "hnsw_search_filtered_batch: the filter at position %zu is stale (the index was loaded since it was built)", i);
-      it = held.emplace(filters[i], std::move(f)).first;
-    }
-    fl[i] = it->second.get();
-  }
-  COLTT_DEVICE(x->device);
-  CtxLease<HCtx> ctx(x->pool);
-  if (!ctx.c) return COLTT_E_DEVICE;
-  return filter_batch_common(x.get(), ctx.c, fl, queries, nq, k, ef_override, mode, out_ids, out_scores, out_counts, out_paths, stats);
-}
-
-int coltt_hnsw_pq_search_filtered_batch(coltt_handle_t h, const coltt_handle_t* filters, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,
-                                        uint32_t rerank, int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, int32_t* out_paths,
-                                        coltt_hnsw_filter_stats* stats) {
-  auto x = lookup<Hnsw>(h);
-  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_pq_search_filtered_batch: unknown index handle");
-  ReadLock g(x->rw);
-  // no codes attached: checked first, for every mode
-  if (!x->pq_on) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: the index carries no product-quantiser codes (coltt_hnsw_pq_attach)");
-  if (nq && !filters) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: NULL filters");
-  if (nq && (!queries || !out_ids || !out_scores || !out_counts)) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: NULL buffer");
-  // every handle is checked before anything is launched; each distinct filter is held until the call returns (a concurrent destroy
-  // only unregisters it)
-  std::unordered_map<coltt_handle_t, std::shared_ptr<HnswFilter>> held;
-  std::vector<HnswFilter*> fl(nq);
-  for (size_t i = 0; i < nq; i++) {
-    auto it = held.find(filters[i]);
-    if (it == held.end()) {
-      auto f = lookup<HnswFilter>(filters[i]);
-      if (!f) return fail(COLTT_E_NOT_FOUND, "hnsw_pq_search_filtered_batch: unknown filter handle at position %zu", i);
-      if (f->index != h) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: the filter at position %zu was built for another index", i);
-      if (f->gen != x->gen) return fail(COLTT_E_INVALID, "hnsw_pq_search_filtered_batch: the filter at position %zu is stale (the index was loaded since it was built)", i);
-      it = held.emplace(filters[i], std::move(f)).first;
-    }
-    fl[i] = it->second.get();
-  }
-  COLTT_DEVICE(x->device);
-  CtxLease<HCtx> ctx(x->pool);
-  if (!ctx.c) return COLTT_E_DEVICE;
-  return pq_filter_batch_common(x.get(), ctx.c, fl, queries, nq, k, ef_override, rerank, mode, out_ids, out_scores, out_counts, out_paths, stats);
 }
 
 }  // extern "C"

@@ -217,7 +217,7 @@ struct FiltSet { unsigned long long* r; uint32_t len, cap; FilterView f; };
 // LDS geometry search_geom gives that ef (ef_pad, hcap), and the batch row it reads its query from and writes its answer to.
 struct FiltQuery { const uint32_t* bits; uint32_t slots, ef, ef_pad, hcap, row, pad_; };
 // coltt_hnsw_pq_search_filtered_batch, WALK: the same for the walk over the quantiser's codes — the geometry is pq_geom's for that ef_walk and the
-// capacity fcap of the query's allowed set R (hnsw.hip); vis_words: the LDS hash's words, 0 over the byte map.  The walk addresses its table, survivors
+// capacity fcap of the query's allowed set R (hnsw_index.hpp: pq_filt_cap); vis_words: the LDS hash's words, 0 over the byte map.  The walk addresses its table, survivors
 // and count by its position in the launch; `row` is the batch row the select kernel answers.  err: written by the walk when it is not 0 (8: the LDS
 // hash would have needed its reset path — the host runs that query again over the byte map).
 struct PqFiltQuery { const uint32_t* bits; uint32_t slots, ef, ef_pad, vis_words, fcap, row, err, pad_; };

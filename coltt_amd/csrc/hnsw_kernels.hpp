@@ -641,33 +641,7 @@ __global__ __launch_bounds__(64) void hnsw_pq_rerank_kernel(GraphView g, const f
   const float d = eval_pair<METRIC, QUANT, PROF_SEARCH_HBM, R8>(g, w, slot, half);
   if (valid && half == 0) keys[(size_t)qi * ef_pad + i] = ((unsigned long long)__float_as_uint(d) << 32) | ((unsigned long long)slot << 1);
 }
-// step 2: the k smallest keys of a query — (exact score bits, slot) order — by k rounds of a wave minimum over the keys staged in LDS
-__global__ __launch_bounds__(64) void hnsw_pq_select_kernel(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ surv_cnt, uint32_t ef_pad, uint32_t k,
-                                                            const uint64_t* __restrict__ ids, uint64_t* __restrict__ out_ids, float* __restrict__ out_scores,
-                                                            uint32_t* __restrict__ out_counts, const PqFiltQuery* __restrict__ pd = nullptr) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  unsigned long long* const res = reinterpret_cast<unsigned long long*>(smem);
-  const uint32_t qi = blockIdx.x, r = surv_cnt[qi];
-  const uint32_t row = pd ? pd[qi].row : qi;   // pd (coltt_hnsw_pq_search_filtered_batch): query qi of the launch answers batch row pd[qi].row
-  const int lane_in = threadIdx.x;
-  for (uint32_t i = (uint32_t)lane_in; i < r; i += 64) res[i] = keys[(size_t)qi * ef_pad + i];
-  wave_sync();
-  const uint32_t n = r < k ? r : k;
-  for (uint32_t t = 0; t < n; t++) {
-    const int lane = opaque_lane(lane_in);
-    unsigned long long best = ~0ull; uint32_t bi = 0;
-    for (uint32_t i = (uint32_t)lane; i < r; i += 64) { const unsigned long long e = res[i]; if (e < best) { best = e; bi = i; } }
-    const unsigned long long km = wave_min_u64(best);
-    if (best == km && km != ~0ull) {   // keys are distinct (a slot appears once): exactly one lane
-      const uint32_t slot = (uint32_t)km >> 1;
-      out_ids[(size_t)row * k + t] = ids ? ids[slot] : (uint64_t)slot;
-      out_scores[(size_t)row * k + t] = __uint_as_float((uint32_t)(km >> 32));
-      res[bi] = ~0ull;
-    }
-    wave_sync();
-  }
-  if (lane_in == 0) out_counts[row] = n;
-}
+// step 2, hnsw_pq_select_kernel: hnsw.hip, beside its launcher (not a template: it stands in the one translation unit that launches it)
 
 // coltt_hnsw_search_filtered, EXACT: the k nearest live allowed vertices by (score bits, slot), over the filter's compacted slot list.
 // Step 1: one wave per (query group of <= FILT_QG queries, chunk of the list).  The group's queries sit in LDS; lane pair p scores slot
@@ -720,32 +694,7 @@ __global__ __launch_bounds__(64) void hnsw_filter_scan_kernel(GraphView g, const
   }
   if (lane_in == 0 && rows) atomicAdd(&stats[5], rows * nqg);
 }
-// step 2: one wave per query merges its chunks' lists (the same top-k in LDS) and writes the answer ascending
-__global__ __launch_bounds__(64) void hnsw_filter_select_kernel(const unsigned long long* __restrict__ part, const uint32_t* __restrict__ part_cnt,
-                                                                uint32_t nchunks, uint32_t k, const uint64_t* __restrict__ ids, uint64_t* __restrict__ out_ids,
-                                                                float* __restrict__ out_scores, uint32_t* __restrict__ out_counts) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  unsigned long long* const top = reinterpret_cast<unsigned long long*>(smem);
-  const size_t q = blockIdx.x;
-  const int lane_in = threadIdx.x;
-  uint32_t len = 0;
-  for (uint32_t c = 0; c < nchunks; c++) {
-    const uint32_t cnt = part_cnt[q * nchunks + c];
-    const unsigned long long* src = part + (q * nchunks + c) * k;
-    for (uint32_t b = 0; b < cnt; b += 64) {
-      const int lane = opaque_lane(lane_in);
-      const bool take = b + (uint32_t)lane < cnt;
-      sorted_offer(top, len, k, take, take ? src[b + lane] : ~0ull, lane, false);
-    }
-  }
-  for (uint32_t i = (uint32_t)lane_in; i < len; i += 64) {
-    const unsigned long long e = top[i];
-    const uint32_t slot = (uint32_t)e >> 1;
-    out_ids[q * k + i] = ids ? ids[slot] : (uint64_t)slot;
-    out_scores[q * k + i] = __uint_as_float((uint32_t)(e >> 32));
-  }
-  if (lane_in == 0) out_counts[q] = len;
-}
+// step 2, hnsw_filter_select_kernel: hnsw_filter.hip, beside its launcher (as hnsw_pq_select_kernel)
 
 // coltt_hnsw_search_filtered_batch, EXACT: the two steps above with a filter per query.  The host sorts the exact-path queries by filter
 // and cuts groups of <= qg queries that share one; FiltExactQ e = such a query: its batch row and its run of chunk lists in part.  A tile

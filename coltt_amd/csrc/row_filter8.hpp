@@ -3,7 +3,7 @@
 // (row_filter_rejects) and the epilogue are shared.  Plain C++ on purpose (no HIP header): tests/test_row_filter8_bound.py compiles this file with g++ and
 // calls the very code the kernel runs.
 //
-// The quantiser (rows8.hpp: rows_b_kernel; restated in the tests): s = fl(max|x_i| / 127), c_i = clamp(rint(fl(x_i / s)), -127, 127) (an integer, stored
+// The quantiser (rows8_ingest.hpp: rows_b_kernel; restated in the tests): s = fl(max|x_i| / 127), c_i = clamp(rint(fl(x_i / s)), -127, 127) (an integer, stored
 // signed), e >= ||x - s c||_2: the squared differences summed in f64, the root inflated by 1 + 2^-20 (the f64 roundings: (dim + 4) 2^-53) and rounded
 // towards +infinity to f32.  Nothing below depends on HOW c was chosen: whatever the codes are — clipped, tied, rounded the other way — e measures it.
 // A zero row, a row with a non-finite element and a row whose scale underflows to 0 get e = +infinity: no certificate.

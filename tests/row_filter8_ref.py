@@ -1,4 +1,4 @@
-"""The ingest quantiser of the 8-bit row-filter shadow (coltt_amd/csrc/rows8.hpp: rows_b_kernel), restated in numpy for the tests that check the
+"""The ingest quantiser of the 8-bit row-filter shadow (coltt_amd/csrc/rows8_ingest.hpp: rows_b_kernel), restated in numpy for the tests that check the
 bound (test_row_filter8_bound.py) and the device's arrays (test_gpu_row_filter8.py)."""
 import math
 
@@ -6,7 +6,7 @@ import numpy as np
 
 
 def quantise(x):
-    """rows8.hpp: rows_b_kernel — (s, codes, stored e) of one f32 row; a zero row, a row with a non-finite element and a scale that underflows
+    """rows8_ingest.hpp: rows_b_kernel — (s, codes, stored e) of one f32 row; a zero row, a row with a non-finite element and a scale that underflows
     to 0 get codes 0, s = 0 and e = +inf"""
     x = np.ascontiguousarray(x, np.float32)
     none = (np.zeros(x.size, np.int8), np.float32(0), np.float32(np.inf))

@@ -1,6 +1,6 @@
 """The margin of the level-0 row filter over the 8-BIT shadow is a theorem, not a tolerance (coltt_amd/csrc/row_filter8.hpp).
 
-The header is compiled with the host compiler — the very function the kernel runs — and the ingest quantiser (rows8.hpp: rows_b_kernel) is restated
+The header is compiled with the host compiler — the very function the kernel runs — and the ingest quantiser (rows8_ingest.hpp: rows_b_kernel) is restated
 here in numpy.  Against exact rational arithmetic (fractions.Fraction over the exact binary values of the f32 inputs):
 
     dot_exact_f32  <=  s G + E_exact  <=  U = fl(fl(s G) + E)            and            d_exact >= d_lo
