@@ -82,6 +82,8 @@ Policy read_policy_from_env() {
   v = num("COLTT_WAVES_PER_CU", set); p.waves_per_cu = set ? (int)std::max<long long>(1, std::min<long long>(12, v)) : 0;
   v = num("COLTT_ROWS_NT", set); p.rows_nt = set ? (v > 0 ? 1 : (v < 0 ? -1 : 0)) : -1;
   v = num("COLTT_ROW_FILTER", set); p.row_filter = set ? (v > 0 ? 1 : 0) : -1;
+  v = num("COLTT_ROW_FILTER_UPPER", set); p.row_filter_upper = set ? (v > 0 ? 1 : 0) : -1;
+  v = num("COLTT_DESCENT_NT", set); p.descent_nt = set ? (v > 0 ? 1 : 0) : -1;
   p.row_shadow = !off("COLTT_ROW_SHADOW");
   v = num("COLTT_ROW_FILTER_BITS", set); p.row_filter_bits = set && (v == 8 || v == 16) ? (int)v : 0;
   { const char* e = getenv("COLTT_ROW_FILTER_BITS"); if (e && !strcmp(e, "8i")) p.row_filter_bits = 80; }   // row_filter8i.hpp: ROW_FILTER_8I

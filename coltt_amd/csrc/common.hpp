@@ -116,6 +116,8 @@ struct Policy {
   int row_filter_bits = 0;     // COLTT_ROW_FILTER_BITS = 8 / 16 / 8i (= 80): the shadow a filtered launch reads (row_filter8.hpp / row_filter.hpp / row_filter8i.hpp: the 8-bit shadow against the quantised query); 0 = unset: 8i where the index keeps the 8-bit shadow, else 16.  The other kind serves where the asked one is missing
   int row_shadow_bits = 8;     // COLTT_ROW_SHADOW_BITS = 8 / 16 / both (read at create): which shadows a new f32 cosine index keeps — bit 3: the 8-bit codes (dim bytes per slot + 8 bytes per slot and per level-0 edge), bit 4: binary16 (dim * 2 bytes per slot)
   long long rows_nt_min_mb = 12288;  // COLTT_ROWS_NT_MIN_MB: ... row arrays of at least this many MiB (see exact.hpp: row_ld; measured crossover: profiles/r06ag_nt_rows_ab.md)
+  int row_filter_upper = -1;   // COLTT_ROW_FILTER_UPPER: the greedy descent of the 8-bit row-filter walks through the certified filter (hnsw_walk2.hpp: greedy_level8_filtered): -1 = the default (off: hnsw_search2.hip has the measurement), 0 never, 1 wherever the launch reads the 8-bit shadow
+  int descent_nt = -1;         // COLTT_DESCENT_NT (diagnostic): 1 = the entrypoint row and the descent's rows of the row-filter walks keep the launch's non-temporal hint, 0 = they are loaded cacheable; -1 = the default (cacheable)
   bool vis16 = true;           // COLTT_VIS16=0: the headline row-filter walk keeps the 32-bit LDS visited table (four traversals per CU) instead of the 16-bit one (vis16.hpp: seven)
   int vis16_bucket_bits = 0;   // COLTT_VIS16_BUCKET_BITS (test knob): log2 of the 16-bit table's bucket count, 1 .. 10, and no capacity rule; 0 = the library's 10
   int pq_waves = 0;            // COLTT_PQ_WAVES: resident traversals per CU of the product-quantised walk, 0 = the default cap

@@ -919,7 +919,7 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
   COLTT_TRY(rc);
   COLTT_HIP(hipEventRecord(c->ev1, c->stream));
   if (x->dense && x->dense_base) add_base_kernel<<<ceil_div(nq * k, 256), 256, 0, c->stream>>>(d_oi, nq * k, x->dense_base);
-  unsigned long long h_stats[18] = {0};   // [6], [7]: the row filter's counters; [16], [17]: the 16-bit visited set's maxima (hnsw_kernels.hpp: hnsw_search2_rowfilter_kernel; [8, 16) is the phase clock's)
+  unsigned long long h_stats[21] = {0};   // [18 .. 20]: the filtered descent's (shadow rows, rejected, f32 rows above level 0); [6], [7]: the row filter's counters; [16], [17]: the 16-bit visited set's maxima (hnsw_kernels.hpp: hnsw_search2_rowfilter_kernel; [8, 16) is the phase clock's)
   if (packed) COLTT_HIP(hipMemcpyAsync(c->h_out.p, c->w_pack.p, pack_bytes, hipMemcpyDeviceToHost, c->stream));
   else {
     if (!on_device) {
@@ -970,7 +970,8 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
     return search_common(x, c, queries, on_device, nq, k, ef_override, out_ids, out_scores, out_counts, stats, force | 3);
   if (h_stats[4]) return fail(COLTT_E_DEVICE, "hnsw_search: traversal watchdog tripped (code %llu)", h_stats[4]);
   if (stats) { stats->n_dist = h_stats[0]; stats->n_exp = h_stats[1]; stats->n_hops = h_stats[2]; stats->n_visit_resets = h_stats[3]; }
-  if (c->flt_launch && sg.w2 >= 0 && !mw) { x->flt_launches.fetch_add(1); x->flt_rejected.fetch_add(h_stats[6]); x->flt_f32_rows.fetch_add(h_stats[7]); x->flt_shadow_rows.fetch_add(h_stats[5]); }   // (a call re-run after err 8 returned above: only the launch that answered counts)
+  if (c->flt_launch && sg.w2 >= 0 && !mw) { x->flt_launches.fetch_add(1); x->flt_rejected.fetch_add(h_stats[6]); x->flt_f32_rows.fetch_add(h_stats[7]); x->flt_shadow_rows.fetch_add(h_stats[5]); }
+  if (c->flt_launch && c->upper_launch && sg.w2 >= 0 && !mw) { x->flt_up_launches.fetch_add(1); x->flt_up_shadow_rows.fetch_add(h_stats[18]); x->flt_up_rejected.fetch_add(h_stats[19]); x->flt_up_f32_rows.fetch_add(h_stats[20]); }   // (a call re-run after err 8 returned above: only the launch that answered counts)
   return COLTT_OK;
 }
 

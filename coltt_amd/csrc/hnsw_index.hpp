@@ -27,6 +27,7 @@ struct HCtx {
   DevBuf w_fdesc;                  // filtered batch: the walks' per-query descriptors, the exact path's queries and tiles
   PinnedBuf h_in, h_out;   // small calls: see PinnedBuf
   bool flt_launch = false;   // launch_search2 took the row-filter twin for the call in flight
+  bool upper_launch = false; // ... with its greedy descent through the certified filter (COLTT_ROW_FILTER_UPPER)
   bool v16_launch = false;   // ... and that twin walks over the 16-bit visited set (vis16.hpp)
   const void* occ_kern = nullptr; size_t occ_lds = 0; int occ_per_cu = 0;   // the runtime's occupancy answer for the last (kernel, LDS) asked about
   int init() {  // the caller has selected the index's device
@@ -74,6 +75,7 @@ struct Hnsw : Object {
   }
   bool has_shadow8() const { return shadow8 && rows_b.p && rows_m.p && adj0_m.p; }
   bool has_shadow16() const { return shadow && rows_h.p; }
+  std::atomic<uint64_t> flt_up_launches{0}, flt_up_shadow_rows{0}, flt_up_rejected{0}, flt_up_f32_rows{0};   // the same for the filtered descent (levels above 0): launches that ran it; shadow rows, rejected evaluations, f32 rows up there
   std::atomic<uint64_t> flt_launches{0}, flt_rejected{0}, flt_f32_rows{0}, flt_shadow_rows{0};   // filtered launches whose call completed; evaluations the filter rejected; f32 rows / shadow rows they read at level 0
   // the visited set of the last search launch (coltt_hnsw_visited_stats): 0 HBM byte map, 32 the LDS hash of 32-bit slots, 16 the 16-bit one (vis16.hpp); the
   // traversals that launch kept resident per CU, its grid and, if it ran on the 16-bit table, the fullest stash and the most vertices one of its traversals

@@ -248,6 +248,30 @@ void hnsw_search2_kernel(GraphView g, int32_t entry, int32_t entry_level,
 // VISMODE == VIS_LDS16 (the headline instance alone: walk variant 4, BITS == ROW_FILTER_8I): the LDS visited set at 16 bits per entry (vis16.hpp), which is what
 // lets seven traversals share a CU's LDS; the instance leaves the register allocator room for two waves per SIMD.  bloom_words then carries
 // (capacity limit << 8) | log2(buckets); stats[16] / stats[17]: the largest stash count / visited count of a traversal (atomic maxima).
+// upper (kernel argument, wave-uniform): how the prologue descends.  ROWF_UPPER_FILTER: the 8-bit kinds run the upper levels through the certified filter
+// (hnsw_walk2.hpp: greedy_level8_filtered; stats[18] / [19] / [20]: shadow rows / rejected evaluations / f32 rows above level 0, the entrypoint's own row
+// not among them).  ROWF_UPPER_CACHED: the entrypoint row and the descent's rows are loaded without the launch's non-temporal hint — they are what all the
+// queries of a launch share.  The level-0 loads keep the hint either way.
+enum { ROWF_UPPER_FILTER = 1u, ROWF_UPPER_CACHED = 2u };
+// entrypoint + upper levels of the row-filter kernel: DNT is the hint of THESE loads.  fev: the level-0 evaluator, for the query's digit planes.
+template <bool DNT, int BITS, class FEV>
+__device__ __forceinline__ void rowfilter_descent(const GraphView& g, WaveCtx& w, const FEV& fev, uint32_t& cur, float& curd, int entry_level, int lane, bool filter,
+                                                  uint32_t& up_sh, uint32_t& up_rej, uint32_t& up_f32) {
+  curd = Group8Eval<M_COS, Q_NONE, false, false, DNT>().one(g, w, cur, lane);   // hnsw.go:253
+  curd = __shfl(curd, 0, 64);
+  w.n_dist += 1;
+  if constexpr (BITS == 8 || BITS == ROW_FILTER_8I) {
+    if (filter) {
+      Group8FilterEval<M_COS, Q_NONE, true, DNT, BITS> uev;
+      uev.qd = fev.qd; uev.qt = fev.qt; uev.qe = fev.qe;
+      for (int l = entry_level; l > 0; l--) greedy_level8_filtered(g, w, cur, curd, l, lane, uev);  // :254-256
+      up_sh += uev.n_h16; up_rej += uev.n_rej; up_f32 += uev.n_f32;
+      return;
+    }
+  }
+  for (int l = entry_level; l > 0; l--) greedy_level8<M_COS, Q_NONE, false, DNT>(g, w, cur, curd, l, lane);  // :254-256
+}
+
 template <int PROFILE, int OPT, int VISMODE, bool NT, int BITS = 16>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VISMODE == VIS_LDS16 ? 2 : 1)))
 void hnsw_search2_rowfilter_kernel(GraphView g, int32_t entry, int32_t entry_level,
@@ -256,7 +280,7 @@ void hnsw_search2_rowfilter_kernel(GraphView g, int32_t entry, int32_t entry_lev
                                                                    uint32_t* __restrict__ counter, uint64_t* __restrict__ out_ids,
                                                                    float* __restrict__ out_scores, uint32_t* __restrict__ out_counts,
                                                                    unsigned long long* __restrict__ stats, uint8_t* __restrict__ visg,
-                                                                   size_t vis_stride, uint32_t* __restrict__ vis_epoch) {
+                                                                   size_t vis_stride, uint32_t* __restrict__ vis_epoch, uint32_t upper) {
   static_assert((OPT & W2_ADJN) != 0, "the filter takes the neighbours' norms from the adjacency rows");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x;
@@ -311,10 +335,11 @@ void hnsw_search2_rowfilter_kernel(GraphView g, int32_t entry, int32_t entry_lev
     // (two waves per SIMD: the entry row's line addresses are the same for every query, and hoisted out of this loop they are 24 registers the instance has to
     // spill and reload one by one in front of each line's load; re-derived per query they cost a dozen additions)
     if constexpr (VISMODE == VIS_LDS16) asm volatile("" : "+s"(cur));
-    float curd = Group8Eval<M_COS, Q_NONE, false, false, NT>().one(g, w, cur, lane);   // hnsw.go:253
-    curd = __shfl(curd, 0, 64);
-    w.n_dist += 1;
-    for (int l = entry_level; l > 0; l--) greedy_level8<M_COS, Q_NONE, false, NT>(g, w, cur, curd, l, lane);  // :254-256
+    float curd;
+    uint32_t up_sh = 0, up_rej = 0, up_f32 = 0;   // the descent's own filter counters (stats[18 .. 20])
+    // (both branches wave-uniform, decided by a kernel argument: one of the descents runs per launch)
+    if (NT && (upper & ROWF_UPPER_CACHED)) rowfilter_descent<false, BITS>(g, w, fev, cur, curd, entry_level, lane, (upper & ROWF_UPPER_FILTER) != 0, up_sh, up_rej, up_f32);
+    else rowfilter_descent<NT, BITS>(g, w, fev, cur, curd, entry_level, lane, (upper & ROWF_UPPER_FILTER) != 0, up_sh, up_rej, up_f32);
     COLTT_PT(w, 5)
     w.n_dist += 1;  // searchLevel re-evaluates the entrypoint distance (hnsw.go:346)
     uint32_t len;
@@ -335,6 +360,9 @@ void hnsw_search2_rowfilter_kernel(GraphView g, int32_t entry, int32_t entry_lev
       atomicAdd(&stats[6], (unsigned long long)fev.n_rej);
       atomicAdd(&stats[7], (unsigned long long)fev.n_f32);
       atomicAdd(&stats[5], (unsigned long long)fev.n_h16);
+      if constexpr (BITS == 8 || BITS == ROW_FILTER_8I) {
+        if (upper & ROWF_UPPER_FILTER) { atomicAdd(&stats[18], (unsigned long long)up_sh); atomicAdd(&stats[19], (unsigned long long)up_rej); atomicAdd(&stats[20], (unsigned long long)up_f32); }
+      }
       if constexpr (VISMODE == VIS_LDS16) { atomicMax(&stats[16], (unsigned long long)w.v16_stash); atomicMax(&stats[17], (unsigned long long)w.v16_count); }
 #ifdef COLTT_PHASE_TIMING
       COLTT_PT(w, 6)

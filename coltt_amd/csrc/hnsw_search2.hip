@@ -13,13 +13,23 @@ using namespace coltt::hnsw;
 
 namespace {
 
+// What the prologue of a row-filter launch does unless COLTT_DESCENT_NT / COLTT_ROW_FILTER_UPPER say otherwise.  Measured on 10 M x 768, ef 128, 10 000 queries
+// per launch, four sides alternating in one process (tools/descent_filter_ab.py; profiles/r12a_descent_filter.md): cacheable descent loads 9.06 -> 8.76 ms
+// (+3.4 %); the filtered descent on top of them 8.80 ms — it rejects 90 % of the 116 evaluations above level 0 and asks for a third of the bytes, but with the
+// top of the graph served from cache those bytes were no longer HBM's, and a hop now waits for two dependent phases instead of one.
+constexpr bool DESCENT_NT_DEFAULT = false;         // the entrypoint's and the descent's rows are loaded cacheable: every query of a launch reads them
+constexpr bool ROW_FILTER_UPPER_DEFAULT = false;   // the greedy descent evaluates every listed neighbour exactly
+
 // hnsw_walk2.hpp kernels: the shipped variant (and its Bloom-less twin for geometries whose LDS has no room for the filter).
 template <int METRIC, int QUANT>
 int launch_search2_for(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
                    uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
   typedef void (*kern_t)(GraphView, int32_t, int32_t, const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*,
                          uint64_t*, float*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*);
+  typedef void (*fkern_t)(GraphView, int32_t, int32_t, const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*,
+                          uint64_t*, float*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*, uint32_t);   // the row-filter twins: + how the prologue descends
   kern_t kern = nullptr;
+  fkern_t fkern = nullptr;
   const bool nt = rows_nt(x);   // non-temporal row loads (eight-lane kernels): see exact.hpp: row_ld
   bool flt = false;             // the row-filter twin (row_filter_on)
   bool v16 = false;             // ... over the 16-bit visited set (search_geom: vis16)
@@ -35,10 +45,10 @@ int launch_search2_for(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, ui
         if constexpr (METRIC == M_COS && QUANT == Q_NONE) {   // the row-filter twin of the eight-lane instance just chosen
           if (sg.ev8 && row_filter_on(x, false)) {
             const int fb = row_filter_bits(x);
-            if (fb == ROW_FILTER_8I && sg.qd8i && sg.vis16) { kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS16, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS16, false, ROW_FILTER_8I>; v16 = true; }
-            else if (fb == ROW_FILTER_8I && sg.qd8i) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, ROW_FILTER_8I>;   // (sg.qd8i: search_geom made room for the digit planes)
-            else if (fb == 8 || fb == ROW_FILTER_8I) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, 8>;
-            else kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false>;
+            if (fb == ROW_FILTER_8I && sg.qd8i && sg.vis16) { fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS16, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS16, false, ROW_FILTER_8I>; v16 = true; }
+            else if (fb == ROW_FILTER_8I && sg.qd8i) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, ROW_FILTER_8I>;   // (sg.qd8i: search_geom made room for the digit planes)
+            else if (fb == 8 || fb == ROW_FILTER_8I) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, 8>;
+            else fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false>;
             flt = true;
           }
         }
@@ -53,15 +63,15 @@ int launch_search2_for(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, ui
     }
     if constexpr (METRIC == M_COS && QUANT == Q_NONE) {   // W2_ADJN: both shipped HBM-visited variants carry the neighbours' norms
       if (sg.ev8 && row_filter_on(x, true) && (sg.w2 == 6 || sg.w2 == 7)) flt = true;
-      if (flt && sg.w2 == 6) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false>;
-      if (flt && sg.w2 == 7) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false>;
+      if (flt && sg.w2 == 6) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false>;
+      if (flt && sg.w2 == 7) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false>;
       const int fb = flt ? row_filter_bits(x) : 0;
       if (fb == ROW_FILTER_8I && sg.qd8i) {
-        if (sg.w2 == 6) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false, ROW_FILTER_8I>;
-        if (sg.w2 == 7) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false, ROW_FILTER_8I>;
+        if (sg.w2 == 6) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false, ROW_FILTER_8I>;
+        if (sg.w2 == 7) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false, ROW_FILTER_8I>;
       } else if (fb == 8 || fb == ROW_FILTER_8I) {
-        if (sg.w2 == 6) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false, 8>;
-        if (sg.w2 == 7) kern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false, 8>;
+        if (sg.w2 == 6) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false, 8>;
+        if (sg.w2 == 7) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false, 8>;
       }
     }
     if constexpr (QUANT != Q_F8) { if (!flt) {
@@ -72,27 +82,41 @@ int launch_search2_for(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, ui
     } }
   }
 #undef COLTT_W2
-  if (!kern) return fail(COLTT_E_UNSUPPORTED, "hnsw_search: walk variant %d is not compiled into this build (COLTT_WALK2)", sg.w2);
+  uint32_t upper = 0;
+  if (flt && fkern) {   // (the binary16 kind has no per-slot (scale, error norm): its descent stays exact)
+    const Policy p = policy();
+    const int fb = row_filter_bits(x);
+    if ((fb == 8 || fb == ROW_FILTER_8I) && (p.row_filter_upper >= 0 ? p.row_filter_upper != 0 : ROW_FILTER_UPPER_DEFAULT)) upper |= ROWF_UPPER_FILTER;
+    if (nt && (p.descent_nt >= 0 ? p.descent_nt == 0 : !DESCENT_NT_DEFAULT)) upper |= ROWF_UPPER_CACHED;
+  }
+  c->upper_launch = (upper & ROWF_UPPER_FILTER) != 0;
+  if (!kern && !fkern) return fail(COLTT_E_UNSUPPORTED, "hnsw_search: walk variant %d is not compiled into this build (COLTT_WALK2)", sg.w2);
   if (x->r8 && !sg.ev8 && !(sg.w2_lds ? sg.w2 == 4 : (sg.w2 == 6 || sg.w2 == 7)))
     return fail(COLTT_E_UNSUPPORTED, "hnsw_search: walk variant %d has no instance for line-transposed rows (create the index with COLTT_ROWS8=0 for this experiment)", sg.w2);
   if (sg.ev8) x->ev8_launches.fetch_add(1);
   if (sg.vis16 && !v16) return fail(COLTT_E_DEVICE, "hnsw_search: the launch's LDS was sized for the 16-bit visited set, but the walk chosen does not use it");
   c->flt_launch = flt; c->v16_launch = v16;
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
+  const void* const kp = fkern ? reinterpret_cast<const void*>(fkern) : reinterpret_cast<const void*>(kern);
+  COLTT_HIP(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
   static const bool dbg_occ = [] { const char* e = getenv("COLTT_DEBUG_OCCUPANCY"); return e && *e == '1'; }();   // diagnostics: the waves the runtime keeps resident per CU at this launch's LDS
   if (dbg_occ || v16) {   // (the 16-bit launches report it through coltt_hnsw_visited_stats: asked once per (kernel, LDS) and context)
-    if (c->occ_kern != reinterpret_cast<const void*>(kern) || c->occ_lds != sg.lds) {
+    if (c->occ_kern != kp || c->occ_lds != sg.lds) {
       int per_cu = 0;
-      COLTT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64, sg.lds));
-      c->occ_kern = reinterpret_cast<const void*>(kern); c->occ_lds = sg.lds; c->occ_per_cu = per_cu;
+      COLTT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, 64, sg.lds));
+      c->occ_kern = kp; c->occ_lds = sg.lds; c->occ_per_cu = per_cu;
     }
     if (dbg_occ) fprintf(stderr, "[occupancy] walk variant %d%s filter %d (8i planes %d) visited set %s: %zu B of LDS per wave, %d waves resident per CU, grid %u\n", sg.w2, sg.w2_lds ? " (LDS hash)" : "", flt ? 1 : 0, sg.qd8i ? 1 : 0,
                          v16 ? "16-bit LDS table" : (sg.w2_lds ? "32-bit LDS table" : "HBM byte map"), sg.lds, c->occ_per_cu, grid);
   }
-  kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
-                                        k, sg.ef, sg.ef_pad, sg.w2_lds ? (v16 ? ((sg.v16_limit << 8) | sg.v16_bits) : sg.hcap) : sg.bloom_words, counter, oi, os, oc, stats,
-                                        x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
-                                        x->w_vepoch.as<uint32_t>() + region_base);
+  const uint32_t vis_arg = sg.w2_lds ? (v16 ? ((sg.v16_limit << 8) | sg.v16_bits) : sg.hcap) : sg.bloom_words;
+  if (fkern) fkern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
+                                                    k, sg.ef, sg.ef_pad, vis_arg, counter, oi, os, oc, stats,
+                                                    x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
+                                                    x->w_vepoch.as<uint32_t>() + region_base, upper);
+  else kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
+                                             k, sg.ef, sg.ef_pad, vis_arg, counter, oi, os, oc, stats,
+                                             x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
+                                             x->w_vepoch.as<uint32_t>() + region_base);
   COLTT_HIP(hipGetLastError());
   return COLTT_OK;
 }
@@ -128,6 +152,17 @@ int coltt_hnsw_row_filter_stats(coltt_handle_t h, uint64_t* out_rejected, uint64
   if (out_launches) *out_launches = x->flt_launches.load();
   if (out_shadow_rows) *out_shadow_rows = x->flt_shadow_rows.load();
   if (out_has_shadow) *out_has_shadow = (x->has_shadow16() ? 16 : 0) | (x->has_shadow8() ? 8 : 0);   // non-zero: some shadow is kept; bit 3 / bit 4: which
+  return COLTT_OK;
+}
+
+int coltt_hnsw_row_filter_stats_ex(coltt_handle_t h, uint64_t* out_upper_shadow_rows, uint64_t* out_upper_rejected, uint64_t* out_upper_f32_rows, uint64_t* out_upper_launches) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_row_filter_stats_ex: unknown handle");
+  ReadLock g(x->rw);
+  if (out_upper_shadow_rows) *out_upper_shadow_rows = x->flt_up_shadow_rows.load();
+  if (out_upper_rejected) *out_upper_rejected = x->flt_up_rejected.load();
+  if (out_upper_f32_rows) *out_upper_f32_rows = x->flt_up_f32_rows.load();
+  if (out_upper_launches) *out_upper_launches = x->flt_up_launches.load();
   return COLTT_OK;
 }
 

@@ -343,6 +343,8 @@ template <int METRIC, int QUANT, bool ADJN, bool NT, int BITS = 16> struct Group
   }
   __device__ __forceinline__ float one(const GraphView& g, const WaveCtx& w, uint32_t slot, int lane) const { return base_t().one(g, w, slot, lane); }
   // the chunk's distances given the pop's lowerBound and whether the set was full at the pop (search_level2)
+  // PT_A: the phase clock's slot for phase A (diagnostic build only; the descent charges its own to the prologue's)
+  template <int PT_A = 7>
   __device__ __forceinline__ float filtered(const GraphView& g, const WaveCtx& w, uint32_t nb, bool fresh, float nrm, int half, int lane, float lower_bound, bool full_at_pop) {
     const int nl = (g.dim * 4) >> 7, nlh = nl >> 1;   // rows_h_shape: dim % 256 == 0, so nl % 8 == 0 and nlh % 4 == 0
     const bool mine = fresh && half == 0;
@@ -393,7 +395,7 @@ template <int METRIC, int QUANT, bool ADJN, bool NT, int BITS = 16> struct Group
     const unsigned long long S = __ballot(surv);
     const uint32_t ns = (uint32_t)__popcll(S);
     n_rej += nf - ns; n_f32 += ns; n_h16 += nf;
-    COLTT_PT(const_cast<WaveCtx&>(w), 7)  // phase A: shadow rows + bounds (diagnostic build only; slot 3 then holds phase B and the unfiltered chunks)
+    COLTT_PT(const_cast<WaveCtx&>(w), PT_A)  // phase A: shadow rows + bounds (diagnostic build only; slot 3 then holds phase B and the unfiltered chunks)
     float r = d_lo;
     wave_sync();   // every lane holds its bound before the scratch is rewritten
     if (ns) {      // phase B (wave-uniform): the survivors' f32 rows through the exact stream
@@ -436,6 +438,47 @@ __device__ __forceinline__ void greedy_level8(const GraphView& g, WaveCtx& w, ui
       const bool valid = nb != NBR_NONE && !is_deleted(g, nb);
       float d = 0.f;
       if (__ballot(valid)) d = ev(g, w, nb, valid, 0.f, half, lane);
+      w.n_dist += __popcll(__ballot(valid && half == 0));
+      const unsigned long long key = valid ? (((unsigned long long)__float_as_uint(d) << 32) | idx) : ~0ull;
+      const unsigned long long km = wave_min_u64(key);
+      if (km < best) {
+        best = km;
+        const int src = (int)(((uint32_t)km - c0) * 2);
+        best_slot = (uint32_t)__builtin_amdgcn_readlane((int)nb, src);
+      }
+    }
+    w.n_hops++;
+    const float bd = __uint_as_float((uint32_t)(best >> 32));
+    if (best != ~0ull && bd < curd) { cur = best_slot; curd = bd; }
+    else break;
+  }
+}
+// greedy_level8 THROUGH THE CERTIFIED FILTER (the 8-bit kinds of Group8FilterEval; COLTT_ROW_FILTER_UPPER).  A hop uses its distances for one decision: is
+// the smallest of them < curd?  A neighbour with a certified d_lo >= curd can neither be that minimum nor tie with it, so the chunk goes through
+// Group8FilterEval::filtered with lower_bound = curd and a full set: shadow rows for every valid neighbour, the exact stream for what the shadow cannot
+// reject (and for everything row_filter_rejects gives no verdict on).  A survivor gets the exact distance (the bits Group8Eval returns), a rejected
+// neighbour a value >= curd: the minimum key below is < curd exactly when the exact minimum is, and then it IS the exact minimum — same cur, curd,
+// n_dist and n_hops (tests/test_descent_filter_host.py replays it with the headers' bounds).  The upper rows carry neither norms nor (scale, error
+// norm): two small gathers per neighbour.  ev's counters: shadow rows / rejected / f32 rows of the descent (the level-0 walk has an evaluator of its own).
+template <class FEV>
+__device__ __forceinline__ void greedy_level8_filtered(const GraphView& g, WaveCtx& w, uint32_t& cur, float& curd, int level, int lane_in, FEV& ev) {
+  static_assert(FEV::ROW_META, "the filtered descent reads the 8-bit shadow");
+  for (uint32_t hops = 0;; hops++) {
+    const int lane = opaque_lane(lane_in);
+    const int half = lane & 1, p = lane >> 1;
+    if (hops > (1u << 20)) { w.err |= 4u; break; }
+    uint32_t width;
+    const uint32_t* row = adj_row(g, cur, level, width);
+    unsigned long long best = ~0ull;
+    uint32_t best_slot = NBR_NONE;
+    for (uint32_t c0 = 0; c0 < width; c0 += 32) {
+      const uint32_t idx = c0 + p;
+      const uint32_t nb = idx < width ? row[idx] : NBR_NONE;
+      const bool valid = nb != NBR_NONE && !is_deleted(g, nb);
+      const float nrm = valid ? g.norms[nb] : 0.f;
+      ev.mt = valid ? g.rows_m[nb] : float2{0.f, 0.f};
+      float d = 0.f;
+      if (__ballot(valid)) d = ev.template filtered<5>(g, w, nb, valid, nrm, half, lane, curd, true);
       w.n_dist += __popcll(__ballot(valid && half == 0));
       const unsigned long long key = valid ? (((unsigned long long)__float_as_uint(d) << 32) | idx) : ~0ull;
       const unsigned long long km = wave_min_u64(key);

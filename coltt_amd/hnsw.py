@@ -537,11 +537,15 @@ class Hnsw:
 
     def RowFilterStats(self):
         """the level-0 row filter (coltt_hnsw_row_filter_stats): cumulative evaluations it rejected, f32 rows and shadow rows the filtered
-        launches read at level 0, filtered launches, whether the index keeps a shadow of its rows and of which kinds (8 / 16 bits)"""
+        launches read at level 0, filtered launches, whether the index keeps a shadow of its rows and of which kinds (8 / 16 bits); upper_*: the same
+        counters of the filtered descent (levels above 0; COLTT_ROW_FILTER_UPPER) and the launches that ran it (coltt_hnsw_row_filter_stats_ex)"""
         r, e, s, n, f = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
         L.check(L.lib().coltt_hnsw_row_filter_stats(self.h, C.byref(r), C.byref(e), C.byref(s), C.byref(n), C.byref(f)))
+        us, ur, uf, un = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.check(L.lib().coltt_hnsw_row_filter_stats_ex(self.h, C.byref(us), C.byref(ur), C.byref(uf), C.byref(un)))
         return {"rejected": r.value, "f32_rows": e.value, "shadow_rows": s.value, "launches": n.value, "shadow": bool(f.value),
-                "shadow_bits": tuple(b for b in (8, 16) if f.value & b)}
+                "shadow_bits": tuple(b for b in (8, 16) if f.value & b),
+                "upper_shadow_rows": us.value, "upper_rejected": ur.value, "upper_f32_rows": uf.value, "upper_launches": un.value}
 
     def VisitedStats(self):
         """the visited set of the last search launch (coltt_hnsw_visited_stats): its kind (0 HBM byte map, 32 LDS table of 32-bit slots, 16 the 16-bit LDS

@@ -543,6 +543,10 @@ int coltt_hnsw_rows8_searches(coltt_handle_t h, uint64_t* out_launches, int32_t*
  * index keeps the 8-bit shadow, else 16; the kind an index does not keep is served by the one it does.  *out_has_shadow is non-zero when any
  * shadow is kept: 8, 16 or 24 (both).  The shadow-row counter counts rows of whichever kind the launches read. */
 int coltt_hnsw_row_filter_stats(coltt_handle_t h, uint64_t* out_rejected, uint64_t* out_f32_rows, uint64_t* out_shadow_rows, uint64_t* out_launches, int32_t* out_has_shadow);
+/* The same for the greedy descent of the 8-bit row-filter walks (COLTT_ROW_FILTER_UPPER=1): cumulative shadow rows read, evaluations rejected and f32 rows
+ * read at the levels ABOVE 0 (the entrypoint's own row is not among them), and the launches that ran the filtered descent.  The counters of
+ * coltt_hnsw_row_filter_stats keep their level-0 meaning.  Any pointer may be NULL. */
+int coltt_hnsw_row_filter_stats_ex(coltt_handle_t h, uint64_t* out_upper_shadow_rows, uint64_t* out_upper_rejected, uint64_t* out_upper_f32_rows, uint64_t* out_upper_launches);
 /* The visited set of the level-0 walks (an internal of the search kernels: same answers and counters whichever serves).  Walks with ef <= 128 keep it in
  * LDS: an open-addressed table of 32-bit slots (32 KiB, four traversals per CU with 768-d f32 rows), or — the row-filter walk over the quantised query on an
  * index of at most 2^24 slots — an exact two-choice table of 16-bit entries with a 16-word stash (coltt_amd/csrc/vis16.hpp: 16 KiB, seven traversals per CU).

@@ -61,7 +61,7 @@ PQF_ALL(true)
                       // the quantised query (integer phase A, row_filter8i.hpp), that kind's ef > 128 twin (walk variant 7), and the headline over the
                       // 16-bit visited set (vis16.hpp; VIS_LDS16 = 2: two waves per SIMD)
 #define RFK(PROF, OPT, VIS, BITS) template __global__ void hnsw_search2_rowfilter_kernel<PROF, OPT, VIS, true, BITS>(GraphView, int32_t, int32_t, const float*, const float*, uint32_t, uint32_t, uint32_t, \
-    uint32_t, uint32_t, uint32_t*, uint64_t*, float*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*);
+    uint32_t, uint32_t, uint32_t*, uint64_t*, float*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*, uint32_t);
 RFK(1, 4, 1, 8)
 RFK(1, 4, 1, 16)
 RFK(1, 4, 1, 80)

@@ -33,7 +33,11 @@ def read_counter(path, counter="FETCH_SIZE"):
             per_dispatch[key] = per_dispatch.get(key, 0.0) + float(r["Counter_Value"])
     out = collections.defaultdict(list)
     for (_, name, grid), v in per_dispatch.items():
-        if "hnsw_search2_kernel" in name:   # round 3: hnsw_walk2.hpp — <METRIC, QUANT, PROFILE, OPT[, VISMODE]>; VISMODE 1 = the LDS hash (ef <= 128)
+        if "hnsw_search2_rowfilter_kernel" in name:   # the row-filter twins: <PROFILE, OPT, VISMODE, NT, BITS>; VISMODE 0 = the HBM byte map, 1 / 2 = the LDS tables; f32 rows only
+            m = re.search(r"hnsw_search2_rowfilter_kernel<([^>]*)>", name)
+            t = [x.strip() for x in m.group(1).split(",")] if m else ["0", "0", "1"]
+            short = "hnsw_search_kernel/hbm" if len(t) >= 3 and t[2].endswith("0") else "hnsw_search_kernel/lds"
+        elif "hnsw_search2_kernel" in name:   # round 3: hnsw_walk2.hpp — <METRIC, QUANT, PROFILE, OPT[, VISMODE]>; VISMODE 1 = the LDS hash (ef <= 128)
             m = re.search(r"hnsw_search2_kernel<([^>]*)>", name)
             t = [x.strip() for x in m.group(1).split(",")] if m else ["0", "0"]
             q = t[1]
