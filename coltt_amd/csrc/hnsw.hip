@@ -540,7 +540,7 @@ namespace coltt {
 namespace hnsw {
 // (Re)allocate the HBM visited set for the current slot capacity: one byte per slot and workgroup, zeroed, epochs reset.
 // Sized against a quarter of the device memory; if that buys fewer than one region per CU the LDS hash is used instead.
-int ensure_visg(Hnsw* x) {
+int ensure_visg(Hnsw* x, const Policy& pol) {
   // Callers hold the index lock (shared or exclusive).  The slot capacity only changes under the exclusive lock, and every
   // search that wants the byte map passes through here first, so a re-allocation can never race a traversal that uses it.
   std::lock_guard<std::mutex> vg(x->vis_mu);
@@ -553,7 +553,7 @@ int ensure_visg(Hnsw* x) {
   size_t free_b = 0, total_b = 0;
   COLTT_HIP(hipMemGetInfo(&free_b, &total_b));
   uint64_t budget = std::min<uint64_t>(total_b / 4, free_b / 2);
-  if (policy().visg_budget_mb >= 0) budget = std::min<uint64_t>(budget, (uint64_t)policy().visg_budget_mb << 20);  // test knob
+  if (pol.visg_budget_mb >= 0) budget = std::min<uint64_t>(budget, (uint64_t)pol.visg_budget_mb << 20);  // test knob
   const uint64_t regions = std::min<uint64_t>(want_max, budget / stride);
   x->vis_stride = stride; x->vis_want = want_max;
   x->vis_regions = 0;
@@ -600,25 +600,91 @@ void acquire_regions(Hnsw* x, uint32_t want, RegionLease& out) {
 }  // namespace hnsw
 }  // namespace coltt
 
-namespace {
+// ---- The search plan: which kernel one coltt_hnsw_search call launches, and how.  Pure functions of (PlanFacts, Policy): no HIP call, no Hnsw, no
+// environment.  search_common takes one policy() snapshot and calls plan_search once; coltt_hnsw_search_plan_host runs the same code with no device.
+// DESIGN.md ("The search plan") has the decision table in one place.
+namespace coltt {
+namespace hnsw {
+PlanFacts plan_facts(const Hnsw* x) {
+  PlanFacts f{};
+  f.dim = x->dim; f.metric = x->metric; f.quant = x->quant; f.m_max0 = (uint32_t)x->cfg.m_max0; f.stride = x->stride; f.slots = x->n;
+  f.r8 = x->r8; f.shadow8 = x->has_shadow8(); f.shadow16 = x->has_shadow16();
+  f.vis_ready = x->vis_stride != 0 && x->vis_regions > 0; f.vis_regions = x->vis_regions;
+  return f;
+}
+
 // COLTT_VISG=0 / 1 forces the LDS hash / the HBM byte map (measurement and test knob, read at every call); default: the
 // byte map above ef 128.  Measured on 10 M x 768 f16 (lowrank:32), queries/s LDS hash -> byte map: ef 128 728 k -> 724 k,
 // ef 256 246 k -> 404 k, ef 512 62 k -> 212 k, ef 1024 25 k -> 105 k; build (efConstruction 200) 36 s -> 22 s.
-int visg_policy() { return policy().visg; }
+bool wants_visg(const Policy& pol, uint32_t ef) { return pol.visg < 0 ? ef > COLTT_VISG_MIN_EF : pol.visg != 0; }
 
-}  // namespace
-
-namespace coltt {
-namespace hnsw {
-// does this ef want the HBM visited set (policy only; whether the workspace could be had is vis_regions > 0)
-bool wants_visg(uint32_t ef) {
-  const int pol = visg_policy();
-  return pol < 0 ? ef > COLTT_VISG_MIN_EF : pol != 0;
+// The one-wave walk's LDS: query + `extra` bytes + result set (merged in place) + the visited set.
+static SearchGeom row_walk_lds(const PlanFacts& f, const Policy& pol, uint32_t ef, size_t extra) {
+  SearchGeom s;
+  s.ef = ef;
+  s.ef_pad = (ef + 63) & ~63u;
+  const size_t fixed = (((size_t)f.dim * 4 + 15) & ~(size_t)15) + extra + (size_t)s.ef_pad * 8;
+  // LDS visited set: sized so that a typical traversal (a few dozen evaluations per result slot) never resets
+  s.hcap = std::min<uint32_t>(32768u, std::max<uint32_t>(8192u, next_pow2(ef * 48u)));
+  // large ef x dim: shrink it until the wave's state fits the CU's 160 KiB (the reset-and-reseed path keeps results exact;
+  // it needs 0.75 * hcap > ef + 64)
+  while (fixed + (size_t)s.hcap * 4 > 160 * 1024 && s.hcap > 4096 && (s.hcap / 2) * 3 / 4 > ef + 64) s.hcap /= 2;
+  s.visg = wants_visg(pol, ef) && f.vis_ready;
+  if (s.visg) { s.hcap = 64; s.lds = fixed; s.max_grid = f.vis_regions; }
+  else { s.lds = fixed + (size_t)s.hcap * 4; s.max_grid = 0xffffffffu; }
+  return s;
 }
-}  // namespace hnsw
-}  // namespace coltt
+SearchGeom walk_geom(const PlanFacts& f, const Policy& pol, uint32_t ef, uint32_t allowed) { return row_walk_lds(f, pol, ef, (size_t)((allowed + 63) & ~63u) * 8); }
 
-namespace {
+// Resident waves per CU.  2-byte rows want all 8 (two per SIMD); f32 rows are faster with 4: eight 3-KB-per-row streams per
+// CU measured slower both in search (ef 256: 160 k vs 197 k q/s) and in the 10 M build (61 s vs 50 s).  COLTT_WAVES_PER_CU
+// overrides (measurement knob).
+static size_t waves_per_cu_cap(const Policy& pol, int quant) { return pol.waves_per_cu > 0 ? (size_t)pol.waves_per_cu : (quant == Q_NONE ? 4 : 8); }
+// The walk over the 16-bit visited set is compiled for two waves per SIMD and its LDS fits seven times: all seven (COLTT_WAVES_PER_CU overrides here too).
+#ifndef COLTT_VIS16_WAVES_PER_CU
+#define COLTT_VIS16_WAVES_PER_CU 7
+#endif
+uint32_t resident_waves(const Policy& pol, int quant, size_t lds, int w2, bool vis16) {
+  const size_t cap = (w2 >= 0 && (w2 & 8)) ? 4 : (vis16 && pol.waves_per_cu <= 0) ? (size_t)COLTT_VIS16_WAVES_PER_CU : waves_per_cu_cap(pol, quant);
+  return 256u * (uint32_t)std::max<size_t>(1, std::min<size_t>(cap, (160 * 1024) / lds));
+}
+
+// Non-temporal row loads for the eight-lane walks (exact.hpp: row_ld): worth it when the row array is far larger than L2 + MALL, costly when later queries
+// would have found the rows there.  COLTT_ROWS_NT = 0 / 1 forces, COLTT_ROWS_NT_MIN_MB moves the threshold (default 12 GiB of rows: 768-d rows, same box — f16 0.5 M -24 %, 1 M -10 %,
+// 2 M -2 %, 4 M +0.8 %, 10 M +-0; f32 1 M -4 %, 3 M +0.7 %, 10 M +4.5 %: profiles/r06ag_nt_rows_ab.md).
+static bool rows_far_larger_than_caches(const PlanFacts& f, const Policy& pol) { return (unsigned long long)f.slots * (unsigned long long)f.stride >= ((unsigned long long)pol.rows_nt_min_mb << 20); }
+static bool rows_nt(const PlanFacts& f, const Policy& pol) { return pol.rows_nt >= 0 ? pol.rows_nt != 0 : rows_far_larger_than_caches(f, pol); }
+// The certified row filter of the eight-lane f32 cosine walks (hnsw_walk2.hpp: Group8FilterEval).  COLTT_ROW_FILTER = 0 / 1 forces (read per call: one index in
+// one process runs both kernels, tools/row_filter_ab.py); unset: on for the LDS-hash walk (ef <= 128, the measured instance: 10 M x 768, ef 128, 1.41 x in one
+// process, profiles/r07a_row_filter.md) where the row array is far larger than the caches: every row read is then an HBM read and the kernel sits at what the
+// memory system delivers, so bytes are time.
+// COLTT_ROW_FILTER_BITS = 8 / 16 / 8i picks the shadow a filtered launch reads; unset: the 8-bit one where the index keeps it.  An index keeps
+// what COLTT_ROW_SHADOW_BITS said when it was created; the kind it does not keep is served by the one it does.  8i (ROW_FILTER_8I) reads the 8-bit shadow
+// against the query quantised once per traversal: phase A is an integer sum (row_filter8i.hpp); it is what an unset knob takes over the 8-bit shadow
+// (COLTT_ROW_FILTER8I_DEFAULT; the measurement behind it: profiles/r10a_row_filter8i.md).
+#ifndef COLTT_ROW_FILTER8I_DEFAULT
+#define COLTT_ROW_FILTER8I_DEFAULT 1
+#endif
+// the shadow an eight-lane f32 cosine launch filters through (16, 8, ROW_FILTER_8I), 0 = no filter
+static int row_filter_kind(const PlanFacts& f, const Policy& pol, bool vis_hbm) {
+  const bool h8 = f.shadow8 != 0, h16 = f.shadow16 != 0;
+  if (!h8 && !h16) return 0;
+  // unset and over the HBM map: off — the ef > 128 twins have not been timed against their unfiltered partners: COLTT_ROW_FILTER=1 only.  Unset otherwise:
+  // the SIZE rule of the non-temporal hint (not its forcing knob COLTT_ROWS_NT: an A/B of the hint must not toggle the filter too).  The threshold is
+  // inherited from that rule's measured crossover, the filter's own crossover on 1 M / 3 M has not been measured.
+  if (!(pol.row_filter >= 0 ? pol.row_filter != 0 : (!vis_hbm && rows_far_larger_than_caches(f, pol)))) return 0;
+  const int want = pol.row_filter_bits;
+  if (want == 16) return h16 ? 16 : 8;
+  if (want == 8) return h8 ? 8 : 16;
+  if (want == ROW_FILTER_8I) return h8 ? ROW_FILTER_8I : 16;
+  return h8 ? (COLTT_ROW_FILTER8I_DEFAULT ? ROW_FILTER_8I : 8) : 16;
+}
+// What the prologue of a row-filter launch does unless COLTT_DESCENT_NT / COLTT_ROW_FILTER_UPPER say otherwise.  Measured on 10 M x 768, ef 128, 10 000 queries
+// per launch, four sides alternating in one process (tools/descent_filter_ab.py; profiles/r12a_descent_filter.md): cacheable descent loads 9.06 -> 8.76 ms
+// (+3.4 %); the filtered descent on top of them 8.80 ms — it rejects 90 % of the 116 evaluations above level 0 and asks for a third of the bytes, but with the
+// top of the graph served from cache those bytes were no longer HBM's, and a hop now waits for two dependent phases instead of one.
+constexpr bool DESCENT_NT_DEFAULT = false;         // the entrypoint's and the descent's rows are loaded cacheable: every query of a launch reads them
+constexpr bool ROW_FILTER_UPPER_DEFAULT = false;   // the greedy descent evaluates every listed neighbour exactly
 
 // Which level-0 walk serves the HBM-visited searches.  COLTT_WALK2=off: hnsw_dev.hpp:search_level (the round-2 kernel);
 // COLTT_WALK2=<n>: hnsw_walk2.hpp with OPT = n (1 Bloom, 2 delta result set, 4 adjacency-carried norms); the library carries 6 and 7.
@@ -626,8 +692,6 @@ namespace {
 #ifndef COLTT_WALK2_DEFAULT
 #define COLTT_WALK2_DEFAULT 7
 #endif
-int walk2_policy() { const int v = policy().walk2; return v == 7 ? COLTT_WALK2_DEFAULT : v; }
-
 // The walk of the LDS-visited searches (ef <= 128 by default).  COLTT_WALK2_LDS=off: hnsw_dev.hpp:search_level; 2 / 4 / 6: hnsw_walk2.hpp
 // with the delta result set / adjacency-carried norms / both.  A traversal that would overflow the hash table re-runs the call on
 // search_level (which re-seeds the table from the result set) — never seen on the benchmark collections.
@@ -637,130 +701,102 @@ int walk2_policy() { const int v = policy().walk2; return v == 7 ? COLTT_WALK2_D
 #ifndef COLTT_WALK2_LDS_DEFAULT
 #define COLTT_WALK2_LDS_DEFAULT 4
 #endif
-int walk2_lds_policy() { const int v = policy().walk2_lds; return v == 4 ? COLTT_WALK2_LDS_DEFAULT : v; }
+// Batches of at most COLTT_LAT_MAX_NQ queries (default below; COLTT_MW_MAX_NQ is the round-2 name of the knob) take the
+// 256-thread latency kernel (hnsw_lat.hpp).
+// Measured at 10 M x 768 f32, ef 128 (profiles/r03_latency.json): 1 query 1.04 ms against 1.43 ms on the one-wave kernel, 128 queries
+// 1.45 against 1.97 ms; beyond ~256 queries every CU already holds a workgroup and the one-wave kernel's 1024+ resident traversals win.
+#ifndef COLTT_LAT_MAX_NQ_DEFAULT
+#define COLTT_LAT_MAX_NQ_DEFAULT 256
+#endif
+#ifndef COLTT_LAT_MIN_STRIDE
+#define COLTT_LAT_MIN_STRIDE 1024   // bytes per stored row below which a lane pair streams the whole row in one burst anyway
+#endif
 
-// Resident waves per CU.  2-byte rows want all 8 (two per SIMD); f32 rows are faster with 4: eight 3-KB-per-row streams per
-// CU measured slower both in search (ef 256: 160 k vs 197 k q/s) and in the 10 M build (61 s vs 50 s).  COLTT_WAVES_PER_CU
-// overrides (measurement knob).
-size_t waves_per_cu_cap(int quant) {
-  if (policy().waves_per_cu > 0) return (size_t)policy().waves_per_cu;
-  return quant == Q_NONE ? 4 : 8;
-}
-
-// COLTT_EV8=0: level-0 distances from the pair-owned rows even when the index carries the line-transposed copy (A/B and test knob)
-bool ev8_policy() { return policy().ev8; }
-
-}  // namespace
-
-namespace coltt {
-namespace hnsw {
-SearchGeom search_geom(Hnsw* x, uint32_t ef, bool for_search, bool no_w2_lds, uint32_t filt_k) {
-  SearchGeom s;
-  s.ef = ef;
-  s.ef_pad = (ef + 63) & ~63u;
-  const size_t qbytes = ((size_t)x->dim * 4 + 15) & ~(size_t)15;
+// force: 1 = not the latency kernel, 2 = not the walk2 LDS-hash kernel (both after an err 8).  ef: the call's or the index's; the plan's is max(ef, k).
+int plan_search(const PlanFacts& f, const Policy& pol, size_t nq, uint32_t k, uint32_t ef, int force, SearchPlan& s) {
+  s = SearchPlan{};
+  if (k == 0) return fail(COLTT_E_INVALID, "hnsw_search: k must be >= 1");
+  ef = std::max(ef, k);  // gomath.MaxInt(ef, k), hnsw.go:258
+  if (ef > 4096) return fail(COLTT_E_UNSUPPORTED, "hnsw_search: ef=%u > 4096", ef);
+  const bool hbm = wants_visg(pol, ef) && f.vis_ready;
+  // The walk: hnsw_walk2.hpp over the HBM map (COLTT_WALK2) or over the LDS hash (small ef: delta result set, adjacency-carried norms; no Bloom filter —
+  // the hash is on chip), else the one-wave walk.
+  int w2 = -1;
+  if (f.m_max0 <= 1024) {
+    if (hbm) w2 = pol.walk2 == 7 ? COLTT_WALK2_DEFAULT : pol.walk2;
+    else if (!(force & 2)) w2 = pol.walk2_lds == 4 ? COLTT_WALK2_LDS_DEFAULT : pol.walk2_lds;
+  }
   // eight lanes per row (rows8.hpp): a second, permuted copy of the query and 96 words of scratch per wave.  Served by the shipped
-  // walk2 variants only (LDS hash: 4; HBM map: 6 / 7).
-  const bool vis_hbm = wants_visg(ef) && x->vis_stride != 0 && x->vis_regions > 0;
-  const bool want8 = for_search && x->r8 && x->n > 0 && ev8_policy() && x->cfg.m_max0 <= 1024 &&
-                     (vis_hbm ? (walk2_policy() == 6 || walk2_policy() == 7) : (!no_w2_lds && walk2_lds_policy() == 4));
+  // walk2 variants only (LDS hash: 4; HBM map: 6 / 7).  COLTT_EV8=0: level-0 distances from the pair-owned rows even when the index carries the
+  // line-transposed copy (A/B and test knob)
+  const bool ev8 = f.r8 && f.slots > 0 && pol.ev8 && walk2_shipped(hbm, w2);
+  const int filter = ev8 && f.metric == COLTT_COSINE && f.quant == COLTT_Q_NONE ? row_filter_kind(f, pol, hbm) : 0;
   // the row filter over the quantised query (row_filter8i.hpp): two planes of dim signed bytes per wave behind the scratch (hnsw_kernels.hpp:
   // hnsw_search2_rowfilter_kernel).  768-d, ef 128: 4 x (37 248 + 1 536) = 155 136 bytes per CU, four traversals still fit.
-  s.qd8i = want8 && filt_k == 0 && x->metric == COLTT_COSINE && x->quant == COLTT_Q_NONE && row_filter_on(x, vis_hbm) && row_filter_bits(x) == ROW_FILTER_8I;
-  const size_t fixed = qbytes + (want8 ? 96 * 4 : 0) + (s.qd8i ? (size_t)x->dim * 2 : 0) + (size_t)s.ef_pad * 8 + (size_t)((filt_k + 63) & ~63u) * 8;   // query (+ the eight-lane core's scratch) (+ the digit planes) + result set (merged in place) (+ the allowed set)
-  // LDS visited set: sized so that a typical traversal (a few dozen evaluations per result slot) never resets
-  s.hcap = std::min<uint32_t>(32768u, std::max<uint32_t>(8192u, next_pow2(ef * 48u)));
-  // large ef x dim: shrink it until the wave's state fits the CU's 160 KiB (the reset-and-reseed path keeps results exact;
-  // it needs 0.75 * hcap > ef + 64)
-  while (fixed + (size_t)s.hcap * 4 > 160 * 1024 && s.hcap > 4096 && (s.hcap / 2) * 3 / 4 > ef + 64) s.hcap /= 2;
-  s.visg = wants_visg(ef) && x->vis_stride != 0 && x->vis_regions > 0;
-  if (s.visg) { s.hcap = 64; s.lds = fixed; s.max_grid = x->vis_regions; }
-  else { s.lds = fixed + (size_t)s.hcap * 4; s.max_grid = 0xffffffffu; }
-  if (s.visg && for_search && x->cfg.m_max0 <= 1024) {
-    s.w2 = walk2_policy();
-    if (s.w2 >= 0 && (s.w2 & 1)) {
-      // Bloom filter: the largest power of two that keeps the profile's resident waves (>= 2 KiB, <= 32 KiB), else none
-      const size_t waves = (s.w2 & 8) ? 4 : waves_per_cu_cap(x->quant);
-      const size_t budget = (160 * 1024) / waves;
-      size_t kb = 32;
-      if (policy().bloom_kb > 0) kb = (size_t)policy().bloom_kb;
-      else while (kb >= 2 && fixed + kb * 1024 > budget) kb >>= 1;
-      size_t p2 = 1; while (p2 * 2 <= kb) p2 *= 2;   // power of two
-      if (kb >= 2 && fixed + p2 * 1024 <= 160 * 1024) { s.bloom_words = (uint32_t)(p2 * 256); s.lds = fixed + p2 * 1024; }
-      else s.w2 &= ~1;
-    }
+  const SearchGeom g = w2 < 0 ? walk_geom(f, pol, ef) : row_walk_lds(f, pol, ef, (ev8 ? 96 * 4 : 0) + (filter == ROW_FILTER_8I ? (size_t)f.dim * 2 : 0));
+  s.family = w2 >= 0 ? COLTT_PLAN_WALK2 : COLTT_PLAN_ONE_WAVE;
+  s.ef = g.ef; s.ef_pad = g.ef_pad; s.hcap = g.hcap; s.lds = g.lds; s.vis_kind = hbm ? 0 : 32; s.w2 = w2; s.r8 = f.r8 && f.quant != COLTT_Q_F8;
+  s.ev8 = ev8; s.filter = filter;
+  if (hbm && w2 >= 0 && (w2 & 1)) {
+    // Bloom filter: the largest power of two that keeps the profile's resident waves (>= 2 KiB, <= 32 KiB), else none
+    const size_t budget = (160 * 1024) / ((w2 & 8) ? 4 : waves_per_cu_cap(pol, f.quant));
+    size_t kb = 32;
+    if (pol.bloom_kb > 0) kb = (size_t)pol.bloom_kb;
+    else while (kb >= 2 && g.lds + kb * 1024 > budget) kb >>= 1;
+    size_t p2 = 1; while (p2 * 2 <= kb) p2 *= 2;   // power of two
+    if (kb >= 2 && g.lds + p2 * 1024 <= 160 * 1024) { s.bloom_words = (uint32_t)(p2 * 256); s.lds = g.lds + p2 * 1024; }
+    else s.w2 &= ~1;
   }
-  if (!s.visg && for_search && !no_w2_lds && x->cfg.m_max0 <= 1024) {
-    // small ef: the same walk over the LDS hash (delta result set, adjacency-carried norms; no Bloom filter — the hash is on chip)
-    const int pol = walk2_lds_policy();
-    if (pol >= 0) { s.w2 = pol; s.w2_lds = true; }
-  }
-  s.ev8 = want8 && s.w2 >= 0;
   // The headline walk (LDS variant 4, eight-lane core, row filter over the quantised query) keeps its visited set at 16 bits per entry (vis16.hpp) where every
   // slot is representable: query + scratch + digit planes + result set + 16 KiB + the stash = 22 464 bytes at 768-d, ef 128 — SEVEN traversals per CU where the
   // 32-bit table (38 784 bytes) held four.  The capacity rule is the 32-bit table's: 3/4 of 8 192 entries.  COLTT_VIS16=0 keeps the 32-bit table (per call).
   // COLTT_VIS16_BUCKET_BITS (test knob) shrinks the table to 2^bits buckets and lifts the capacity rule, so that a small walk fills buckets, uses the stash and
   // overflows it.
-  const Policy pol = policy();
-  if (s.ev8 && s.qd8i && s.w2_lds && s.w2 == 4 && !s.visg && pol.vis16 && ef <= 128) {
+  if (filter == ROW_FILTER_8I && !hbm && pol.vis16 && ef <= 128) {   // (a filter over the LDS hash: variant 4 with the eight-lane core)
     const uint32_t bits = pol.vis16_bucket_bits > 0 ? (uint32_t)pol.vis16_bucket_bits : VIS16_BUCKET_BITS;
-    if (x->n <= ((uint64_t)1 << (VIS16_TAG_BITS + bits))) {
-      s.vis16 = true; s.v16_bits = bits;
+    if (f.slots <= ((uint64_t)1 << (VIS16_TAG_BITS + bits))) {
+      s.vis_kind = 16; s.v16_bits = bits;
       s.v16_limit = pol.vis16_bucket_bits > 0 ? 0xffffffu : ((8u << bits) >> 2) * 3;
-      s.lds = fixed + (size_t)vis16_table_words(bits) * 4 + VIS16_STASH * 4;
+      s.lds = g.lds - (size_t)g.hcap * 4 + (size_t)vis16_table_words(bits) * 4 + VIS16_STASH * 4;
     }
   }
-  return s;
-}
-
-// The walk over the 16-bit visited set is compiled for two waves per SIMD and its LDS fits seven times: all seven (COLTT_WAVES_PER_CU overrides here too).
-#ifndef COLTT_VIS16_WAVES_PER_CU
-#define COLTT_VIS16_WAVES_PER_CU 7
-#endif
-uint32_t resident_waves(const SearchGeom& sg, int quant) {
-  const size_t cap = (sg.w2 >= 0 && (sg.w2 & 8)) ? 4 : (sg.vis16 && policy().waves_per_cu <= 0) ? (size_t)COLTT_VIS16_WAVES_PER_CU : waves_per_cu_cap(quant);
-  return 256u * (uint32_t)std::max<size_t>(1, std::min<size_t>(cap, (160 * 1024) / sg.lds));
-}
-
-// Non-temporal row loads for the eight-lane walks (exact.hpp: row_ld): worth it when the row array is far larger than L2 + MALL, costly when later queries
-// would have found the rows there.  COLTT_ROWS_NT = 0 / 1 forces, COLTT_ROWS_NT_MIN_MB moves the threshold (default 12 GiB of rows: 768-d rows, same box — f16 0.5 M -24 %, 1 M -10 %,
-// 2 M -2 %, 4 M +0.8 %, 10 M +-0; f32 1 M -4 %, 3 M +0.7 %, 10 M +4.5 %: profiles/r06ag_nt_rows_ab.md).
-// The certified row filter of the eight-lane f32 cosine walks (hnsw_walk2.hpp: Group8FilterEval).  COLTT_ROW_FILTER = 0 / 1 forces (read per call: one index in
-// one process runs both kernels, tools/row_filter_ab.py); unset: on for the LDS-hash walk (ef <= 128, the measured instance: 10 M x 768, ef 128, 1.41 x in one
-// process, profiles/r07a_row_filter.md) where the row array is far larger than the caches: every row read is then an HBM read and the kernel sits at what the
-// memory system delivers, so bytes are time.
-// COLTT_ROW_FILTER_BITS = 8 / 16 / 8i picks the shadow a filtered launch reads (row_filter_bits); unset: the 8-bit one where the index keeps it.  An index keeps
-// what COLTT_ROW_SHADOW_BITS said when it was created; the kind it does not keep is served by the one it does.  8i (ROW_FILTER_8I) reads the 8-bit shadow
-// against the query quantised once per traversal: phase A is an integer sum (row_filter8i.hpp); it is what an unset knob takes over the 8-bit shadow
-// (COLTT_ROW_FILTER8I_DEFAULT; the measurement behind it: profiles/r10a_row_filter8i.md).
-#ifndef COLTT_ROW_FILTER8I_DEFAULT
-#define COLTT_ROW_FILTER8I_DEFAULT 1
-#endif
-int row_filter_bits(const Hnsw* x) {
-  const bool h8 = x->has_shadow8(), h16 = x->has_shadow16();
-  if (!h8 && !h16) return 0;
-  const int want = policy().row_filter_bits;
-  if (want == 16) return h16 ? 16 : 8;
-  if (want == 8) return h8 ? 8 : 16;
-  if (want == ROW_FILTER_8I) return h8 ? ROW_FILTER_8I : 16;
-  return h8 ? (COLTT_ROW_FILTER8I_DEFAULT ? ROW_FILTER_8I : 8) : 16;
-}
-bool row_filter_on(const Hnsw* x, bool vis_hbm) {
-  if (!x->has_shadow8() && !x->has_shadow16()) return false;
-  const Policy p = policy();
-  if (p.row_filter >= 0) return p.row_filter != 0;
-  if (vis_hbm) return false;   // the ef > 128 twins (HBM visited map) have not been timed against their unfiltered partners: COLTT_ROW_FILTER=1 only
-  // the SIZE rule of the non-temporal hint (not its forcing knob COLTT_ROWS_NT: an A/B of the hint must not toggle the filter too).  The threshold is
-  // inherited from that rule's measured crossover, the filter's own crossover on 1 M / 3 M has not been measured.
-  return (unsigned long long)x->n * (unsigned long long)x->stride >= ((unsigned long long)p.rows_nt_min_mb << 20);
-}
-bool rows_nt(const Hnsw* x) {
-  const Policy p = policy();
-  const unsigned long long bytes = (unsigned long long)x->n * (unsigned long long)x->stride, least = (unsigned long long)p.rows_nt_min_mb << 20;
-  const bool on = p.rows_nt >= 0 ? p.rows_nt != 0 : bytes >= least;
-  static const bool dbg = [] { const char* e = getenv("COLTT_DEBUG_ROWS_NT"); return e && *e == '1'; }();   // diagnostics: which twin a launch takes, and why
-  if (dbg) fprintf(stderr, "[rows_nt] slots=%llu stride=%zu row bytes=%llu threshold=%llu knob=%d -> %s\n", (unsigned long long)x->n, (size_t)x->stride, bytes, least, p.rows_nt, on ? "nt" : "default");
-  return on;
+  if (s.lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "hnsw_search: dim/ef need %zu B of LDS (> 160 KiB)", (size_t)s.lds);
+  // latency kernel for small batches.  Its LDS hash must never need the reset path, so it gets the largest table that fits beside the
+  // staging area (one workgroup per CU); if even that is too small for this ef the one-wave kernel (or the walk above) serves the call.
+  if (nq <= (pol.lat_knob_set ? pol.lat_max_nq : (uint32_t)COLTT_LAT_MAX_NQ_DEFAULT) && !(force & 1) &&
+      f.stride <= LAT_MAX_STRIDE /* else: rows too long to hold (or stage) 32 at a time */ &&
+      (f.stride >= COLTT_LAT_MIN_STRIDE || pol.lat_knob_set) /* short rows: not the latency kernel (unless asked for) */) {
+    // LDS: query + result set + exchange words + the staging area (32 padded rows) + the visited hash
+    // (line-transposed rows are evaluated out of the registers they land in: no staging area — hnsw_lat.hpp: lat_eval_chunk, TP != 0)
+    const size_t fixed = ((lat_q_floats((int)f.dim) * 4 + 15) & ~(size_t)15) + (size_t)s.ef_pad * 8 + sizeof(LatShared) + (s.r8 ? (size_t)0 : (size_t)LAT_ROWS * (f.stride + LAT_PAD));
+    uint32_t hcap = 32768; while (fixed + (size_t)hcap * 4 > 160 * 1024 && hcap > 1024) hcap /= 2;
+    if (fixed + (size_t)hcap * 4 <= 160 * 1024 && (hcap / 4) * 3 >= ef * 34u + 64u) {   // else: table too small to be sure
+      SearchPlan m{};
+      m.family = COLTT_PLAN_LATENCY; m.ef = s.ef; m.ef_pad = s.ef_pad; m.hcap = hcap; m.lds = fixed + (size_t)hcap * 4; m.vis_kind = 32; m.w2 = -1; m.r8 = s.r8;
+      m.rows8_launch = s.r8;   // the latency kernel reads the index's ONE row array in the layout it has: COLTT_EV8 does not choose here
+      // COLTT_LAT_SEQ=1: the sequential walk (search_level2 + LatEval) also for one-chunk rows — the A/B partner of the pipelined one.  COLTT_LAT_HELPERS =
+      // 1 .. 3 helper workgroups per walking one; OFF by default — exact, but 3-5 % slower than no helpers at all (profiles/r06f_latency_helpers_ab.md); not
+      // with the sequential walk.
+      m.lat_seq = pol.lat_seq || f.m_max0 > 32;
+      m.lat_helpers = m.lat_seq ? 0 : std::min(pol.lat_helpers, LAT_HELPERS_MAX);
+      m.per_cu = 1; m.grid = std::min<uint32_t>((uint32_t)nq, 256u);
+      s = m;
+      return COLTT_OK;
+    }
+  }
+  if (s.family == COLTT_PLAN_WALK2) {
+    s.nt = ev8 && rows_nt(f, pol);
+    if (filter) {   // (the binary16 kind has no per-slot (scale, error norm): its descent stays exact)
+      if (filter != 16 && (pol.row_filter_upper >= 0 ? pol.row_filter_upper != 0 : ROW_FILTER_UPPER_DEFAULT)) s.upper |= ROWF_UPPER_FILTER;
+      if (s.nt && (pol.descent_nt >= 0 ? pol.descent_nt == 0 : !DESCENT_NT_DEFAULT)) s.upper |= ROWF_UPPER_CACHED;
+    }
+    s.rows8_launch = ev8;
+    if (!walk2_shipped(hbm, s.w2)) return fail(COLTT_E_UNSUPPORTED, "hnsw_search: walk variant %d is not compiled into this build (COLTT_WALK2)", s.w2);
+  }
+  const uint32_t waves = resident_waves(pol, f.quant, s.lds, s.w2, s.vis_kind == 16);
+  s.per_cu = waves / 256u;
+  s.grid = std::min<uint32_t>((uint32_t)std::min<size_t>(nq, 0xffffffffu), waves);
+  return COLTT_OK;
 }
 }  // namespace hnsw
 }  // namespace coltt
@@ -769,13 +805,14 @@ namespace {
 // hnsw_walk2.hpp kernels: hnsw_search2.hip (launch_search2).
 
 template <int METRIC, int QUANT>
-int launch_search(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
+int launch_search(Hnsw* x, HCtx* c, const SearchPlan& sp, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
                   uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
-  auto kern = sg.visg ? hnsw_search_kernel<METRIC, QUANT, true> : hnsw_search_kernel<METRIC, QUANT, false>;
-  if constexpr (QUANT != Q_F8) { if (x->r8) kern = sg.visg ? hnsw_search_kernel<METRIC, QUANT, true, true> : hnsw_search_kernel<METRIC, QUANT, false, true>; }
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
-  kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
-                                        k, sg.ef, sg.ef_pad, sg.hcap, counter, oi, os, oc, stats,
+  const bool visg = sp.vis_kind == 0;
+  auto kern = visg ? hnsw_search_kernel<METRIC, QUANT, true> : hnsw_search_kernel<METRIC, QUANT, false>;
+  if constexpr (QUANT != Q_F8) { if (sp.r8) kern = visg ? hnsw_search_kernel<METRIC, QUANT, true, true> : hnsw_search_kernel<METRIC, QUANT, false, true>; }
+  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.lds));
+  kern<<<grid, 64, sp.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
+                                        k, sp.ef, sp.ef_pad, sp.hcap, counter, oi, os, oc, stats,
                                         x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
                                         x->w_vepoch.as<uint32_t>() + region_base);
   COLTT_HIP(hipGetLastError());
@@ -784,11 +821,10 @@ int launch_search(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32_
 
 // latency launch: one 4-wave workgroup per query in flight, at most one per CU
 template <int METRIC, int QUANT>
-int launch_search_lat(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
+int launch_search_lat(Hnsw* x, HCtx* c, const SearchPlan& sp, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
                       uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
   (void)region_base;
-  // COLTT_LAT_SEQ=1: the sequential walk (search_level2 + LatEval) also for one-chunk rows — the A/B partner of the pipelined one
-  const bool seq = policy().lat_seq || x->cfg.m_max0 > 32;
+  const bool seq = sp.lat_seq != 0;   // the sequential walk (search_level2 + LatEval): plan_search
   // the latency kernel reads the index's ONE row array in the layout it has (line-transposed: lines evaluated out of their registers; natural:
   // staged and transposed through LDS).  COLTT_EV8 chooses between distance cores over the same bytes in the THROUGHPUT kernels; here the layout
   // alone decides (the A/B partner is an index created with COLTT_ROWS8=0).  One kernel instance per (layout, walk): TP = the row's 128-byte lines
@@ -800,19 +836,17 @@ int launch_search_lat(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uin
   if constexpr (QUANT == Q_F8) kern = seq ? (lat_kern_t)hnsw_search_lat_kernel<METRIC, QUANT, LAT_TP_STAGED, true> : (lat_kern_t)hnsw_search_lat_kernel<METRIC, QUANT, LAT_TP_STAGED, false>;
   else {
     const int lines = gv.rows8 ? (int)(x->stride >> 7) : 0;
-    if (gv.rows8) x->ev8_launches.fetch_add(1);
     if (!gv.rows8) kern = seq ? (lat_kern_t)hnsw_search_lat_kernel<METRIC, QUANT, LAT_TP_STAGED, true> : (lat_kern_t)hnsw_search_lat_kernel<METRIC, QUANT, LAT_TP_STAGED, false>;
     else if (seq) kern = hnsw_search_lat_kernel<METRIC, QUANT, LAT_TP_R8_ANY, true>;
     else if (lines == 24) kern = hnsw_search_lat_kernel<METRIC, QUANT, 24, false>;
     else if (lines == 12) kern = hnsw_search_lat_kernel<METRIC, QUANT, 12, false>;
     else kern = hnsw_search_lat_kernel<METRIC, QUANT, LAT_TP_R8_ANY, false>;
   }
-  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
+  COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.lds));
   // Batches of at most LAT_MASTERS queries (the reference's one-query RPC above all) get helper workgroups that warm the XCD's L2 with the rows the walk
-  // will want next (hnsw_lat.hpp).  COLTT_LAT_HELPERS = 1 .. 3 per walking workgroup; OFF by default — exact, but 3-5 % slower than no helpers at all
-  // (profiles/r06f_latency_helpers_ab.md); not with the sequential walk.
+  // will want next (hnsw_lat.hpp; COLTT_LAT_HELPERS: plan_search).
   unsigned long long* mbox = nullptr;
-  const int helpers = seq ? 0 : std::min(policy().lat_helpers, LAT_HELPERS_MAX);
+  const int helpers = sp.lat_helpers;
   if (helpers > 0 && nq <= (uint32_t)LAT_MASTERS) {
     const size_t mb = (size_t)LAT_MASTERS * (LAT_HELPERS_MAX + 1) * 8;
     COLTT_TRY(c->w_mbox.reserve(mb));
@@ -820,35 +854,24 @@ int launch_search_lat(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uin
     mbox = c->w_mbox.as<unsigned long long>();
     grid = (uint32_t)LAT_MASTERS * (uint32_t)(helpers + 1);
   }
-  kern<<<grid, 256, sg.lds, c->stream>>>(gv, x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
-                                         k, sg.ef, sg.ef_pad, sg.hcap, counter, oi, os, oc, stats, mbox, helpers);
+  kern<<<grid, 256, sp.lds, c->stream>>>(gv, x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
+                                         k, sp.ef, sp.ef_pad, sp.hcap, counter, oi, os, oc, stats, mbox, helpers);
   COLTT_HIP(hipGetLastError());
   return COLTT_OK;
 }
 
-// Batches of at most COLTT_LAT_MAX_NQ queries (default below; COLTT_MW_MAX_NQ is the round-2 name of the knob) take the
-// 256-thread latency kernel (hnsw_lat.hpp).
-// Measured at 10 M x 768 f32, ef 128 (profiles/r03_latency.json): 1 query 1.04 ms against 1.43 ms on the one-wave kernel, 128 queries
-// 1.45 against 1.97 ms; beyond ~256 queries every CU already holds a workgroup and the one-wave kernel's 1024+ resident traversals win.
-#ifndef COLTT_LAT_MAX_NQ_DEFAULT
-#define COLTT_LAT_MAX_NQ_DEFAULT 256
-#endif
-#ifndef COLTT_LAT_MIN_STRIDE
-#define COLTT_LAT_MIN_STRIDE 1024   // bytes per stored row below which a lane pair streams the whole row in one burst anyway
-#endif
-uint32_t lat_max_nq() { const Policy p = policy(); return p.lat_knob_set ? p.lat_max_nq : (uint32_t)COLTT_LAT_MAX_NQ_DEFAULT; }
-
 int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t nq, uint32_t k, uint32_t ef_override,
                   uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_stats* stats, int force = 0) {
-  const bool force_single_wave = (force & 1) != 0;   // force: 1 = not the latency kernel, 2 = not the walk2 LDS-hash kernel (both after an err 8)
+  // argument checks, plan, lease, upload, launch by plan, read-back, counters by plan.  force: plan_search (a call re-run after an err 8)
   if (stats) std::memset(stats, 0, sizeof(*stats));
   if (nq == 0) return COLTT_OK;
   if (k == 0) return fail(COLTT_E_INVALID, "hnsw_search: k must be >= 1");
+  const Policy pol = policy();   // the ONE snapshot this call decides by
   uint64_t* d_oi = out_ids; float* d_os = out_scores; uint32_t* d_oc = out_counts;
   // small host-buffer calls: the work counter, the traversal counters and the three answer arrays live in ONE device block that
   // comes back in one copy through page-locked staging (layout: 256 B counter + stats | ids | scores | counts)
   const size_t pack_bytes = 256 + nq * k * 12 + nq * 4;
-  const bool packed = !on_device && pack_bytes <= SMALL_CALL_BYTES && nq * x->dim * 4 <= SMALL_CALL_BYTES && small_call_staging();
+  const bool packed = !on_device && pack_bytes <= SMALL_CALL_BYTES && nq * x->dim * 4 <= SMALL_CALL_BYTES && pol.staging;
   if (packed) {
     COLTT_TRY(c->w_pack.reserve(SMALL_CALL_BYTES + 256));
     COLTT_TRY(c->h_out.reserve(SMALL_CALL_BYTES + 256));
@@ -867,32 +890,22 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
     COLTT_HIP(hipStreamSynchronize(c->stream));
     return COLTT_OK;
   }
-  uint32_t ef = std::max<uint32_t>(ef_override ? ef_override : (uint32_t)x->cfg.ef, k);  // gomath.MaxInt(ef, k), hnsw.go:258
-  if (ef > 4096) return fail(COLTT_E_UNSUPPORTED, "hnsw_search: ef=%u > 4096", ef);
-  if (wants_visg(ef)) COLTT_TRY(ensure_visg(x));  // lazily: N bytes x <= 2048 regions are only worth having for ef > 128
-  SearchGeom sg = search_geom(x, ef, true, (force & 2) != 0);
-  if (sg.lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "hnsw_search: dim/ef need %zu B of LDS (> 160 KiB)", sg.lds);
-  // latency kernel for small batches.  Its LDS hash must never need the reset path, so it gets the largest table that fits beside the
-  // staging area (one workgroup per CU); if even that is too small for this ef the one-wave kernel serves the call.
-  bool mw = nq <= lat_max_nq() && !force_single_wave;
-  if (mw) {
-    SearchGeom m = sg; m.w2 = -1; m.w2_lds = false; m.bloom_words = 0; m.visg = false; m.vis16 = false;
-    // LDS: query + result set + exchange words + the staging area (32 padded rows) + the visited hash
-    // (line-transposed rows are evaluated out of the registers they land in: no staging area — hnsw_lat.hpp: lat_eval_chunk, TP != 0)
-    const bool lat_r8 = x->r8 && x->quant != COLTT_Q_F8;
-    const size_t fixed = ((lat_q_floats((int)x->dim) * 4 + 15) & ~(size_t)15) + (size_t)m.ef_pad * 8 + sizeof(LatShared) + (lat_r8 ? (size_t)0 : (size_t)LAT_ROWS * (x->stride + LAT_PAD));
-    if (x->stride > LAT_MAX_STRIDE) mw = false;               // rows too long to hold (or stage) 32 at a time
-    else if (x->stride < COLTT_LAT_MIN_STRIDE && !policy().lat_knob_set) mw = false;   // short rows: the one-wave kernel (unless asked for)
-    else {
-      m.hcap = 32768; while (fixed + (size_t)m.hcap * 4 > 160 * 1024 && m.hcap > 1024) m.hcap /= 2;
-      m.lds = fixed + (size_t)m.hcap * 4;
-      if (m.lds > 160 * 1024 || (m.hcap / 4) * 3 < ef * 34u + 64u) mw = false;        // table too small to be sure: one-wave kernel
-    }
-    if (mw) sg = m;
+  const uint32_t ef = std::max<uint32_t>(ef_override ? ef_override : (uint32_t)x->cfg.ef, k);
+  if (ef <= 4096 && wants_visg(pol, ef)) COLTT_TRY(ensure_visg(x, pol));  // lazily: N bytes x <= 2048 regions are only worth having for ef > 128
+  const PlanFacts facts = plan_facts(x);
+  SearchPlan sp;
+  const int plan_rc = plan_search(facts, pol, nq, k, ef, force, sp);
+  const bool mw = sp.family == COLTT_PLAN_LATENCY, w2 = sp.family == COLTT_PLAN_WALK2, v16 = sp.vis_kind == 16;
+  static const bool dbg_nt = [] { const char* e = getenv("COLTT_DEBUG_ROWS_NT"); return e && *e == '1'; }();   // diagnostics: which twin a walk2 launch takes, and why
+  if (dbg_nt && w2) {
+    const unsigned long long bytes = (unsigned long long)facts.slots * (unsigned long long)facts.stride, least = (unsigned long long)pol.rows_nt_min_mb << 20;
+    fprintf(stderr, "[rows_nt] slots=%llu stride=%zu row bytes=%llu threshold=%llu knob=%d -> %s\n", (unsigned long long)facts.slots, (size_t)facts.stride, bytes, least, pol.rows_nt,
+            rows_nt(facts, pol) ? "nt" : "default");
   }
-  uint32_t grid = mw ? std::min<uint32_t>((uint32_t)nq, 256u) : std::min<uint32_t>((uint32_t)std::min<size_t>(nq, 0xffffffffu), resident_waves(sg, x->quant));
+  COLTT_TRY(plan_rc);
+  uint32_t grid = sp.grid;
   RegionLease lease;
-  if (sg.visg) { acquire_regions(x, grid, lease); grid = lease.count; }
+  if (sp.vis_kind == 0) { acquire_regions(x, grid, lease); grid = lease.count; }
   const float* d_q = queries;
   if (!on_device) {
     COLTT_TRY(c->w_qraw.reserve(nq * x->dim * 4));
@@ -908,10 +921,11 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
   unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(misc + 16);
   COLTT_TRY(prep_queries_any(x, c, d_q, nq, reinterpret_cast<uint32_t*>(misc)));   // ... which also clears the 256 bytes of counters (no memset of their own)
   COLTT_HIP(hipEventRecord(c->ev0, c->stream));
+  if (sp.rows8_launch) x->ev8_launches.fetch_add(1);
   int rc;
-#define COLTT_LS_ARGS x, c, sg, grid, lease.base, (uint32_t)nq, k, counter, d_oi, d_os, d_oc, d_stats
+#define COLTT_LS_ARGS x, c, sp, grid, lease.base, (uint32_t)nq, k, counter, d_oi, d_os, d_oc, d_stats
 #define COLTT_LS(Q) rc = mw ? (x->metric == COLTT_COSINE ? launch_search_lat<M_COS, Q>(COLTT_LS_ARGS) : launch_search_lat<M_L2, Q>(COLTT_LS_ARGS)) \
-                     : sg.w2 >= 0 ? launch_search2(COLTT_LS_ARGS) /* hnsw_search2.hip: the same dispatch over its own kernels */ \
+                     : w2 ? launch_search2(COLTT_LS_ARGS) /* hnsw_search2.hip: the same dispatch over its own kernels */ \
                             : (x->metric == COLTT_COSINE ? launch_search<M_COS, Q>(COLTT_LS_ARGS) : launch_search<M_L2, Q>(COLTT_LS_ARGS))
   COLTT_DISPATCH_QUANT(x->quant, COLTT_LS)
 #undef COLTT_LS
@@ -948,7 +962,7 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
     static const char* nm_l[8] = {"pop+publish", "adjacency", "visited+fetch+stage", "eval", "barrier2+admission", "-", "prologue(upper levels)", "-"};
     const char* const* nm = mw ? nm_l : nm_w;
     double tot = 0; for (int i = 0; i < 8; i++) tot += (double)h_pt[i];
-    fprintf(stderr, "[phase] nq=%zu ef=%u visg=%d:", nq, sg.ef, (int)sg.visg);
+    fprintf(stderr, "[phase] nq=%zu ef=%u visg=%d:", nq, sp.ef, (int)(sp.vis_kind == 0));
     for (int i = 0; i < 8; i++) fprintf(stderr, " %s %.1f%%", nm[i], 100.0 * (double)h_pt[i] / tot);
     fprintf(stderr, "  | ticks/query %.0f\n", tot / (double)nq);
   }
@@ -957,21 +971,20 @@ int search_common(Hnsw* x, HCtx* c, const float* queries, bool on_device, size_t
   (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
   x->last_ms.store(ms);
   {   // what this launch kept its visited set in, and how many traversals per CU it kept resident (the grid rule's figure; the 16-bit launches: the runtime's too)
-    const bool v16 = !mw && sg.w2 >= 0 && c->v16_launch;
-    uint32_t per_cu = mw ? 1u : resident_waves(sg, x->quant) / 256u;
+    uint32_t per_cu = sp.per_cu;
     if (v16 && c->occ_per_cu > 0) per_cu = std::min<uint32_t>(per_cu, (uint32_t)c->occ_per_cu);
-    x->last_vis_kind.store(sg.visg ? 0 : (v16 ? 16 : 32)); x->last_per_cu.store(per_cu); x->last_grid.store(grid);
+    x->last_vis_kind.store(sp.vis_kind); x->last_per_cu.store(per_cu); x->last_grid.store(grid);
     x->last_stash_max.store(v16 ? h_stats[16] : 0); x->last_visited_max.store(v16 ? h_stats[17] : 0);
     if (v16) x->v16_launches.fetch_add(1);
   }
   if (mw && (h_stats[4] & 8ull))  // the multi-wave kernel's visited table would have needed a reset: same call on the single-wave kernel
     return search_common(x, c, queries, on_device, nq, k, ef_override, out_ids, out_scores, out_counts, stats, force | 1);
-  if (sg.w2_lds && (h_stats[4] & 8ull))  // same for the walk2 kernel with the LDS hash: hnsw_dev.hpp:search_level has the reset-and-reseed path
+  if (w2 && sp.vis_kind != 0 && (h_stats[4] & 8ull))  // same for the walk2 kernel with the LDS hash: hnsw_dev.hpp:search_level has the reset-and-reseed path
     return search_common(x, c, queries, on_device, nq, k, ef_override, out_ids, out_scores, out_counts, stats, force | 3);
   if (h_stats[4]) return fail(COLTT_E_DEVICE, "hnsw_search: traversal watchdog tripped (code %llu)", h_stats[4]);
   if (stats) { stats->n_dist = h_stats[0]; stats->n_exp = h_stats[1]; stats->n_hops = h_stats[2]; stats->n_visit_resets = h_stats[3]; }
-  if (c->flt_launch && sg.w2 >= 0 && !mw) { x->flt_launches.fetch_add(1); x->flt_rejected.fetch_add(h_stats[6]); x->flt_f32_rows.fetch_add(h_stats[7]); x->flt_shadow_rows.fetch_add(h_stats[5]); }
-  if (c->flt_launch && c->upper_launch && sg.w2 >= 0 && !mw) { x->flt_up_launches.fetch_add(1); x->flt_up_shadow_rows.fetch_add(h_stats[18]); x->flt_up_rejected.fetch_add(h_stats[19]); x->flt_up_f32_rows.fetch_add(h_stats[20]); }   // (a call re-run after err 8 returned above: only the launch that answered counts)
+  if (sp.filter) { x->flt_launches.fetch_add(1); x->flt_rejected.fetch_add(h_stats[6]); x->flt_f32_rows.fetch_add(h_stats[7]); x->flt_shadow_rows.fetch_add(h_stats[5]); }
+  if (sp.filter && (sp.upper & ROWF_UPPER_FILTER)) { x->flt_up_launches.fetch_add(1); x->flt_up_shadow_rows.fetch_add(h_stats[18]); x->flt_up_rejected.fetch_add(h_stats[19]); x->flt_up_f32_rows.fetch_add(h_stats[20]); }   // (a call re-run after err 8 returned above: only the launch that answered counts)
   return COLTT_OK;
 }
 
@@ -1105,10 +1118,10 @@ bool pq_geom(Hnsw* x, uint32_t ef, bool force_hbm, PqGeom& out, uint32_t filt_ca
                      + (filt_cap ? (size_t)((filt_cap + 63u) & ~63u) * 8 : 0);                                         // | R
   if (fixed > 160 * 1024) return false;
   const bool hbm_ok = x->vis_stride != 0 && x->vis_regions > 0;
-  // LDS hash: as search_geom sizes it; it must never need the reset path (err 8 -> the call is re-run over the byte map)
+  // LDS hash: as walk_geom sizes it; it must never need the reset path (err 8 -> the call is re-run over the byte map)
   uint32_t hcap = std::min<uint32_t>(32768u, std::max<uint32_t>(8192u, next_pow2(ef * 48u)));
   const bool lds_fits = fixed + (size_t)hcap * 4 <= 160 * 1024;
-  if (!force_hbm && !(wants_visg(ef) && hbm_ok) && lds_fits) { s.variant = 0; s.vis_words = hcap; s.lds = fixed + (size_t)hcap * 4; }
+  if (!force_hbm && !(wants_visg(policy(), ef) && hbm_ok) && lds_fits) { s.variant = 0; s.vis_words = hcap; s.lds = fixed + (size_t)hcap * 4; }
   else {
     if (!hbm_ok) return false;
     s.variant = 2; s.vis_words = 0; s.lds = fixed;
@@ -1234,9 +1247,10 @@ int launch_pq_rerank(Hnsw* x, HCtx* c, const PqGeom& sg, uint32_t q0, uint32_t n
 
 // the geometry of one walk at ef, as every entry point decides it: the LDS hash unless the policy, the caller (force_hbm) or the table's size says the byte map
 int pq_walk_geom(Hnsw* x, uint32_t ef, bool force_hbm, uint32_t fcap, PqGeom& sg) {
-  if (wants_visg(ef) || force_hbm) COLTT_TRY(ensure_visg(x));
+  const Policy pol = policy();
+  if (wants_visg(pol, ef) || force_hbm) COLTT_TRY(ensure_visg(x, pol));
   bool have = pq_geom(x, ef, force_hbm, sg, fcap);
-  if (!have && !force_hbm) { COLTT_TRY(ensure_visg(x)); have = pq_geom(x, ef, true, sg, fcap); }   // no room for the LDS hash beside the table: the byte map
+  if (!have && !force_hbm) { COLTT_TRY(ensure_visg(x, pol)); have = pq_geom(x, ef, true, sg, fcap); }   // no room for the LDS hash beside the table: the byte map
   if (!have) return fail(COLTT_E_UNSUPPORTED, "hnsw_pq_search: dim %u / ef %u / %u sub-vectors need more than the CU's 160 KiB of LDS", x->dim, ef, x->pq_shape.m);
   return COLTT_OK;
 }
@@ -1409,7 +1423,7 @@ int launch_build(Hnsw* x, const SearchGeom& sg, uint32_t base, uint32_t count, c
   const size_t lds = diverse ? ext_off + (((size_t)x->dim * 4 + 15) & ~(size_t)15) + 2 * 64 * 8 : sg.lds;
   if (lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "hnsw insert: dim/efConstruction need %zu B of LDS", lds);
   COLTT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(waves_per_cu_cap(QUANT), (160 * 1024) / lds));
+  const uint32_t per_cu = resident_waves(policy(), QUANT, lds) / 256u;
   uint32_t grid = std::min<uint32_t>({count, 256u * per_cu, sg.max_grid});
   kern<<<grid, 64, lds, x->stream>>>(x->view(), x->entry, x->entry_level, base, count, d_levels, (uint32_t)x->cfg.m,
                                      sg.ef, sg.ef_pad, sg.hcap, x->cap, counter, req_count, req, head, stats,
@@ -1453,6 +1467,7 @@ int insert_core(Hnsw* x, const uint64_t* ids, uint64_t first_id, const float* d_
   const uint64_t first_new = x->n;
   const PqNbrPatch patch = pq_nbr_patch_begin(x, (uint64_t)n * (uint64_t)x->cfg.m);
   const uint32_t efc = (uint32_t)x->cfg.ef_construction;
+  const Policy pol = policy();
   COLTT_TRY(x->w_misc.reserve(64));
   uint32_t* counter = x->w_misc.as<uint32_t>();
   uint32_t* req_count = counter + 1;
@@ -1469,8 +1484,8 @@ int insert_core(Hnsw* x, const uint64_t* ids, uint64_t first_id, const float* d_
     for (uint32_t j = 0; j < b; j++) up += first ? 0 : (uint64_t)levels[i + j];
     const uint64_t base = x->n;
     COLTT_TRY(x->reserve(base + b, x->n_upper + up));
-    if (wants_visg(efc)) COLTT_TRY(ensure_visg(x));  // (re)sized here: the slot capacity may just have grown
-    const SearchGeom sg = search_geom(x, efc);
+    if (wants_visg(pol, efc)) COLTT_TRY(ensure_visg(x, pol));  // (re)sized here: the slot capacity may just have grown
+    const SearchGeom sg = walk_geom(plan_facts(x), pol, efc);
     if (sg.lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "hnsw insert: dim/efConstruction need %zu B of LDS", sg.lds);
     // per-slot tables of the batch.  Host mirrors (h_levels, h_upper_off, h_ids, id2slot, h_del) are committed only after
     // the device work of the batch has succeeded: a failed batch leaves the index exactly as it was (slots >= n unreferenced).
@@ -2471,7 +2486,7 @@ int coltt_hnsw_pq_attach(coltt_handle_t h, coltt_handle_t pq) {
   x->pq_shape = sh; x->pq_row = row; x->pq_done = 0; x->pq_on = true;
   if (x->pq_codes.p) COLTT_HIP(hipMemsetAsync(x->pq_codes.p, 0, x->pq_codes.cap, x->stream));
   int rc = sync_pq(x.get());
-  if (rc == COLTT_OK && x->vis_stride != 0) rc = ensure_visg(x.get());   // (exclusive lock: no traversal holds a region) 2048 -> 3072 regions for the table walk
+  if (rc == COLTT_OK && x->vis_stride != 0) rc = ensure_visg(x.get(), policy());   // (exclusive lock: no traversal holds a region) 2048 -> 3072 regions for the table walk
   if (rc != COLTT_OK) x->pq_on = false;
   return rc;
 }
@@ -2579,6 +2594,24 @@ int coltt_hnsw_visited_stats(coltt_handle_t h, int32_t* out_kind, uint32_t* out_
   if (out_launches16) *out_launches16 = x->v16_launches.load();
   if (out_stash_max) *out_stash_max = x->last_stash_max.load();
   if (out_visited_max) *out_visited_max = x->last_visited_max.load();
+  return COLTT_OK;
+}
+
+int coltt_hnsw_search_plan_host(const coltt_hnsw_plan_facts* facts, size_t nq, uint32_t k, uint32_t ef_override, int force, coltt_hnsw_search_plan* out) {
+  if (!facts || !out) return fail(COLTT_E_INVALID, "hnsw_search_plan_host: NULL facts or out");
+  if (nq == 0 || ef_override == 0) return fail(COLTT_E_INVALID, "hnsw_search_plan_host: nq and ef_override must be >= 1 (the index's default ef is not among the facts)");
+  SearchPlan sp;
+  const int rc = plan_search(*facts, policy(), nq, k, ef_override, force, sp);
+  *out = rc == COLTT_OK ? sp : SearchPlan{};
+  return rc;
+}
+
+int coltt_hnsw_search_plan_facts(coltt_handle_t h, coltt_hnsw_plan_facts* out_facts) {
+  auto x = lookup<Hnsw>(h);
+  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_search_plan_facts: unknown handle");
+  if (!out_facts) return fail(COLTT_E_INVALID, "hnsw_search_plan_facts: NULL out");
+  ReadLock g(x->rw);
+  *out_facts = plan_facts(x.get());
   return COLTT_OK;
 }
 

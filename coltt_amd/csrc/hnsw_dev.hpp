@@ -214,7 +214,7 @@ __device__ __forceinline__ bool filter_allows(const FilterView& f, uint32_t slot
 // vertices whose distance the level-0 walk holds.  r[0..len) ascending, in LDS beside the result set.
 struct FiltSet { unsigned long long* r; uint32_t len, cap; FilterView f; };
 // coltt_hnsw_search_filtered_batch, WALK: one query's walk as the single-filter call would run it — its filter, its breadth ef, the
-// LDS geometry search_geom gives that ef (ef_pad, hcap), and the batch row it reads its query from and writes its answer to.
+// LDS geometry walk_geom gives that ef (ef_pad, hcap), and the batch row it reads its query from and writes its answer to.
 struct FiltQuery { const uint32_t* bits; uint32_t slots, ef, ef_pad, hcap, row, pad_; };
 // coltt_hnsw_pq_search_filtered_batch, WALK: the same for the walk over the quantiser's codes — the geometry is pq_geom's for that ef_walk and the
 // capacity fcap of the query's allowed set R (hnsw_index.hpp: pq_filt_cap); vis_words: the LDS hash's words, 0 over the byte map.  The walk addresses its table, survivors

@@ -344,10 +344,11 @@ int filter_search_common(Hnsw* x, HCtx* c, const HnswFilter* f, const float* que
   uint32_t grid = 0;
   RegionLease lease;
   if (path == COLTT_FILTER_WALK) {
-    if (wants_visg(ef_walk)) COLTT_TRY(ensure_visg(x));
-    sg = search_geom(x, ef_walk, false, true, k);   // the one-wave walk (hnsw_dev.hpp: search_level) over the LDS hash or the HBM byte map
+    const Policy pol = policy();
+    if (wants_visg(pol, ef_walk)) COLTT_TRY(ensure_visg(x, pol));
+    sg = walk_geom(plan_facts(x), pol, ef_walk, k);   // the one-wave walk (hnsw_dev.hpp: search_level) over the LDS hash or the HBM byte map
     if (sg.lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "%s: dim/ef/k need %zu B of LDS (> 160 KiB)", who, sg.lds);
-    grid = std::min<uint32_t>((uint32_t)nq, resident_waves(sg, x->quant));
+    grid = std::min<uint32_t>((uint32_t)nq, resident_waves(pol, x->quant, sg.lds));
     if (sg.visg) { acquire_regions(x, grid, lease); grid = lease.count; }
   }
   uint32_t* counter;
@@ -369,7 +370,7 @@ int filter_search_common(Hnsw* x, HCtx* c, const HnswFilter* f, const float* que
 }
 
 // ---- coltt_hnsw_search_filtered_batch: a filter per query.  Row i is the single-filter call on query i alone: its path from its own filter's
-// allowed count (filter_path), its walk at the geometry search_geom gives its ef_walk, its exact scan chunked by launch_filter_exact's rule (the
+// allowed count (filter_path), its walk at the geometry walk_geom gives its ef_walk, its exact scan chunked by launch_filter_exact's rule (the
 // answer is a pure top-k, so the chunking cannot change it).  One call launches at most two walks (LDS hash, HBM byte map), one scan, one select.
 int filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, const float* queries, size_t nq, uint32_t k, uint32_t ef_override,
                         int mode, uint64_t* out_ids, float* out_scores, uint32_t* out_counts, int32_t* out_paths, coltt_hnsw_filter_stats* st) {
@@ -382,16 +383,18 @@ int filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, co
   FiltRoute rt;
   filter_route(x, fl, nq, ef, mode, out_paths, out_counts, st, rt);
   if (rt.none()) return COLTT_OK;
-  // the walks: each query's geometry is search_geom(x, ef_walk, false, true, k), the one-wave walk (hnsw_dev.hpp: search_level) over the LDS hash
+  // the walks: each query's geometry is walk_geom(facts, policy, ef_walk, k), the one-wave walk (hnsw_dev.hpp: search_level) over the LDS hash
   // or the HBM byte map; split by visited set
+  const Policy pol = policy();
   for (uint32_t i : rt.walk_q)
-    if (wants_visg(rt.efw[i])) { COLTT_TRY(ensure_visg(x)); break; }
+    if (wants_visg(pol, rt.efw[i])) { COLTT_TRY(ensure_visg(x, pol)); break; }
+  const PlanFacts facts = plan_facts(x);
   std::map<uint32_t, SearchGeom> geoms;
   std::vector<FiltQuery> wq[2];
   SearchGeom wmax[2]{};
   for (uint32_t i : rt.walk_q) {
     auto it = geoms.find(rt.efw[i]);
-    if (it == geoms.end()) it = geoms.emplace(rt.efw[i], search_geom(x, rt.efw[i], false, true, k)).first;
+    if (it == geoms.end()) it = geoms.emplace(rt.efw[i], walk_geom(facts, pol, rt.efw[i], k)).first;
     const SearchGeom& sg = it->second;
     if (sg.lds > 160 * 1024) return fail(COLTT_E_UNSUPPORTED, "%s: dim/ef/k need %zu B of LDS (> 160 KiB)", who, sg.lds);
     const int v = sg.visg ? 1 : 0;
@@ -408,7 +411,7 @@ int filter_batch_common(Hnsw* x, HCtx* c, const std::vector<HnswFilter*>& fl, co
   COLTT_TRY(filter_upload(c, wq[0].data(), w0_bytes, wq[1].data(), wq[1].size() * sizeof(FiltQuery), ep, nq, k, blob, d_desc, o));
   uint32_t grid[2] = {0, 0};
   RegionLease lease;
-  for (int v = 0; v < 2; v++) if (!wq[v].empty()) grid[v] = std::min<uint32_t>((uint32_t)wq[v].size(), resident_waves(wmax[v], x->quant));
+  for (int v = 0; v < 2; v++) if (!wq[v].empty()) grid[v] = std::min<uint32_t>((uint32_t)wq[v].size(), resident_waves(pol, x->quant, wmax[v].lds));
   if (grid[1]) { acquire_regions(x, grid[1], lease); grid[1] = lease.count; }
   uint32_t* counters;   // [0]: the LDS-hash walk's work counter, [1]: the byte-map walk's
   unsigned long long* d_stats;

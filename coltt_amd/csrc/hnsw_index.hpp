@@ -26,9 +26,6 @@ struct HCtx {
   DevBuf w_mbox;                   // latency kernel: the walking workgroups' hint mailboxes (hnsw_lat.hpp: cache-warming helper workgroups)
   DevBuf w_fdesc;                  // filtered batch: the walks' per-query descriptors, the exact path's queries and tiles
   PinnedBuf h_in, h_out;   // small calls: see PinnedBuf
-  bool flt_launch = false;   // launch_search2 took the row-filter twin for the call in flight
-  bool upper_launch = false; // ... with its greedy descent through the certified filter (COLTT_ROW_FILTER_UPPER)
-  bool v16_launch = false;   // ... and that twin walks over the 16-bit visited set (vis16.hpp)
   const void* occ_kern = nullptr; size_t occ_lds = 0; int occ_per_cu = 0;   // the runtime's occupancy answer for the last (kernel, LDS) asked about
   int init() {  // the caller has selected the index's device
     COLTT_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -162,9 +159,12 @@ struct Hnsw : Object {
   }
 };
 
-// The launch geometry of one row walk at one ef (search_geom).
-struct SearchGeom { uint32_t ef, ef_pad, hcap; size_t lds; bool visg; uint32_t max_grid; int w2 = -1; uint32_t bloom_words = 0; bool w2_lds = false; bool ev8 = false; bool qd8i = false;
-                    bool vis16 = false; uint32_t v16_bits = 0, v16_limit = 0; };   // vis16: the LDS visited set at 16 bits per entry (vis16.hpp): log2 of its bucket count, the capacity rule's limit  // w2: hnsw_walk2.hpp variant (OPT bits | 8 = deep profile), -1 = hnsw_dev.hpp:search_level
+// What the search decisions read of an index, and what they decide (include/coltt_gpu.h; hnsw.hip: plan_search).
+typedef coltt_hnsw_plan_facts PlanFacts;
+typedef coltt_hnsw_search_plan SearchPlan;
+
+// The LDS layout of the one-wave walk (hnsw_dev.hpp: search_level) at one ef: what the builder and the filtered drivers launch (walk_geom).
+struct SearchGeom { uint32_t ef, ef_pad, hcap; size_t lds; bool visg; uint32_t max_grid; };
 
 // Lease a contiguous run of visited-set regions for one search launch: `want` if a free run that long exists, else the
 // longest free run; blocks while every region is out.  Released by the RegionLease destructor.
@@ -209,15 +209,17 @@ inline uint32_t pq_filt_cap(uint32_t ef, uint32_t k, uint32_t rerank) { return r
 int prep_queries_any(Hnsw* x, HCtx* c, const float* d_qraw, size_t nq, uint32_t* zero64 = nullptr);
 // ids[i] += base on `stream`: the answers of a dense-id index whose ids do not start at 0
 void add_base(hipStream_t stream, uint64_t* ids, size_t n, uint64_t base);
-int ensure_visg(Hnsw* x);
+int ensure_visg(Hnsw* x, const Policy& pol);
 void acquire_regions(Hnsw* x, uint32_t want, RegionLease& out);
-bool wants_visg(uint32_t ef);
-// filt_k > 0: the filtered walk's allowed set (k rounded up to 64 entries) sits beside the result set (hnsw_kernels.hpp: search_one_wave)
-SearchGeom search_geom(Hnsw* x, uint32_t ef, bool for_search = false, bool no_w2_lds = false, uint32_t filt_k = 0);
-uint32_t resident_waves(const SearchGeom& sg, int quant);
-bool rows_nt(const Hnsw* x);
-bool row_filter_on(const Hnsw* x, bool vis_hbm);
-int row_filter_bits(const Hnsw* x);
+// The search decisions: pure functions of (facts, knob snapshot).  A caller takes ONE policy() snapshot per call and passes it down.
+PlanFacts plan_facts(const Hnsw* x);
+bool wants_visg(const Policy& pol, uint32_t ef);   // does this ef want the HBM visited set (whether the workspace could be had is PlanFacts::vis_ready)
+// allowed > 0: the filtered walk's allowed set (rounded up to 64 entries) sits beside the result set (hnsw_kernels.hpp: search_one_wave)
+SearchGeom walk_geom(const PlanFacts& f, const Policy& pol, uint32_t ef, uint32_t allowed = 0);
+uint32_t resident_waves(const Policy& pol, int quant, size_t lds, int w2 = -1, bool vis16 = false);
+// the hnsw_walk2.hpp variants the library carries over the HBM map / the LDS hash (hnsw_search2.hip instantiates exactly these)
+inline bool walk2_shipped(bool hbm, int w2) { return hbm ? (w2 == 6 || w2 == 7) : w2 == 4; }
+int plan_search(const PlanFacts& f, const Policy& pol, size_t nq, uint32_t k, uint32_t ef, int force, SearchPlan& out);
 int ensure_pq_nbr(Hnsw* x, hipStream_t stream, bool* use);
 int pq_walk_geom(Hnsw* x, uint32_t ef, bool force_hbm, uint32_t fcap, PqGeom& sg);
 int launch_pq_walk(Hnsw* x, HCtx* c, const PqGeom& sg, bool nbr, uint32_t grid, uint32_t region_base, const unsigned short* lut, uint32_t nq, uint32_t k,
@@ -230,7 +232,7 @@ int pq_search_filtered_walk(Hnsw* x, HCtx* c, const FilterView& fv, const float*
                             uint64_t* out_ids, float* out_scores, uint32_t* out_counts, coltt_hnsw_stats* stats, uint64_t* out_n_exact);
 
 // ---- hnsw_search2.hip
-int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
+int launch_search2(Hnsw* x, HCtx* c, const SearchPlan& sp, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
                    uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats);
 
 }  // namespace hnsw

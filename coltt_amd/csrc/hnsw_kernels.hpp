@@ -167,7 +167,7 @@ void hnsw_search2_kernel(GraphView g, int32_t entry, int32_t entry_level,
   size_t off = ((size_t)g.dim * 4 + 15) & ~(size_t)15;
   w.qs = reinterpret_cast<float*>(smem);
   w.qp = nullptr; w.scr = nullptr;
-  if constexpr (EV8) {   // [query in rows8 order | scratch] then the result set (search_geom adds the same bytes); no natural-order copy
+  if constexpr (EV8) {   // [query in rows8 order | scratch] then the result set (plan_search adds the same bytes); no natural-order copy
     w.qp = w.qs; w.qs = nullptr;
     w.scr = reinterpret_cast<uint32_t*>(smem + off);
     off += 96 * 4;
@@ -289,7 +289,7 @@ void hnsw_search2_rowfilter_kernel(GraphView g, int32_t entry, int32_t entry_lev
   w.qp = reinterpret_cast<float*>(smem); w.qs = nullptr;   // [query in rows8 order | scratch | result set | visited hash or Bloom filter], as hnsw_search2_kernel<.., EV8>
   w.scr = reinterpret_cast<uint32_t*>(smem + off);
   off += 96 * 4;
-  [[maybe_unused]] uint8_t* qd = nullptr;   // BITS == ROW_FILTER_8I: the query's two digit planes between the scratch and the result set (search_geom: qd_bytes)
+  [[maybe_unused]] uint8_t* qd = nullptr;   // BITS == ROW_FILTER_8I: the query's two digit planes between the scratch and the result set (plan_search adds the same bytes)
   if constexpr (BITS == ROW_FILTER_8I) { qd = smem + off; off += (size_t)g.dim * 2; }
   w.res0 = reinterpret_cast<unsigned long long*>(smem + off);
   w.ef_pad = ef_pad;

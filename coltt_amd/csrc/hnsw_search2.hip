@@ -13,108 +13,73 @@ using namespace coltt::hnsw;
 
 namespace {
 
-// What the prologue of a row-filter launch does unless COLTT_DESCENT_NT / COLTT_ROW_FILTER_UPPER say otherwise.  Measured on 10 M x 768, ef 128, 10 000 queries
-// per launch, four sides alternating in one process (tools/descent_filter_ab.py; profiles/r12a_descent_filter.md): cacheable descent loads 9.06 -> 8.76 ms
-// (+3.4 %); the filtered descent on top of them 8.80 ms — it rejects 90 % of the 116 evaluations above level 0 and asks for a third of the bytes, but with the
-// top of the graph served from cache those bytes were no longer HBM's, and a hop now waits for two dependent phases instead of one.
-constexpr bool DESCENT_NT_DEFAULT = false;         // the entrypoint's and the descent's rows are loaded cacheable: every query of a launch reads them
-constexpr bool ROW_FILTER_UPPER_DEFAULT = false;   // the greedy descent evaluates every listed neighbour exactly
+typedef void (*kern_t)(GraphView, int32_t, int32_t, const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*,
+                       uint64_t*, float*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*);
+typedef void (*fkern_t)(GraphView, int32_t, int32_t, const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*,
+                        uint64_t*, float*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*, uint32_t);   // the row-filter twins: + how the prologue descends
 
-// hnsw_walk2.hpp kernels: the shipped variant (and its Bloom-less twin for geometries whose LDS has no room for the filter).
+// The instances of one shipped walk (profile, variant, visited set), each named once.  The distance core: eight lanes per row (with non-temporal row loads
+// or not: exact.hpp: row_ld), the pair-owned core over line-transposed rows, the pair-owned core over natural rows.
+template <int METRIC, int QUANT, int PROF, int OPT, int VIS>
+kern_t walk_instance(const SearchPlan& sp) {
+  if constexpr (QUANT != Q_F8) {
+    if (sp.ev8) return sp.nt ? hnsw_search2_kernel<METRIC, QUANT, PROF, OPT, VIS, false, true, false, true> : hnsw_search2_kernel<METRIC, QUANT, PROF, OPT, VIS, false, true>;
+    if (sp.r8) return hnsw_search2_kernel<METRIC, QUANT, PROF, OPT, VIS, false, false, true>;
+  }
+  return hnsw_search2_kernel<METRIC, QUANT, PROF, OPT, VIS>;
+}
+// ... and its row-filter twins (f32 cosine, eight-lane core) by the shadow they read; the 16-bit visited set serves the filter over the quantised query only.
+// (adjacency prefetch for f32 rows in small batches: measured, no gain — 1 M x 128, ef 20, one query 105 vs 111 us)
+template <int PROF, int OPT, int VIS>
+fkern_t filter_instance(const SearchPlan& sp) {
+  if (sp.filter == ROW_FILTER_8I) return sp.nt ? hnsw_search2_rowfilter_kernel<PROF, OPT, VIS, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF, OPT, VIS, false, ROW_FILTER_8I>;
+  if constexpr (VIS != VIS_LDS16) {
+    if (sp.filter == 8) return sp.nt ? hnsw_search2_rowfilter_kernel<PROF, OPT, VIS, true, 8> : hnsw_search2_rowfilter_kernel<PROF, OPT, VIS, false, 8>;
+    if (sp.filter == 16) return sp.nt ? hnsw_search2_rowfilter_kernel<PROF, OPT, VIS, true> : hnsw_search2_rowfilter_kernel<PROF, OPT, VIS, false>;
+  }
+  return nullptr;
+}
+
+// hnsw_walk2.hpp kernels: the launch of one plan (hnsw.hip: plan_search decided everything; a plan it passed has an instance here).
 template <int METRIC, int QUANT>
-int launch_search2_for(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
+int launch_search2_for(Hnsw* x, HCtx* c, const SearchPlan& sp, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
                    uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
-  typedef void (*kern_t)(GraphView, int32_t, int32_t, const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*,
-                         uint64_t*, float*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*);
-  typedef void (*fkern_t)(GraphView, int32_t, int32_t, const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*,
-                          uint64_t*, float*, uint32_t*, unsigned long long*, uint8_t*, size_t, uint32_t*, uint32_t);   // the row-filter twins: + how the prologue descends
   kern_t kern = nullptr;
   fkern_t fkern = nullptr;
-  const bool nt = rows_nt(x);   // non-temporal row loads (eight-lane kernels): see exact.hpp: row_ld
-  bool flt = false;             // the row-filter twin (row_filter_on)
-  bool v16 = false;             // ... over the 16-bit visited set (search_geom: vis16)
-#define COLTT_W2(V, PROF, OPT) case V: kern = hnsw_search2_kernel<METRIC, QUANT, PROF, OPT>; break;
-  if (sg.w2_lds) {
-    switch (sg.w2) {
-      case 4:
-        kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 4, VIS_LDS>;
-        if constexpr (QUANT != Q_F8) {
-          if (sg.ev8) kern = nt ? hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 4, VIS_LDS, false, true, false, true> : hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 4, VIS_LDS, false, true>;
-          else if (x->r8) kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_LDS, 4, VIS_LDS, false, false, true>;   // the pair-owned core over the line-transposed rows
-        }
-        if constexpr (METRIC == M_COS && QUANT == Q_NONE) {   // the row-filter twin of the eight-lane instance just chosen
-          if (sg.ev8 && row_filter_on(x, false)) {
-            const int fb = row_filter_bits(x);
-            if (fb == ROW_FILTER_8I && sg.qd8i && sg.vis16) { fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS16, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS16, false, ROW_FILTER_8I>; v16 = true; }
-            else if (fb == ROW_FILTER_8I && sg.qd8i) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, ROW_FILTER_8I>;   // (sg.qd8i: search_geom made room for the digit planes)
-            else if (fb == 8 || fb == ROW_FILTER_8I) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false, 8>;
-            else fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_LDS, 4, VIS_LDS, false>;
-            flt = true;
-          }
-        }
-        break;   // (adjacency prefetch for f32 rows in small batches: measured, no gain — 1 M x 128, ef 20, one query 105 vs 111 us)
-      default: break;
-    }
-  } else
-  {
-    switch (sg.w2) {
-      COLTT_W2(6, PROF_SEARCH_HBM, 6) COLTT_W2(7, PROF_SEARCH_HBM, 7)
-      default: break;
-    }
-    if constexpr (METRIC == M_COS && QUANT == Q_NONE) {   // W2_ADJN: both shipped HBM-visited variants carry the neighbours' norms
-      if (sg.ev8 && row_filter_on(x, true) && (sg.w2 == 6 || sg.w2 == 7)) flt = true;
-      if (flt && sg.w2 == 6) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false>;
-      if (flt && sg.w2 == 7) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false>;
-      const int fb = flt ? row_filter_bits(x) : 0;
-      if (fb == ROW_FILTER_8I && sg.qd8i) {
-        if (sg.w2 == 6) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false, ROW_FILTER_8I>;
-        if (sg.w2 == 7) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true, ROW_FILTER_8I> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false, ROW_FILTER_8I>;
-      } else if (fb == 8 || fb == ROW_FILTER_8I) {
-        if (sg.w2 == 6) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 6, VIS_HBM, false, 8>;
-        if (sg.w2 == 7) fkern = nt ? hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, true, 8> : hnsw_search2_rowfilter_kernel<PROF_SEARCH_HBM, 7, VIS_HBM, false, 8>;
-      }
-    }
-    if constexpr (QUANT != Q_F8) { if (!flt) {
-      if (sg.ev8 && sg.w2 == 6) kern = nt ? hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 6, VIS_HBM, false, true, false, true> : hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 6, VIS_HBM, false, true>;
-      if (sg.ev8 && sg.w2 == 7) kern = nt ? hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 7, VIS_HBM, false, true, false, true> : hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 7, VIS_HBM, false, true>;
-      if (!sg.ev8 && x->r8 && sg.w2 == 6) kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 6, VIS_HBM, false, false, true>;
-      if (!sg.ev8 && x->r8 && sg.w2 == 7) kern = hnsw_search2_kernel<METRIC, QUANT, PROF_SEARCH_HBM, 7, VIS_HBM, false, false, true>;
-    } }
+  const bool v16 = sp.vis_kind == 16;
+#define COLTT_W2(PROF, OPT, VIS)                                                                                                   \
+  do {                                                                                                                           \
+    if constexpr (METRIC == M_COS && QUANT == Q_NONE) { if (sp.filter) fkern = filter_instance<PROF, OPT, VIS>(sp); }             \
+    if (!sp.filter) kern = walk_instance<METRIC, QUANT, PROF, OPT, VIS>(sp);                                                    \
+  } while (0)
+  switch (sp.vis_kind << 4 | sp.w2) {
+    case 32 << 4 | 4: COLTT_W2(PROF_SEARCH_LDS, 4, VIS_LDS); break;
+    case 16 << 4 | 4: if constexpr (METRIC == M_COS && QUANT == Q_NONE) fkern = filter_instance<PROF_SEARCH_LDS, 4, VIS_LDS16>(sp); break;
+    case 0 << 4 | 6: COLTT_W2(PROF_SEARCH_HBM, 6, VIS_HBM); break;   // W2_ADJN: both shipped HBM-visited variants carry the neighbours' norms
+    case 0 << 4 | 7: COLTT_W2(PROF_SEARCH_HBM, 7, VIS_HBM); break;
+    default: break;
   }
 #undef COLTT_W2
-  uint32_t upper = 0;
-  if (flt && fkern) {   // (the binary16 kind has no per-slot (scale, error norm): its descent stays exact)
-    const Policy p = policy();
-    const int fb = row_filter_bits(x);
-    if ((fb == 8 || fb == ROW_FILTER_8I) && (p.row_filter_upper >= 0 ? p.row_filter_upper != 0 : ROW_FILTER_UPPER_DEFAULT)) upper |= ROWF_UPPER_FILTER;
-    if (nt && (p.descent_nt >= 0 ? p.descent_nt == 0 : !DESCENT_NT_DEFAULT)) upper |= ROWF_UPPER_CACHED;
-  }
-  c->upper_launch = (upper & ROWF_UPPER_FILTER) != 0;
-  if (!kern && !fkern) return fail(COLTT_E_UNSUPPORTED, "hnsw_search: walk variant %d is not compiled into this build (COLTT_WALK2)", sg.w2);
-  if (x->r8 && !sg.ev8 && !(sg.w2_lds ? sg.w2 == 4 : (sg.w2 == 6 || sg.w2 == 7)))
-    return fail(COLTT_E_UNSUPPORTED, "hnsw_search: walk variant %d has no instance for line-transposed rows (create the index with COLTT_ROWS8=0 for this experiment)", sg.w2);
-  if (sg.ev8) x->ev8_launches.fetch_add(1);
-  if (sg.vis16 && !v16) return fail(COLTT_E_DEVICE, "hnsw_search: the launch's LDS was sized for the 16-bit visited set, but the walk chosen does not use it");
-  c->flt_launch = flt; c->v16_launch = v16;
+  if (!kern && !fkern) return fail(COLTT_E_DEVICE, "hnsw_search: no kernel instance for the plan (walk variant %d)", sp.w2);   // (walk2_shipped names the same set)
   const void* const kp = fkern ? reinterpret_cast<const void*>(fkern) : reinterpret_cast<const void*>(kern);
-  COLTT_HIP(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds));
+  COLTT_HIP(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.lds));
   static const bool dbg_occ = [] { const char* e = getenv("COLTT_DEBUG_OCCUPANCY"); return e && *e == '1'; }();   // diagnostics: the waves the runtime keeps resident per CU at this launch's LDS
   if (dbg_occ || v16) {   // (the 16-bit launches report it through coltt_hnsw_visited_stats: asked once per (kernel, LDS) and context)
-    if (c->occ_kern != kp || c->occ_lds != sg.lds) {
+    if (c->occ_kern != kp || c->occ_lds != sp.lds) {
       int per_cu = 0;
-      COLTT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, 64, sg.lds));
-      c->occ_kern = kp; c->occ_lds = sg.lds; c->occ_per_cu = per_cu;
+      COLTT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, 64, sp.lds));
+      c->occ_kern = kp; c->occ_lds = sp.lds; c->occ_per_cu = per_cu;
     }
-    if (dbg_occ) fprintf(stderr, "[occupancy] walk variant %d%s filter %d (8i planes %d) visited set %s: %zu B of LDS per wave, %d waves resident per CU, grid %u\n", sg.w2, sg.w2_lds ? " (LDS hash)" : "", flt ? 1 : 0, sg.qd8i ? 1 : 0,
-                         v16 ? "16-bit LDS table" : (sg.w2_lds ? "32-bit LDS table" : "HBM byte map"), sg.lds, c->occ_per_cu, grid);
+    if (dbg_occ) fprintf(stderr, "[occupancy] walk variant %d%s filter %d (8i planes %d) visited set %s: %zu B of LDS per wave, %d waves resident per CU, grid %u\n", sp.w2, sp.vis_kind ? " (LDS hash)" : "", sp.filter ? 1 : 0, sp.filter == ROW_FILTER_8I ? 1 : 0,
+                         v16 ? "16-bit LDS table" : (sp.vis_kind ? "32-bit LDS table" : "HBM byte map"), (size_t)sp.lds, c->occ_per_cu, grid);
   }
-  const uint32_t vis_arg = sg.w2_lds ? (v16 ? ((sg.v16_limit << 8) | sg.v16_bits) : sg.hcap) : sg.bloom_words;
-  if (fkern) fkern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
-                                                    k, sg.ef, sg.ef_pad, vis_arg, counter, oi, os, oc, stats,
+  const uint32_t vis_arg = sp.vis_kind ? (v16 ? ((sp.v16_limit << 8) | sp.v16_bits) : sp.hcap) : sp.bloom_words;
+  if (fkern) fkern<<<grid, 64, sp.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
+                                                    k, sp.ef, sp.ef_pad, vis_arg, counter, oi, os, oc, stats,
                                                     x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
-                                                    x->w_vepoch.as<uint32_t>() + region_base, upper);
-  else kern<<<grid, 64, sg.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
-                                             k, sg.ef, sg.ef_pad, vis_arg, counter, oi, os, oc, stats,
+                                                    x->w_vepoch.as<uint32_t>() + region_base, sp.upper);
+  else kern<<<grid, 64, sp.lds, c->stream>>>(x->view(), x->entry, x->entry_level, c->w_qeff.as<float>(), c->w_qn.as<float>(), nq,
+                                             k, sp.ef, sp.ef_pad, vis_arg, counter, oi, os, oc, stats,
                                              x->w_visg.as<uint8_t>() + (size_t)region_base * x->vis_stride, (size_t)x->vis_stride,
                                              x->w_vepoch.as<uint32_t>() + region_base);
   COLTT_HIP(hipGetLastError());
@@ -127,10 +92,10 @@ namespace coltt {
 namespace hnsw {
 
 // the launcher for the index's metric and row format
-int launch_search2(Hnsw* x, HCtx* c, const SearchGeom& sg, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
+int launch_search2(Hnsw* x, HCtx* c, const SearchPlan& sp, uint32_t grid, uint32_t region_base, uint32_t nq, uint32_t k, uint32_t* counter,
                    uint64_t* oi, float* os, uint32_t* oc, unsigned long long* stats) {
   int rc;
-#define COLTT_LS_ARGS x, c, sg, grid, region_base, nq, k, counter, oi, os, oc, stats
+#define COLTT_LS_ARGS x, c, sp, grid, region_base, nq, k, counter, oi, os, oc, stats
 #define COLTT_LS(Q) rc = x->metric == COLTT_COSINE ? launch_search2_for<M_COS, Q>(COLTT_LS_ARGS) : launch_search2_for<M_L2, Q>(COLTT_LS_ARGS)
   COLTT_DISPATCH_QUANT(x->quant, COLTT_LS)
 #undef COLTT_LS

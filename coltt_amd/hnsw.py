@@ -132,6 +132,34 @@ def compact_map_host(del_bits, n_slots, levels):
     return new_of_old, upper_off[:live.value].copy(), live.value, up.value
 
 
+class PlanFactsC(C.Structure):
+    """coltt_hnsw_plan_facts (include/coltt_gpu.h): what the search plan reads of an index"""
+    _fields_ = [("dim", C.c_uint32), ("metric", C.c_int32), ("quant", C.c_int32), ("m_max0", C.c_uint32), ("stride", C.c_uint64), ("slots", C.c_uint64),
+                ("r8", C.c_int32), ("shadow8", C.c_int32), ("shadow16", C.c_int32), ("vis_ready", C.c_int32), ("vis_regions", C.c_uint32)]
+
+
+class SearchPlanC(C.Structure):
+    """coltt_hnsw_search_plan (include/coltt_gpu.h): which kernel a search launches, and how"""
+    _fields_ = [("family", C.c_int32), ("ef", C.c_uint32), ("ef_pad", C.c_uint32), ("hcap", C.c_uint32), ("lds", C.c_uint64), ("vis_kind", C.c_int32),
+                ("w2", C.c_int32), ("bloom_words", C.c_uint32), ("r8", C.c_int32), ("ev8", C.c_int32), ("nt", C.c_int32), ("filter", C.c_int32),
+                ("upper", C.c_uint32), ("v16_bits", C.c_uint32), ("v16_limit", C.c_uint32), ("per_cu", C.c_uint32), ("grid", C.c_uint32),
+                ("rows8_launch", C.c_int32), ("lat_seq", C.c_int32), ("lat_helpers", C.c_int32)]
+
+
+SEARCH_PLAN_DTYPE = np.dtype(SearchPlanC)   # an array of plans as numpy records
+PLAN_LATENCY, PLAN_WALK2, PLAN_ONE_WAVE = 0, 1, 2   # SearchPlanC.family
+ROWF_UPPER_FILTER, ROWF_UPPER_CACHED = 1, 2         # SearchPlanC.upper
+
+
+def search_plan_host(facts, nq, k, ef, force=0):
+    """coltt_hnsw_search_plan_host (no device): the plan of a search of nq queries for k answers at ef over an index with these facts (a PlanFactsC or a
+    dict of its fields) under the knobs os.environ holds now — a dict of SearchPlanC's fields; raises ColttError where the search would"""
+    f = facts if isinstance(facts, PlanFactsC) else PlanFactsC(**{n: int(v) for n, v in facts.items()})
+    p = SearchPlanC()
+    L.check(L.lib().coltt_hnsw_search_plan_host(C.byref(f), C.c_size_t(int(nq)), C.c_uint32(int(k)), C.c_uint32(int(ef)), C.c_int(int(force)), C.byref(p)))
+    return {n: getattr(p, n) for n, _ in SearchPlanC._fields_}
+
+
 class HnswFilter:
     """An allow-list of ids against one index (coltt_hnsw_filter_create; include/coltt_gpu.h, "Filtered HNSW search" — an extension the
     reference does not have).  `.allowed` = the live vertices it allows."""
@@ -555,6 +583,17 @@ class Hnsw:
         n, s, v = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         L.check(L.lib().coltt_hnsw_visited_stats(self.h, C.byref(k), C.byref(w), C.byref(g), C.byref(n), C.byref(s), C.byref(v)))
         return {"kind": k.value, "waves_per_cu": w.value, "grid": g.value, "launches16": n.value, "stash_max": s.value, "visited_max": v.value}
+
+    def PlanFacts(self):
+        """what the search plan reads of this index as it is now (coltt_hnsw_search_plan_facts).  vis_ready: the HBM visited workspace exists — the first
+        search that wants it (ef > 128 by default) makes it"""
+        f = PlanFactsC()
+        L.check(L.lib().coltt_hnsw_search_plan_facts(self.h, C.byref(f)))
+        return f
+
+    def SearchPlan(self, nq, k, ef=0, force=0):
+        """which kernel Search(queries[nq], k, ef) launches on this index as it is now, and how (search_plan_host over PlanFacts())"""
+        return search_plan_host(self.PlanFacts(), nq, k, ef or self.cfg.ef, force)
 
     def FetchShadow8(self, first=0, n=None):
         """the 8-bit shadow of slots [first, first + n) (coltt_hnsw_fetch_shadow8): codes [n, dim] int8 in natural element order, (scale, error norm)

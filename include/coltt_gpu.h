@@ -556,6 +556,44 @@ int coltt_hnsw_row_filter_stats_ex(coltt_handle_t h, uint64_t* out_upper_shadow_
  * vertices one traversal of that last launch visited (0 unless it ran on the 16-bit table).
  * Any out pointer may be NULL. */
 int coltt_hnsw_visited_stats(coltt_handle_t h, int32_t* out_kind, uint32_t* out_waves_per_cu, uint32_t* out_grid, uint64_t* out_launches16, uint64_t* out_stash_max, uint64_t* out_visited_max);
+/* Which kernel a coltt_hnsw_search call launches, and how ("The search plan").  The search decides it once per call, in one function of the
+ * index facts below, the knob snapshot (COLTT_*; coltt_policy_reload) and (nq, k, ef, force); coltt_hnsw_search_plan_host runs that function with no
+ * device.  Nothing else about an index influences the plan. */
+typedef struct coltt_hnsw_plan_facts {
+  uint32_t dim; int32_t metric, quant;
+  uint32_t m_max0;
+  uint64_t stride;        /* bytes per stored row */
+  uint64_t slots;
+  int32_t r8;             /* the rows are stored line-transposed (COLTT_ROWS8 at create) */
+  int32_t shadow8, shadow16;   /* the row-filter shadows the index keeps */
+  int32_t vis_ready;      /* the HBM visited workspace exists (it is made by the first search that wants it) */
+  uint32_t vis_regions;   /* ... and its regions: at most that many traversals of one launch */
+} coltt_hnsw_plan_facts;
+enum { COLTT_PLAN_LATENCY = 0, COLTT_PLAN_WALK2 = 1, COLTT_PLAN_ONE_WAVE = 2 };   /* coltt_hnsw_search_plan.family */
+typedef struct coltt_hnsw_search_plan {
+  int32_t family;         /* COLTT_PLAN_*: the 256-thread latency kernel, the hnsw_walk2.hpp walks, the one-wave walk */
+  uint32_t ef, ef_pad;    /* max(ef, k), and rounded up to 64 */
+  uint32_t hcap;          /* words of the 32-bit LDS visited table (64 with the HBM map) */
+  uint64_t lds;           /* dynamic LDS bytes per workgroup */
+  int32_t vis_kind;       /* the visited set: 0 HBM byte map, 32 / 16 the LDS table of 32-bit / 16-bit entries */
+  int32_t w2;             /* COLTT_PLAN_WALK2: the walk variant (OPT bits | 8 deep profile), else -1 */
+  uint32_t bloom_words;   /* ... its Bloom filter (HBM map only), 0 none */
+  int32_t r8;             /* the kernel reads line-transposed rows */
+  int32_t ev8;            /* COLTT_PLAN_WALK2: the eight-lane distance core */
+  int32_t nt;             /* ... with non-temporal row loads */
+  int32_t filter;         /* ... and the level-0 row filter: 0 none, 16, 8, 80 (8i) */
+  uint32_t upper;         /* ... the filter launch's prologue: bit 0 filtered descent, bit 1 cacheable descent loads */
+  uint32_t v16_bits, v16_limit;   /* vis_kind 16: log2 of the bucket count, the capacity rule's limit */
+  uint32_t per_cu, grid;  /* traversals resident per CU by the grid rule; the grid before visited regions are leased */
+  int32_t rows8_launch;   /* the launch counts in coltt_hnsw_rows8_searches */
+  int32_t lat_seq, lat_helpers;   /* COLTT_PLAN_LATENCY: the sequential walk; helper workgroups per walking one (batches <= 8 queries) */
+} coltt_hnsw_search_plan;
+/* The plan of a search of nq queries for k answers at ef_override (>= 1; the index's default ef is not among the facts) over an index with these facts,
+ * under the current knob snapshot.  force: 0, or what a call re-run after a visited-table overflow passes (1 not the latency kernel, 3 nor the walk over the
+ * LDS table).  Returns what the search would: COLTT_E_UNSUPPORTED with its message for ef > 4096, LDS beyond 160 KiB, a walk variant that is not compiled. */
+int coltt_hnsw_search_plan_host(const coltt_hnsw_plan_facts* facts, size_t nq, uint32_t k, uint32_t ef_override, int force, coltt_hnsw_search_plan* out);
+/* The facts of a live index as its next search would read them. */
+int coltt_hnsw_search_plan_facts(coltt_handle_t h, coltt_hnsw_plan_facts* out_facts);
 /* Read-back of the 8-bit shadow for tests and tools: the codes of slots [first_slot, first_slot + n) in natural element order ([n][dim]), their
  * (scale, error norm) pairs ([n][2] floats) and the pairs carried by their level-0 adjacency rows ([n][m_max0][2] floats, zeros at empty positions).
  * Any out pointer may be NULL; COLTT_E_UNSUPPORTED when the index keeps no 8-bit shadow. */

@@ -388,6 +388,14 @@ class Hnsw {
     check(coltt_hnsw_pq_fetch_nbr(h_, first, n, out.data()));
     return out;
   }
+  // which kernel Search(queries[nq], k, ef) launches on this index as it is now, and how (coltt_hnsw_search_plan_host over the index's facts; no launch)
+  coltt_hnsw_plan_facts PlanFacts() const { coltt_hnsw_plan_facts f; check(coltt_hnsw_search_plan_facts(h_, &f)); return f; }
+  coltt_hnsw_search_plan SearchPlan(size_t nq, uint32_t k, uint32_t ef = 0, int force = 0) const {
+    const coltt_hnsw_plan_facts f = PlanFacts();
+    coltt_hnsw_search_plan p;
+    check(coltt_hnsw_search_plan_host(&f, nq, k, ef ? ef : (uint32_t)RawConfig().ef, force, &p));
+    return p;
+  }
   int Len() const { uint64_t n = 0; check(coltt_hnsw_len(h_, &n)); return (int)n; }
   // the collection's size is known (bulk import, Load): every array allocated once; never shrinks, never limits an Insert
   void Reserve(uint64_t vertices, uint64_t upper_rows = 0) { check(coltt_hnsw_reserve(h_, vertices, upper_rows)); }
