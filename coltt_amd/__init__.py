@@ -11,6 +11,7 @@ from ._lib import (COSINE, EUCLIDEAN, Q_NONE, Q_F16, Q_F8, Q_BF16, SELECT_REFERE
 from .flat import FlatSpace  # noqa: F401
 from .hnsw import Hnsw, HnswCfg, HnswFilter, FILTER_AUTO, FILTER_WALK, FILTER_EXACT  # noqa: F401
 from .hnsw import HnswCompactStats, compact_map_host  # noqa: F401
+from .hnsw import HnswCarryStats, carry_bits_host, carry_bits_device  # noqa: F401
 from .hnsw import (PlanFactsC, SearchPlanC, search_plan_host, PLAN_LATENCY, PLAN_WALK2, PLAN_ONE_WAVE,  # noqa: F401
                    ROWF_UPPER_FILTER, ROWF_UPPER_CACHED)
 from .hnsw import FOP_AND, FOP_OR, FOP_ANDNOT, FOP_NOT, FOP_ALL, filter_postfix, filter_tree, filter_prog_check  # noqa: F401

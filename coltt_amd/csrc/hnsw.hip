@@ -28,6 +28,7 @@
 #include "filter_expr.hpp"    // filter expressions: evaluate, compact, read-back
 #include "attr_filter.hpp"    // attribute columns: predicate leaves of a filter programme, scatter, gather
 #include "hnsw_compact.hpp"   // coltt_hnsw_compact: the plan, the row movers, the adjacency re-pack
+#include "filter_carry.hpp"   // coltt_hnsw_compact_carry: resident filters and column bitmaps through the renumbering
 
 using namespace coltt;
 using namespace coltt::dev;
@@ -2139,18 +2140,90 @@ int coltt_hnsw_compact_map_host(const uint32_t* del_bits, uint64_t n_slots, cons
   return COLTT_OK;
 }
 
-int coltt_hnsw_compact(coltt_handle_t h, uint64_t stage_bytes_or_0, uint32_t* out_new_of_old, uint64_t cap_map, coltt_hnsw_compact_stats* stats) {
+}  // extern "C"
+
+namespace {
+
+// what coltt_hnsw_compact_carry adds to a compaction: the listed filters and columns come out valid at the new generation
+struct CarryReq {
+  const coltt_handle_t* filters; size_t n_filters; uint64_t* out_allowed;
+  const coltt_handle_t* columns; size_t n_columns; uint64_t* out_set;
+  coltt_hnsw_carry_stats* stats;
+};
+
+// a carried filter takes its new bitmap and list (slices of `slab`; nullptr: the empty filter) and lets go of what it had
+void filter_install(HnswFilter* f, const std::shared_ptr<FilterSlab>& slab, uint32_t* bits, uint32_t* list, uint32_t slots, uint64_t allowed, uint64_t gen) {
+  if (f->slab) { f->bits.p = nullptr; f->list.p = nullptr; }   // slices of a shared slab: its siblings keep it
+  else { if (f->bits.p) (void)hipFree(f->bits.p); if (f->list.p) (void)hipFree(f->list.p); }
+  f->slab = slab;
+  f->bits.p = bits; f->bits.cap = bits ? ((size_t)slots + 31) / 32 * 4 : 0;
+  f->list.p = allowed ? list : nullptr; f->list.cap = (size_t)allowed * 4;
+  f->slots = slots; f->allowed = allowed; f->gen = gen;
+}
+
+// coltt_hnsw_compact and coltt_hnsw_compact_carry (cr != nullptr): one compaction
+int compact_common(coltt_handle_t h, const char* who, uint64_t stage_bytes_or_0, const CarryReq* cr, uint32_t* out_new_of_old, uint64_t cap_map,
+                   coltt_hnsw_compact_stats* stats) {
   auto x = lookup<Hnsw>(h);
-  if (!x) return fail(COLTT_E_NOT_FOUND, "hnsw_compact: unknown handle");
+  if (!x) return fail(COLTT_E_NOT_FOUND, "%s: unknown handle", who);
+  // ---- the objects to carry: handles first, each distinct object once
+  std::vector<std::shared_ptr<HnswFilter>> cf;
+  std::vector<std::shared_ptr<HnswAttr>> cc;
+  std::vector<size_t> f_at, c_at;   // list position -> its object in cf / cc
+  if (cr) {
+    if (cr->n_filters && !cr->filters) return fail(COLTT_E_INVALID, "%s: filters is NULL with n_filters = %zu", who, cr->n_filters);
+    if (cr->n_columns && !cr->columns) return fail(COLTT_E_INVALID, "%s: columns is NULL with n_columns = %zu", who, cr->n_columns);
+    std::unordered_map<coltt_handle_t, size_t> seen;
+    f_at.resize(cr->n_filters); c_at.resize(cr->n_columns);
+    for (size_t i = 0; i < cr->n_filters; i++) {
+      auto it = seen.find(cr->filters[i]);
+      if (it == seen.end()) {
+        auto f = lookup<HnswFilter>(cr->filters[i]);
+        if (!f) return fail(COLTT_E_NOT_FOUND, "%s: unknown filter handle at filters[%zu]", who, i);
+        if (f->index != h) return fail(COLTT_E_INVALID, "%s: the filter at filters[%zu] was built for another index", who, i);
+        it = seen.emplace(cr->filters[i], cf.size()).first;
+        cf.push_back(std::move(f));
+      }
+      f_at[i] = it->second;
+    }
+    seen.clear();
+    for (size_t i = 0; i < cr->n_columns; i++) {
+      auto it = seen.find(cr->columns[i]);
+      if (it == seen.end()) {
+        auto a = lookup<HnswAttr>(cr->columns[i]);
+        if (!a) return fail(COLTT_E_NOT_FOUND, "%s: unknown column handle at columns[%zu]", who, i);
+        if (a->index != h) return fail(COLTT_E_INVALID, "%s: the column at columns[%zu] belongs to another index", who, i);
+        it = seen.emplace(cr->columns[i], cc.size()).first;
+        cc.push_back(std::move(a));
+      }
+      c_at[i] = it->second;
+    }
+  }
   WriteLock g(x->rw);
+  std::vector<WriteLock> clocks;   // index before column: the order of attr_set
+  clocks.reserve(cc.size());
+  for (auto& a : cc) clocks.emplace_back(a->rw);
+  for (size_t i = 0; i < f_at.size(); i++)
+    if (cf[f_at[i]]->gen != x->gen) return fail(COLTT_E_INVALID, "%s: the filter at filters[%zu] is stale (the index was renumbered since it was built)", who, i);
+  for (size_t i = 0; i < c_at.size(); i++)
+    if (cc[c_at[i]]->gen != x->gen) return fail(COLTT_E_INVALID, "%s: the column at columns[%zu] is stale (the index was renumbered since it was created)", who, i);
   COLTT_DEVICE(x->device);
   const uint64_t n = x->n;
-  if (out_new_of_old && cap_map < n) return fail(COLTT_E_INVALID, "hnsw_compact: the map holds %llu entries, the index has %llu slots", (unsigned long long)cap_map, (unsigned long long)n);
+  if (out_new_of_old && cap_map < n) return fail(COLTT_E_INVALID, "%s: the map holds %llu entries, the index has %llu slots", who, (unsigned long long)cap_map, (unsigned long long)n);
   coltt_hnsw_compact_stats st{};
+  coltt_hnsw_carry_stats cst{};
+  cst.filters = cf.size(); cst.columns = cc.size();
   st.slots_before = st.slots_after = n; st.upper_rows_before = st.upper_rows_after = x->n_upper;
+  auto report = [&]() {   // the carried objects as they are now
+    if (!cr) return;
+    if (cr->out_allowed) for (size_t i = 0; i < f_at.size(); i++) cr->out_allowed[i] = cf[f_at[i]]->allowed;
+    if (cr->out_set) for (size_t i = 0; i < c_at.size(); i++) cr->out_set[i] = cc[c_at[i]]->n_set;
+    if (cr->stats) *cr->stats = cst;
+  };
   if (x->live == n) {   // no tombstone: nothing is launched, nothing is renumbered
     if (out_new_of_old) for (uint64_t s = 0; s < n; s++) out_new_of_old[s] = (uint32_t)s;
     if (stats) *stats = st;
+    report();
     return COLTT_OK;
   }
   // ---- the plan, from the host mirrors
@@ -2160,7 +2233,7 @@ int coltt_hnsw_compact(coltt_handle_t h, uint64_t stage_bytes_or_0, uint32_t* ou
   // Remove elects the removed entrypoint's closest listed neighbour without asking whether it is alive (hnsw.go:197-217): a walk can start from a
   // tombstone, a compacted index cannot — refused before anything changes rather than answered differently
   if (live && x->entry >= 0 && nmap[(size_t)x->entry] == NBR_NONE)
-    return fail(COLTT_E_UNSUPPORTED, "hnsw_compact: the entrypoint (slot %d) is a tombstone; dropping it would change the answers", x->entry);
+    return fail(COLTT_E_UNSUPPORTED, "%s: the entrypoint (slot %d) is a tombstone; dropping it would change the answers", who, x->entry);
   const size_t words = (size_t)((n + 31) / 32);
   uint64_t first = 0;                                   // the first tombstone: the slots below it keep their numbers
   while (nmap[first] != NBR_NONE) first++;
@@ -2176,25 +2249,45 @@ int coltt_hnsw_compact(coltt_handle_t h, uint64_t stage_bytes_or_0, uint32_t* ou
   while (ufirst < up_after && uold[ufirst] == ufirst) ufirst++;
   st.slots_after = live; st.upper_rows_after = up_after; st.rows_moved = live - first;
   x->pq_nbr_stale.store(true);   // the slots are about to be renumbered: the next walk over the blocks rebuilds them, as after Load
+  // new(s) for any s <= n, tombstoned or not: the live slots below s.  Reads the OLD h_del: every use is before the mirrors are rebuilt
+  auto new_below = [&](uint64_t s) -> uint64_t {
+    if (s >= n) return live;
+    return (uint64_t)rank[s >> 5] + (uint64_t)__builtin_popcount(~x->h_del[s >> 5] & ((1u << (s & 31)) - 1u));
+  };
   if (live == 0) {               // every vertex is dead: the empty index
     hipError_t e = hipMemsetAsync(x->del_bits.p, 0, words * 4, x->stream);
+    for (auto& a : cc)           // a carried column covers no slot; no word of its bitmap past the coverage is set
+      if (e == hipSuccess && a->set.p) e = hipMemsetAsync(a->set.p, 0, ((size_t)a->cap + 31) / 32 * 4, x->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
     make_empty(x.get());
-    if (e != hipSuccess) return fail(COLTT_E_DEVICE, "hnsw_compact: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(COLTT_E_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    for (auto& f : cf) filter_install(f.get(), nullptr, nullptr, nullptr, 0, 0, x->gen);
+    for (auto& a : cc) { a->slots = 0; a->n_set = 0; std::fill(a->h_set.begin(), a->h_set.end(), 0u); a->gen = x->gen; }
     if (out_new_of_old) std::copy(nmap.begin(), nmap.end(), out_new_of_old);
     if (stats) *stats = st;
+    report();
     return COLTT_OK;
   }
   // ---- what moves.  Per-slot arrays: rows of rb bytes; every allocation is made before the first kernel, so a refused one leaves the index as it was
-  struct Move { uint8_t* p; size_t rb; };
+  struct Move { uint8_t* p; size_t rb; uint64_t end; };   // the new slots [first, end) of this array move
   std::vector<Move> moves;
-  moves.push_back({x->rows.as<uint8_t>(), x->stride});
-  if (x->has_shadow16()) moves.push_back({x->rows_h.as<uint8_t>(), (size_t)x->dim * 2});
-  if (x->has_shadow8()) { moves.push_back({x->rows_b.as<uint8_t>(), (size_t)x->dim}); moves.push_back({x->rows_m.as<uint8_t>(), 8}); }
-  moves.push_back({x->norms.as<uint8_t>(), 4});
-  if (!x->dense) moves.push_back({x->ids.as<uint8_t>(), 8});
+  moves.push_back({x->rows.as<uint8_t>(), x->stride, live});
+  if (x->has_shadow16()) moves.push_back({x->rows_h.as<uint8_t>(), (size_t)x->dim * 2, live});
+  if (x->has_shadow8()) { moves.push_back({x->rows_b.as<uint8_t>(), (size_t)x->dim, live}); moves.push_back({x->rows_m.as<uint8_t>(), 8, live}); }
+  moves.push_back({x->norms.as<uint8_t>(), 4, live});
+  if (!x->dense) moves.push_back({x->ids.as<uint8_t>(), 8, live});
   const bool pq_move = x->pq_on && x->pq_done == n && x->pq_codes.p;   // (writers leave every slot coded; otherwise the codes are made again below)
-  if (pq_move) moves.push_back({x->pq_codes.as<uint8_t>(), (size_t)x->pq_row});
+  if (pq_move) moves.push_back({x->pq_codes.as<uint8_t>(), (size_t)x->pq_row, live});
+  // a carried column's values: the new slots below new(covered), whose sources lie below the coverage (new() is monotone)
+  // every carried object's new coverage, once, from the old mirrors: new(F.slots), new(covered)
+  std::vector<uint32_t> f_cov(cf.size()), c_cov(cc.size());
+  for (size_t i = 0; i < cf.size(); i++) f_cov[i] = (uint32_t)new_below(cf[i]->slots);
+  for (size_t i = 0; i < cc.size(); i++) c_cov[i] = (uint32_t)new_below(cc[i]->slots);
+  for (size_t i = 0; i < cc.size(); i++) {
+    HnswAttr* a = cc[i].get();
+    const uint64_t end = c_cov[i];
+    if (a->vals.p && end > first) { moves.push_back({a->vals.as<uint8_t>(), 8, end}); cst.column_values += end - first; }
+  }
   const uint32_t W0 = (uint32_t)x->cfg.m_max0, WU = (uint32_t)x->cfg.m_max;
   const bool with_n = x->metric == COLTT_COSINE, with_m = x->has_shadow8();
   auto region = [](uint64_t rows, uint32_t W, size_t elem) { return ((size_t)rows * W * elem + 255) & ~(size_t)255; };   // one array's share of the staging block
@@ -2217,9 +2310,45 @@ int coltt_hnsw_compact(coltt_handle_t h, uint64_t stage_bytes_or_0, uint32_t* ou
   COLTT_TRY(d_plan.reserve(off_cnt + 256));
   if (stage_need) COLTT_TRY(d_stage.reserve(stage_need));
   if (x->dense) COLTT_TRY(x->ids.reserve(std::max<uint64_t>(x->cap, 1024) * 8, false, x->stream));
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // ---- the carry (filter_carry.hpp): the filters' bitmaps first, then the columns' set bitmaps, in one launch.  The filters' new bitmaps and
+  // lists are slices of one slab (lists sized by the OLD allowed counts: no round trip decides an allocation), the columns' new bitmaps go to
+  // scratch and are copied over the old ones in stream order.  Everything is allocated here, before the first kernel.
+  const size_t nF = cf.size(), nC = cc.size(), nP = nF + nC;
+  const uint32_t nw_new = (uint32_t)((live + 31) / 32), c_wg = carry_n_wg(live);
+  const size_t c_stride = carry_stride(live);
+  if (nP * (uint64_t)c_wg > 0x7fffffffull) return fail(COLTT_E_UNSUPPORTED, "%s: %zu bitmaps over %llu slots exceed one launch", who, nP, (unsigned long long)live);
+  std::shared_ptr<FilterSlab> slab;
+  DevBuf d_carry;
+  std::vector<CarryMap> h_maps(nP);
+  std::vector<uint64_t> h_loff(nF);
+  // read-back targets (pageable: the copies are staged and the stream is synchronised before they are read; a column's whole new set bitmap
+  // comes back only to refill its h_set mirror — small at present column counts, pinned staging if they grow)
+  std::vector<uint32_t> h_cnt(nP * (size_t)c_wg), h_cset(nC * (size_t)nw_new);
+  uint64_t list_total = 0;
+  const size_t o_loff = ((nP * sizeof(CarryMap)) + 255) & ~(size_t)255, o_cnt = o_loff + ((nF * 8 + 255) & ~(size_t)255),
+               o_cbits = o_cnt + ((h_cnt.size() * 4 + 255) & ~(size_t)255);
+  if (nP) {
+    for (size_t i = 0; i < nF; i++) { h_loff[i] = list_total; list_total += (cf[i]->allowed + 63) & ~63ull; }
+    COLTT_TRY(d_carry.reserve(o_cbits + nC * c_stride * 4));
+    if (nF) {
+      slab = std::make_shared<FilterSlab>();
+      slab->device = x->device;
+      COLTT_TRY(slab->bits.reserve(nF * c_stride * 4));
+      if (list_total) COLTT_TRY(slab->lists.reserve((size_t)list_total * 4));
+    }
+    for (size_t i = 0; i < nF; i++)
+      h_maps[i] = CarryMap{cf[i]->bits.as<uint32_t>(), slab->bits.as<uint32_t>() + i * c_stride, (uint32_t)std::min<uint64_t>(((uint64_t)cf[i]->slots + 31) / 32, words), 0u};
+    for (size_t i = 0; i < nC; i++)
+      h_maps[nF + i] = CarryMap{cc[i]->set.as<uint32_t>(), reinterpret_cast<uint32_t*>(d_carry.as<uint8_t>() + o_cbits) + i * c_stride,
+                                cc[i]->set.p ? (uint32_t)std::min<uint64_t>(((uint64_t)cc[i]->slots + 31) / 32, words) : 0u, 0u};
+  }
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
   COLTT_HIP(hipEventCreate(&ev0));
-  if (hipEventCreate(&ev1) != hipSuccess) { (void)hipEventDestroy(ev0); return fail(COLTT_E_DEVICE, "hnsw_compact: hipEventCreate"); }
+  if (hipEventCreate(&ev1) != hipSuccess) { (void)hipEventDestroy(ev0); return fail(COLTT_E_DEVICE, "%s: hipEventCreate", who); }
+  if (nP && (hipEventCreate(&ev2) != hipSuccess || hipEventCreate(&ev3) != hipSuccess)) {
+    (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); if (ev2) (void)hipEventDestroy(ev2);
+    return fail(COLTT_E_DEVICE, "%s: hipEventCreate", who);
+  }
   uint8_t* const plan = d_plan.as<uint8_t>(); uint8_t* const stage = d_stage.as<uint8_t>();
   const uint32_t* d_oon = reinterpret_cast<const uint32_t*>(plan); const uint32_t* d_rank = reinterpret_cast<const uint32_t*>(plan + off_rank);
   const uint32_t* d_uold = reinterpret_cast<const uint32_t*>(plan + off_uold);
@@ -2268,8 +2397,8 @@ int coltt_hnsw_compact(coltt_handle_t h, uint64_t stage_bytes_or_0, uint32_t* ou
     for (const Move& mv : moves) {
       const uint64_t ch = chunk_of(mv.rb, live - first);
       const int vb = compact::width_of(mv.rb);
-      for (uint64_t b = first; b < live; b += ch) {
-        const uint64_t m = std::min<uint64_t>(ch, live - b);
+      for (uint64_t b = first; b < mv.end; b += ch) {
+        const uint64_t m = std::min<uint64_t>(ch, mv.end - b);
         compact::launch_gather(s, mv.p, mv.rb, d_oon + b, m, stage);
         compact::launch_copy(s, stage, mv.p + b * mv.rb, m * mv.rb, vb);
         bytes += 2 * m * mv.rb;
@@ -2281,16 +2410,43 @@ int coltt_hnsw_compact(coltt_handle_t h, uint64_t stage_bytes_or_0, uint32_t* ou
       COLTT_HIP(hipGetLastError());
       bytes += live * 8;
     }
+    if (nP) {   // the carry: reads the old tombstones, the rank table, old_of_new and the old bitmaps; writes the slab and the scratch only
+      uint8_t* const cb = d_carry.as<uint8_t>();
+      uint32_t* const d_ccnt = reinterpret_cast<uint32_t*>(cb + o_cnt);
+      COLTT_HIP(hipMemcpyAsync(cb, h_maps.data(), nP * sizeof(CarryMap), hipMemcpyHostToDevice, s));
+      if (nF) COLTT_HIP(hipMemcpyAsync(cb + o_loff, h_loff.data(), nF * 8, hipMemcpyHostToDevice, s));
+      COLTT_HIP(hipEventRecord(ev2, s));
+      launch_carry(s, reinterpret_cast<const CarryMap*>(cb), (uint32_t)nP, x->del_bits.as<uint32_t>(), (uint32_t)n, d_rank, d_oon, (uint32_t)live, d_ccnt);
+      if (list_total)
+        filter_compact_kernel<<<(uint32_t)(nF * c_wg), FEX_THREADS, 0, s>>>(slab->bits.as<uint32_t>(), c_stride, nw_new, c_wg, d_ccnt,
+                                                                            reinterpret_cast<const uint64_t*>(cb + o_loff), slab->lists.as<uint32_t>());
+      COLTT_HIP(hipGetLastError());
+      COLTT_HIP(hipEventRecord(ev3, s));
+      for (size_t i = 0; i < nC; i++) {   // a column keeps its own bitmap array: the new words over the old, 0 past them
+        HnswAttr* a = cc[i].get();
+        if (!a->set.p) continue;
+        const size_t cap_words = ((size_t)a->cap + 31) / 32;
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(cb + o_cbits) + i * c_stride;
+        const size_t cw = std::min<size_t>(nw_new, cap_words);   // (the new words past the column's coverage, hence past its capacity, are 0)
+        COLTT_HIP(hipMemcpyAsync(a->set.p, src, cw * 4, hipMemcpyDeviceToDevice, s));
+        if (cap_words > cw) COLTT_HIP(hipMemsetAsync(a->set.as<uint32_t>() + cw, 0, (cap_words - cw) * 4, s));
+        COLTT_HIP(hipMemcpyAsync(h_cset.data() + i * (size_t)nw_new, src, cw * 4, hipMemcpyDeviceToHost, s));
+      }
+      COLTT_HIP(hipMemcpyAsync(h_cnt.data(), d_ccnt, h_cnt.size() * 4, hipMemcpyDeviceToHost, s));
+    }
     COLTT_HIP(hipMemcpyAsync(x->upper_off.p, nuo.data(), live * 4, hipMemcpyHostToDevice, s));
     COLTT_HIP(hipMemsetAsync(x->del_bits.p, 0, words * 4, s));   // last: every launch above read the old tombstones
     COLTT_HIP(hipEventRecord(ev1, s));
     COLTT_HIP(hipMemcpyAsync(&dropped, d_cnt, 8, hipMemcpyDeviceToHost, s));
     COLTT_HIP(hipStreamSynchronize(s));
     COLTT_HIP(hipEventElapsedTime(&st.ms, ev0, ev1));
+    if (nP) COLTT_HIP(hipEventElapsedTime(&cst.ms, ev2, ev3));
     return COLTT_OK;
   };
   int rc = run();
   (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
+  if (ev2) (void)hipEventDestroy(ev2);
+  if (ev3) (void)hipEventDestroy(ev3);
   if (rc != COLTT_OK) { (void)hipStreamSynchronize(x->stream); make_empty(x.get()); return rc; }
   // ---- the host mirrors, from the plan
   std::vector<int32_t> lv(live);
@@ -2308,8 +2464,118 @@ int coltt_hnsw_compact(coltt_handle_t h, uint64_t stage_bytes_or_0, uint32_t* ou
   rc = sync_pq(x.get());
   if (rc != COLTT_OK) { make_empty(x.get()); return rc; }
   st.edges_dropped = dropped; st.bytes_moved = bytes;
+  // ---- the stream has synchronised: the carried objects take their new data under the same handles (an object that was not listed keeps the
+  // old generation and is stale)
+  auto count_of = [&](size_t p) { uint64_t a = 0; for (uint32_t t = 0; t < c_wg; t++) a += h_cnt[p * c_wg + t]; return a; };
+  for (size_t i = 0; i < nF; i++) {
+    const uint64_t a = count_of(i);
+    filter_install(cf[i].get(), slab, slab->bits.as<uint32_t>() + i * c_stride, list_total ? slab->lists.as<uint32_t>() + h_loff[i] : nullptr,
+                   f_cov[i], a, x->gen);
+    cst.list_entries += a;
+  }
+  for (size_t i = 0; i < nC; i++) {
+    HnswAttr* a = cc[i].get();
+    a->slots = c_cov[i]; a->n_set = count_of(nF + i); a->gen = x->gen;
+    std::fill(a->h_set.begin(), a->h_set.end(), 0u);
+    if (a->set.p) std::copy_n(h_cset.begin() + i * (size_t)nw_new, std::min<size_t>(nw_new, a->h_set.size()), a->h_set.begin());
+  }
+  cst.bitmap_words = (uint64_t)nP * nw_new;
   if (out_new_of_old) std::copy(nmap.begin(), nmap.end(), out_new_of_old);
   if (stats) *stats = st;
+  report();
+  return COLTT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int coltt_hnsw_compact(coltt_handle_t h, uint64_t stage_bytes_or_0, uint32_t* out_new_of_old, uint64_t cap_map, coltt_hnsw_compact_stats* stats) {
+  return compact_common(h, "hnsw_compact", stage_bytes_or_0, nullptr, out_new_of_old, cap_map, stats);
+}
+
+int coltt_hnsw_compact_carry(coltt_handle_t h, uint64_t stage_bytes_or_0, const coltt_handle_t* filters, size_t n_filters, uint64_t* out_allowed,
+                             const coltt_handle_t* columns, size_t n_columns, uint64_t* out_set, uint32_t* out_new_of_old, uint64_t cap_map,
+                             coltt_hnsw_compact_stats* stats, coltt_hnsw_carry_stats* carry) {
+  const CarryReq cr{filters, n_filters, out_allowed, columns, n_columns, out_set, carry};
+  return compact_common(h, "hnsw_compact_carry", stage_bytes_or_0, &cr, out_new_of_old, cap_map, stats);
+}
+
+int coltt_hnsw_carry_bits_host(const uint32_t* bits, uint64_t n_words, const uint32_t* del_bits, uint64_t n_slots, uint32_t* out_bits,
+                               uint64_t* out_allowed, uint64_t* out_live) {
+  if (n_slots >= 0x7fffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_carry_bits_host: more than 2^31-1 slots");
+  if (n_words && !bits) return fail(COLTT_E_INVALID, "hnsw_carry_bits_host: NULL bits");
+  carry_bits_host(bits, n_words, del_bits, n_slots, out_bits, out_allowed, out_live);
+  return COLTT_OK;
+}
+
+int coltt_hnsw_carry_bits_device(const uint32_t* bits, uint64_t n_bitmaps, uint64_t n_words, const uint32_t* del_bits, uint64_t n_slots,
+                                 uint32_t* out_bits, uint64_t* out_allowed, uint32_t* out_lists, const uint64_t* list_off) {
+  if (n_slots >= 0x7fffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_carry_bits_device: more than 2^31-1 slots");
+  if (n_bitmaps && n_words && !bits) return fail(COLTT_E_INVALID, "hnsw_carry_bits_device: NULL bits");
+  if (out_lists && !list_off) return fail(COLTT_E_INVALID, "hnsw_carry_bits_device: lists without their offsets");
+  if (n_bitmaps == 0) return COLTT_OK;
+  const size_t words = (size_t)((n_slots + 31) / 32);
+  std::vector<uint32_t> rank(words, 0u), oon;
+  uint64_t live = 0;
+  for (size_t w = 0; w < words; w++) {
+    rank[w] = (uint32_t)live;
+    for (uint32_t b = carry_live_word_host(del_bits, w, words, n_slots); b; b &= b - 1) oon.push_back((uint32_t)(w * 32 + __builtin_ctz(b)));
+    live = oon.size();
+  }
+  if (live == 0) {   // nothing survives: nothing is launched
+    if (out_allowed) std::fill(out_allowed, out_allowed + n_bitmaps, 0ull);
+    return COLTT_OK;
+  }
+  const uint32_t nw_new = (uint32_t)((live + 31) / 32), n_wg = carry_n_wg(live);
+  const size_t stride = carry_stride(live);
+  if (n_bitmaps * (uint64_t)n_wg > 0x7fffffffull) return fail(COLTT_E_UNSUPPORTED, "hnsw_carry_bits_device: %llu bitmaps over %llu slots exceed one launch", (unsigned long long)n_bitmaps, (unsigned long long)live);
+  const size_t src_words = (size_t)std::min<uint64_t>(n_words, words);   // (no slot lies past `words`)
+  COLTT_DEVICE(-1);
+  DevBuf d_src, d_del, d_rank, d_oon, d_maps, d_out, d_cnt, d_loff, d_lists;
+  std::vector<CarryMap> maps(n_bitmaps);
+  std::vector<uint64_t> loff(n_bitmaps);
+  uint64_t total = 0;   // the lists: sized by what each source allows at most, as the compaction sizes them by the old counts
+  for (uint64_t p = 0; p < n_bitmaps; p++) {
+    uint64_t c = 0;
+    for (size_t w = 0; w < src_words; w++) c += (uint64_t)__builtin_popcount(bits[p * n_words + w]);
+    loff[p] = total; total += (std::min<uint64_t>(c, live) + 63) & ~63ull;
+  }
+  if (src_words) COLTT_TRY(d_src.reserve(n_bitmaps * src_words * 4));
+  if (del_bits) COLTT_TRY(d_del.reserve(words * 4));
+  COLTT_TRY(d_rank.reserve(words * 4));
+  COLTT_TRY(d_oon.reserve(live * 4));
+  COLTT_TRY(d_maps.reserve(n_bitmaps * sizeof(CarryMap)));
+  COLTT_TRY(d_out.reserve(n_bitmaps * stride * 4));
+  COLTT_TRY(d_cnt.reserve(n_bitmaps * (size_t)n_wg * 4));
+  if (out_lists && total) { COLTT_TRY(d_loff.reserve(n_bitmaps * 8)); COLTT_TRY(d_lists.reserve((size_t)total * 4)); }
+  for (uint64_t p = 0; p < n_bitmaps; p++) {
+    maps[p] = CarryMap{d_src.as<uint32_t>() + p * src_words, d_out.as<uint32_t>() + p * stride, (uint32_t)src_words, 0u};
+    if (src_words) COLTT_HIP(hipMemcpy(d_src.as<uint32_t>() + p * src_words, bits + p * n_words, src_words * 4, hipMemcpyHostToDevice));
+  }
+  if (del_bits) COLTT_HIP(hipMemcpy(d_del.p, del_bits, words * 4, hipMemcpyHostToDevice));
+  COLTT_HIP(hipMemcpy(d_rank.p, rank.data(), words * 4, hipMemcpyHostToDevice));
+  COLTT_HIP(hipMemcpy(d_oon.p, oon.data(), live * 4, hipMemcpyHostToDevice));
+  COLTT_HIP(hipMemcpy(d_maps.p, maps.data(), n_bitmaps * sizeof(CarryMap), hipMemcpyHostToDevice));
+  launch_carry(nullptr, d_maps.as<CarryMap>(), (uint32_t)n_bitmaps, d_del.as<uint32_t>(), (uint32_t)n_slots, d_rank.as<uint32_t>(), d_oon.as<uint32_t>(),
+               (uint32_t)live, d_cnt.as<uint32_t>());
+  COLTT_HIP(hipGetLastError());
+  if (out_lists && total) {
+    COLTT_HIP(hipMemcpy(d_loff.p, loff.data(), n_bitmaps * 8, hipMemcpyHostToDevice));
+    filter_compact_kernel<<<(uint32_t)(n_bitmaps * n_wg), FEX_THREADS, 0, nullptr>>>(d_out.as<uint32_t>(), stride, nw_new, n_wg, d_cnt.as<uint32_t>(),
+                                                                                     d_loff.as<uint64_t>(), d_lists.as<uint32_t>());
+    COLTT_HIP(hipGetLastError());
+  }
+  COLTT_HIP(hipDeviceSynchronize());
+  std::vector<uint32_t> cnt(n_bitmaps * (size_t)n_wg);
+  COLTT_HIP(hipMemcpy(cnt.data(), d_cnt.p, cnt.size() * 4, hipMemcpyDeviceToHost));
+  if (out_bits) COLTT_HIP(hipMemcpy2D(out_bits, (size_t)nw_new * 4, d_out.p, stride * 4, (size_t)nw_new * 4, n_bitmaps, hipMemcpyDeviceToHost));
+  for (uint64_t p = 0; p < n_bitmaps; p++) {
+    uint64_t a = 0;
+    for (uint32_t t = 0; t < n_wg; t++) a += cnt[p * n_wg + t];
+    if (out_allowed) out_allowed[p] = a;
+    if (out_lists && a) COLTT_HIP(hipMemcpy(out_lists + list_off[p], d_lists.as<uint32_t>() + loff[p], (size_t)a * 4, hipMemcpyDeviceToHost));
+  }
   return COLTT_OK;
 }
 
@@ -2626,19 +2892,6 @@ int coltt_last_kernel_ms(coltt_handle_t h, float* out_ms) {
 // ---- Filtered search: an allow-list of ids against one index (coltt_hnsw_filter_*, coltt_hnsw_search_filtered) ----------------------
 // An extension the reference does not have (its Core.HybridSearch post-filters an unfiltered search): definitions in include/coltt_gpu.h.
 namespace {
-
-// An attribute column (coltt_hnsw_attr_*; include/coltt_gpu.h, "Attribute columns and predicates").  `rw` is the column's own lock: attr_set holds
-// it exclusive (and the index's shared), attr_get and an evaluation hold it shared.
-struct HnswAttr : Object {
-  coltt_handle_t index = 0; uint64_t gen = 0;   // as HnswFilter
-  int type = COLTT_ATTR_I64;
-  uint32_t slots = 0;            // covered: the index's slot count at the last attr_set
-  uint64_t cap = 0, n_set = 0;   // slots allocated; slots that hold a value
-  DevBuf vals;                   // [cap] 8-byte values
-  DevBuf set;                    // [ceil(cap / 32)] u32, bit s = slot s holds a value; words past the covered slots are 0
-  std::vector<uint32_t> h_set;   // its mirror
-  ~HnswAttr() override { (void)hipSetDevice(device); }
-};
 
 // id -> live slot, as coltt_hnsw_filter_create maps it (the caller holds the index's lock); false: unknown or removed
 inline bool live_slot_of(const Hnsw* x, uint64_t id, uint32_t& s) {
@@ -3039,6 +3292,10 @@ int coltt_attr_cmp_host(int type, int op, const void* operand, const void* value
 int coltt_hnsw_filter_info(coltt_handle_t fh, coltt_handle_t* out_index, uint64_t* out_allowed, uint64_t* out_slots) {
   auto f = lookup<HnswFilter>(fh);
   if (!f) return fail(COLTT_E_NOT_FOUND, "hnsw_filter_info: unknown filter handle");
+  // coltt_hnsw_compact_carry swaps `allowed` and `slots` under the index's exclusive lock: read the pair under the shared one while the index exists
+  auto x = lookup<Hnsw>(f->index);
+  ReadLock g;
+  if (x) g = ReadLock(x->rw);
   if (out_index) *out_index = f->index;
   if (out_allowed) *out_allowed = f->allowed;
   if (out_slots) *out_slots = f->slots;

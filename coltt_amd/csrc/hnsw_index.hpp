@@ -200,6 +200,19 @@ struct HnswFilter : Object {
   }
 };
 
+// An attribute column (coltt_hnsw_attr_*; include/coltt_gpu.h, "Attribute columns and predicates").  `rw` is the column's own lock: attr_set holds
+// it exclusive (and the index's shared), attr_get and an evaluation hold it shared.
+struct HnswAttr : Object {
+  coltt_handle_t index = 0; uint64_t gen = 0;   // as HnswFilter
+  int type = COLTT_ATTR_I64;
+  uint32_t slots = 0;            // covered: the index's slot count at the last attr_set
+  uint64_t cap = 0, n_set = 0;   // slots allocated; slots that hold a value
+  DevBuf vals;                   // [cap] 8-byte values
+  DevBuf set;                    // [ceil(cap / 32)] u32, bit s = slot s holds a value; words past the covered slots are 0
+  std::vector<uint32_t> h_set;   // its mirror
+  ~HnswAttr() override { (void)hipSetDevice(device); }
+};
+
 // log2 of a table row in LDS: the centroid count rounded up to a power of two, at least 16 (codes >= C never occur)
 inline uint32_t pq_lut_shift(const Hnsw* x) { uint32_t sh = 4; while ((1u << sh) < x->pq_shape.C) sh++; return sh; }
 // the capacity of a filtered walk's allowed set R: what the re-rank may read

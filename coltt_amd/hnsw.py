@@ -132,6 +132,62 @@ def compact_map_host(del_bits, n_slots, levels):
     return new_of_old, upper_off[:live.value].copy(), live.value, up.value
 
 
+class HnswCarryStats(C.Structure):
+    """coltt_hnsw_carry_stats (include/coltt_gpu.h, "Carrying resident filters and attribute columns through a compaction")"""
+    _fields_ = [("filters", C.c_uint64), ("columns", C.c_uint64), ("bitmap_words", C.c_uint64), ("list_entries", C.c_uint64),
+                ("column_values", C.c_uint64), ("ms", C.c_float)]
+
+
+def _carry_args(bits, del_bits, n_slots):
+    n = int(n_slots)
+    b = np.ascontiguousarray(np.asarray(bits, dtype=np.uint32))
+    db = None if del_bits is None else np.ascontiguousarray(np.asarray(del_bits, dtype=np.uint32).reshape(-1))
+    if db is not None and db.size * 32 < n:
+        raise ValueError(f"carry_bits: {db.size} tombstone words for {n} slots")
+    dead = 0
+    if db is not None and n:
+        w = db[:(n + 31) // 32].copy()
+        if n & 31:
+            w[-1] &= np.uint32((1 << (n & 31)) - 1)
+        dead = int(np.unpackbits(w.view(np.uint8)).sum())
+    return n, b, db, n - dead
+
+
+def carry_bits_host(bits, del_bits, n_slots):
+    """coltt_hnsw_carry_bits_host (no device): the definition of a bitmap carried through a compaction.  bits: uint32 words over the old slots
+    (words it lacks read as 0); del_bits: the tombstones (None = none).  Returns (out_bits [ceil(live / 32)], allowed, live): bit new(s) of
+    out_bits = bit s of bits for every live slot s."""
+    n, b, db, live = _carry_args(bits, del_bits, n_slots)
+    b = b.reshape(-1)
+    out = np.zeros((live + 31) // 32, np.uint32)
+    al = C.c_uint64(0); lv = C.c_uint64(0)
+    L.check(L.lib().coltt_hnsw_carry_bits_host(L.vp(b), C.c_uint64(b.size), L.vp(db), C.c_uint64(n), L.vp(out), C.byref(al), C.byref(lv)))
+    assert lv.value == live
+    return out, al.value, lv.value
+
+
+def carry_bits_device(bits, del_bits, n_slots, with_lists=False):
+    """coltt_hnsw_carry_bits_device: the kernels of Hnsw.CompactCarry on bitmaps of the caller, no index.  bits: [n_bitmaps, n_words] uint32.
+    Returns (out_bits [n_bitmaps, ceil(live / 32)], allowed [n_bitmaps]) and with with_lists=True also a list of n_bitmaps uint32 arrays: each
+    bitmap's new slots, ascending."""
+    n, b, db, live = _carry_args(bits, del_bits, n_slots)
+    if b.ndim != 2:
+        raise ValueError("carry_bits_device: bits must be [n_bitmaps, n_words]")
+    nb, nw = b.shape
+    out = np.zeros((nb, (live + 31) // 32), np.uint32)
+    al = np.zeros(max(nb, 1), np.uint64)
+    lists = off = None
+    if with_lists:
+        off = np.arange(nb, dtype=np.uint64) * np.uint64(max(live, 1))   # no list is longer than the live count
+        lists = np.zeros(max(nb * max(live, 1), 1), np.uint32)
+    L.check(L.lib().coltt_hnsw_carry_bits_device(L.vp(b), C.c_uint64(nb), C.c_uint64(nw), L.vp(db), C.c_uint64(n), L.vp(out), L.vp(al), L.vp(lists),
+                                                 L.vp(off)))
+    al = al[:nb]
+    if with_lists:
+        return out, al, [lists[int(off[p]):int(off[p]) + int(al[p])].copy() for p in range(nb)]
+    return out, al
+
+
 class PlanFactsC(C.Structure):
     """coltt_hnsw_plan_facts (include/coltt_gpu.h): what the search plan reads of an index"""
     _fields_ = [("dim", C.c_uint32), ("metric", C.c_int32), ("quant", C.c_int32), ("m_max0", C.c_uint32), ("stride", C.c_uint64), ("slots", C.c_uint64),
@@ -403,6 +459,33 @@ class Hnsw:
         if with_map:
             return d, m[:d["slots_before"]]
         return d
+
+    def CompactCarry(self, filters=(), columns=(), stage_bytes=0, with_map=False):
+        """coltt_hnsw_compact_carry: Compact, after which the listed HnswFilter / HnswAttrColumn objects are valid at the new generation under the same
+        handles — a filter allows what it allowed among the live vertices, a column holds at every live vertex what it held; objects that are not
+        listed go stale.  Returns (stats, carry stats, allowed [len(filters)], set [len(columns)]), with with_map=True also new_of_old.  The
+        `.allowed` of the listed filter objects is refreshed."""
+        filters, columns = list(filters), list(columns)
+        fh = np.array([0 if f.h is None else f.h.value for f in filters], np.uint64)
+        ch = np.array([0 if c.h is None else c.h.value for c in columns], np.uint64)
+        al = np.zeros(max(len(filters), 1), np.uint64); ns_ = np.zeros(max(len(columns), 1), np.uint64)
+        ns = C.c_uint64(0)
+        m = None
+        if with_map:
+            L.check(L.lib().coltt_hnsw_export_raw(self.h, C.byref(ns), None, None, None, None, None, None))
+            m = np.empty(ns.value, np.uint32)
+        st = HnswCompactStats(); cs = HnswCarryStats()
+        L.check(L.lib().coltt_hnsw_compact_carry(self.h, C.c_uint64(int(stage_bytes)), L.vp(fh) if fh.size else None, C.c_size_t(fh.size), L.vp(al),
+                                                 L.vp(ch) if ch.size else None, C.c_size_t(ch.size), L.vp(ns_), L.vp(m), C.c_uint64(ns.value),
+                                                 C.byref(st), C.byref(cs)))
+        d = {k: getattr(st, k) for k, _ in HnswCompactStats._fields_}
+        c = {k: getattr(cs, k) for k, _ in HnswCarryStats._fields_}
+        al = al[:len(filters)]; ns_ = ns_[:len(columns)]
+        for f, a in zip(filters, al):
+            f.allowed = int(a)
+        if with_map:
+            return d, c, al, ns_, m[:d["slots_before"]]
+        return d, c, al, ns_
 
     # -- Hnsw.Search (hnsw.go:243-278) for a batch of queries
     def Search(self, queries, k, ef=0, with_stats=False):

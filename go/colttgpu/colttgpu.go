@@ -168,6 +168,56 @@ func HnswCompact(h Handle, stageBytes uint64) (HnswCompactStats, error) {
 	return HnswCompactStats{uint64(st.slots_before), uint64(st.slots_after), uint64(st.upper_rows_before), uint64(st.upper_rows_after),
 		uint64(st.edges_dropped), uint64(st.rows_moved), uint64(st.bytes_moved), float32(st.ms)}, err
 }
+
+// HnswCarryStats mirrors coltt_hnsw_carry_stats.
+type HnswCarryStats struct {
+	Filters, Columns uint64 // distinct objects carried
+	BitmapWords      uint64 // written for them
+	ListEntries      uint64
+	ColumnValues     uint64
+	Ms               float32 // device time of the carry launches alone
+}
+
+// HnswCompactCarry is HnswCompact after which the listed filters and attribute columns are valid at the new generation under the same
+// handles (coltt_hnsw_compact_carry): a filter allows what it allowed among the live vertices, a column holds at every live vertex what it
+// held.  Objects that are not listed go stale.  allowed[i] / set[i]: the allowed count of filters[i] / the set count of columns[i] after
+// the call.  A handle may repeat.  A bad handle fails the call before anything changes.  code is the library's status (Code* below), so
+// that a caller can tell a rejected handle (CodeNotFound, CodeInvalid: nothing changed) from a refusal that left the index as it was
+// (CodeUnsupported, CodeNoMem) and from a device failure (anything else: the index is empty and every object stale).
+func HnswCompactCarry(h Handle, stageBytes uint64, filters, columns []Handle) (st HnswCompactStats, carry HnswCarryStats, allowed, set []uint64, code int, err error) {
+	var cst C.coltt_hnsw_compact_stats
+	var ccs C.coltt_hnsw_carry_stats
+	allowed = make([]uint64, len(filters))
+	set = make([]uint64, len(columns))
+	var fp, cp *Handle
+	var ap, sp *C.uint64_t
+	if len(filters) > 0 {
+		fp = &filters[0]
+		ap = (*C.uint64_t)(unsafe.Pointer(&allowed[0]))
+	}
+	if len(columns) > 0 {
+		cp = &columns[0]
+		sp = (*C.uint64_t)(unsafe.Pointer(&set[0]))
+	}
+	err = call(func() C.int {
+		rc := C.coltt_hnsw_compact_carry(h, C.uint64_t(stageBytes), fp, C.size_t(len(filters)), ap, cp, C.size_t(len(columns)), sp, nil, 0, &cst, &ccs)
+		code = int(rc)
+		return rc
+	})
+	st = HnswCompactStats{uint64(cst.slots_before), uint64(cst.slots_after), uint64(cst.upper_rows_before), uint64(cst.upper_rows_after),
+		uint64(cst.edges_dropped), uint64(cst.rows_moved), uint64(cst.bytes_moved), float32(cst.ms)}
+	carry = HnswCarryStats{uint64(ccs.filters), uint64(ccs.columns), uint64(ccs.bitmap_words), uint64(ccs.list_entries), uint64(ccs.column_values), float32(ccs.ms)}
+	return st, carry, allowed, set, code, err
+}
+
+// The library's status codes a caller of HnswCompactCarry tells apart.
+const (
+	CodeOK          = int(C.COLTT_OK)
+	CodeInvalid     = int(C.COLTT_E_INVALID)
+	CodeNotFound    = int(C.COLTT_E_NOT_FOUND)
+	CodeUnsupported = int(C.COLTT_E_UNSUPPORTED)
+	CodeNoMem       = int(C.COLTT_E_NOMEM)
+)
 func HnswLen(h Handle) int {
 	var n C.uint64_t
 	C.coltt_hnsw_len(h, &n)

@@ -218,6 +218,30 @@ type Hnsw struct {
 	metaMu    [metaShards]sync.RWMutex
 	commitMu  sync.RWMutex // Insert / Remove hold it shared, Commit exclusive: a snapshot never interleaves with a mutation
 	err       error // creation error, surfaced by the first call (NewHnsw has no error result in the reference)
+	// the open filters and attribute columns made through this object: Compact carries them (coltt_hnsw_compact_carry)
+	carryMu sync.Mutex
+	filters map[*HnswFilter]struct{}
+	columns map[*AttrColumn]struct{}
+}
+
+// trackFilter / trackColumn register an open object with its index; Close takes it out again.
+func (xx *Hnsw) trackFilter(f *HnswFilter) *HnswFilter {
+	xx.carryMu.Lock()
+	if xx.filters == nil {
+		xx.filters = make(map[*HnswFilter]struct{})
+	}
+	xx.filters[f] = struct{}{}
+	xx.carryMu.Unlock()
+	return f
+}
+func (xx *Hnsw) trackColumn(c *AttrColumn) *AttrColumn {
+	xx.carryMu.Lock()
+	if xx.columns == nil {
+		xx.columns = make(map[*AttrColumn]struct{})
+	}
+	xx.columns[c] = struct{}{}
+	xx.carryMu.Unlock()
+	return c
 }
 
 func metric(d distance.Space) int {
@@ -388,6 +412,7 @@ type HnswFilter struct {
 	h       colttgpu.Handle
 	index   *Hnsw
 	Allowed uint64 // live vertices the filter allows
+	stale   bool   // a Load renumbered the index since: Compact does not list it
 }
 
 // NewFilter builds a filter from ids (unknown / removed ids are ignored, duplicates count once).
@@ -399,7 +424,7 @@ func (xx *Hnsw) NewFilter(ids []uint64) (*HnswFilter, error) {
 	if err != nil {
 		return nil, err
 	}
-	return &HnswFilter{h: f, index: xx, Allowed: n}, nil
+	return xx.trackFilter(&HnswFilter{h: f, index: xx, Allowed: n}), nil
 }
 
 // Handle: the library's handle of the filter (colttgpu.Batcher.SearchFiltered takes it)
@@ -411,6 +436,11 @@ func (xx *Hnsw) Handle() colttgpu.Handle { return xx.h }
 func (f *HnswFilter) Close() error {
 	if f.h == 0 {
 		return nil
+	}
+	if f.index != nil {
+		f.index.carryMu.Lock()
+		delete(f.index.filters, f)
+		f.index.carryMu.Unlock()
 	}
 	err := colttgpu.HnswFilterDestroy(f.h)
 	f.h = 0
@@ -487,7 +517,7 @@ func (xx *Hnsw) EvalFilter(expr FilterExpr, leaves ...*HnswFilter) (*HnswFilter,
 	if err != nil {
 		return nil, err
 	}
-	return &HnswFilter{h: f, index: xx, Allowed: n}, nil
+	return xx.trackFilter(&HnswFilter{h: f, index: xx, Allowed: n}), nil
 }
 
 // EvalFilters: one filter per expression over a shared leaf table in one call (coltt_hnsw_filter_eval_batch): two kernel launches and
@@ -513,7 +543,7 @@ func (xx *Hnsw) EvalFilters(exprs []FilterExpr, leaves ...*HnswFilter) ([]*HnswF
 	}
 	out := make([]*HnswFilter, len(hs))
 	for i := range hs {
-		out[i] = &HnswFilter{h: hs[i], index: xx, Allowed: ns[i]}
+		out[i] = xx.trackFilter(&HnswFilter{h: hs[i], index: xx, Allowed: ns[i]})
 	}
 	return out, nil
 }
@@ -521,12 +551,13 @@ func (xx *Hnsw) EvalFilters(exprs []FilterExpr, leaves ...*HnswFilter) ([]*HnswF
 // AttrColumn — a numeric field beside the index: one int64 (colttgpu.AttrI64) or float64 (colttgpu.AttrF64) per vertex on the device
 // (coltt_gpu.h, "Attribute columns and predicates").  NOT reference behaviour: the reference keeps a bitmap per distinct value of a field
 // and, for every operator but OpEqual, walks all of them per request (pkg/inverted/search.go:36-45).  A vertex never set — or inserted after
-// the last Set, or re-inserted by Update, which is Remove + Insert — holds no value and satisfies no comparison.  Load / Compact make the
-// column stale: build a new one by ids.  Close releases its device memory.
+// the last Set, or re-inserted by Update, which is Remove + Insert — holds no value and satisfies no comparison.  Load makes the column
+// stale: build a new one by ids.  (*Hnsw).Compact carries the open columns along.  Close releases its device memory.
 type AttrColumn struct {
 	h     colttgpu.Handle
 	index *Hnsw
 	Type  int
+	stale bool // a Load renumbered the index since: Compact does not list it
 }
 
 func (xx *Hnsw) NewAttrColumn(typ int) (*AttrColumn, error) {
@@ -537,7 +568,7 @@ func (xx *Hnsw) NewAttrColumn(typ int) (*AttrColumn, error) {
 	if err != nil {
 		return nil, err
 	}
-	return &AttrColumn{h: c, index: xx, Type: typ}, nil
+	return xx.trackColumn(&AttrColumn{h: c, index: xx, Type: typ}), nil
 }
 
 func (c *AttrColumn) Handle() colttgpu.Handle { return c.h }
@@ -562,6 +593,11 @@ func (c *AttrColumn) Get(ids []uint64) ([]uint64, []bool, error) { return colttg
 func (c *AttrColumn) Close() error {
 	if c.h == 0 {
 		return nil
+	}
+	if c.index != nil {
+		c.index.carryMu.Lock()
+		delete(c.index.columns, c)
+		c.index.carryMu.Unlock()
 	}
 	err := colttgpu.HnswAttrDestroy(c.h)
 	c.h = 0
@@ -621,7 +657,7 @@ func (xx *Hnsw) EvalFilterAttr(expr FilterExpr, leaves []*HnswFilter, preds []co
 	if err != nil {
 		return nil, err
 	}
-	return &HnswFilter{h: f, index: xx, Allowed: n}, nil
+	return xx.trackFilter(&HnswFilter{h: f, index: xx, Allowed: n}), nil
 }
 
 // Ids: the ids the filter allows, in ascending slot order (gathered on the device)
@@ -814,16 +850,63 @@ func (xx *Hnsw) Commit(w io.Writer, header bool) error {
 // Compact reclaims the device memory of removed vertices (coltt_hnsw_compact) — NOT in the reference, whose Remove frees its vertex to
 // the garbage collector.  An index that is updated in place (Core.Update = Remove + Insert) should call it now and then: answers do not
 // change, walks stop testing tombstones, later Inserts fill the freed slots.  It takes commitMu exclusive like Commit: Commit's blob table
-// is indexed by slot from HnswSlots, and the call renumbers the slots (the metadata here is keyed by id and stays as it is).  Filters
-// built before the call are stale: build them again from their ids.
+// is indexed by slot from HnswSlots, and the call renumbers the slots (the metadata here is keyed by id and stays as it is).  The open
+// filters and attribute columns made through this object (NewFilter, EvalFilter*, NewAttrColumn; not yet closed) are carried along
+// (coltt_hnsw_compact_carry): they stay valid under their handles, a filter's Allowed is refreshed.  A filter or column this object knows
+// to be stale (a Load, a failed call) is left out of the carry and stays stale.  If the library rejects a handle all the same — an object
+// made stale behind this object's back (a direct colttgpu.HnswCompact or BulkLoad on the handle), or closed between the snapshot of the
+// lists and the call — nothing has changed yet: the index is then compacted without a carry, as before this call existed, and every open
+// object is stale and marked so.  A device failure leaves the empty index and likewise marks them.
 func (xx *Hnsw) Compact() (colttgpu.HnswCompactStats, error) {
 	if xx.err != nil {
 		return colttgpu.HnswCompactStats{}, xx.err
 	}
 	xx.commitMu.Lock()
 	defer xx.commitMu.Unlock()
-	st, err := colttgpu.HnswCompact(xx.h, 0)
+	xx.carryMu.Lock()
+	fs := make([]*HnswFilter, 0, len(xx.filters))
+	fh := make([]colttgpu.Handle, 0, len(xx.filters))
+	for f := range xx.filters {
+		if f.h != 0 && !f.stale {
+			fs = append(fs, f)
+			fh = append(fh, f.h)
+		}
+	}
+	ch := make([]colttgpu.Handle, 0, len(xx.columns))
+	for c := range xx.columns {
+		if c.h != 0 && !c.stale {
+			ch = append(ch, c.h)
+		}
+	}
+	xx.carryMu.Unlock()
+	st, _, allowed, _, code, err := colttgpu.HnswCompactCarry(xx.h, 0, fh, ch)
+	switch code {
+	case colttgpu.CodeOK:
+		for i, f := range fs {
+			f.Allowed = allowed[i]
+		}
+	case colttgpu.CodeUnsupported, colttgpu.CodeNoMem: // refused, the index and the objects are as they were
+	case colttgpu.CodeNotFound, colttgpu.CodeInvalid: // a handle was rejected before anything changed: compact without a carry
+		st, err = colttgpu.HnswCompact(xx.h, 0)
+		if err != nil || st.SlotsAfter != st.SlotsBefore {
+			xx.markStale()
+		}
+	default: // a device failure: the empty index
+		xx.markStale()
+	}
 	return st, mapErr(err)
+}
+
+// markStale: the slots were renumbered without the open objects (or the index was emptied): Compact lists none of them again.
+func (xx *Hnsw) markStale() {
+	xx.carryMu.Lock()
+	for f := range xx.filters {
+		f.stale = true
+	}
+	for c := range xx.columns {
+		c.stale = true
+	}
+	xx.carryMu.Unlock()
 }
 
 // Load(r, header) — hnsw_commit.go:164-278: the stream goes straight into HBM; metadata blobs are decoded here.
@@ -833,6 +916,7 @@ func (xx *Hnsw) Load(r io.Reader, header bool) error {
 		return err
 	}
 	ids, off, ln, err := colttgpu.HnswLoad(xx.h, header, data, uint32(xx.dim))
+	xx.markStale() // the slots were renumbered (or the index emptied by a failed install): what was open is stale for good
 	if err != nil {
 		return err
 	}

@@ -417,7 +417,8 @@ int coltt_hnsw_filter_prog_check_host(const int32_t* prog, size_t n_prog, size_t
  * removed id and an unset slot give value 0, flag 0.  coltt_hnsw_attr_info (every out may be NULL): the index, the type, the slots covered
  * and the slots that hold a value (those of vertices removed since included).
  * Staleness.  A column records the index's generation as a filter does: after coltt_hnsw_load, coltt_hnsw_bulk_load or a coltt_hnsw_compact
- * that renumbered the slots it is stale and every use but info and destroy is COLTT_E_INVALID; the caller sets it again by ids.
+ * that renumbered the slots it is stale and every use but info and destroy is COLTT_E_INVALID; the caller sets it again by ids — or lists it
+ * in coltt_hnsw_compact_carry, which renumbers it with the index ("HNSW compaction" below).
  * Locking.  attr_set takes the index's lock shared and the column's own lock exclusive and returns after its device work is complete;
  * attr_get and an evaluation hold the columns they read shared, so an evaluation sees a column wholly before or wholly after a concurrent
  * attr_set.  Destroying a column an evaluation holds is safe.
@@ -440,7 +441,8 @@ int coltt_hnsw_filter_prog_check_host(const int32_t* prog, size_t n_prog, size_t
  * coltt_attr_cmp_host (no device) is the comparison itself, the function the kernel compiles: 1 or 0 for is_set && cmp(*value, *operand), or
  * COLTT_E_INVALID for an unknown type or op, a NaN operand or value of type F64, or a NULL operand / value where one is read (operand: every
  * op but SET; value: is_set != 0).
- * Not carried through coltt_hnsw_compact, Commit / Load (columns go stale, as filters do); no string columns (dictionary-encode to I64). */
+ * Not carried through Commit / Load (columns go stale, as filters do); through a compaction only by coltt_hnsw_compact_carry; no string
+ * columns (dictionary-encode to I64). */
 #define COLTT_ATTR_I64 0
 #define COLTT_ATTR_F64 1
 #define COLTT_CMP_EQ 0   /* the order of the reference's FilterOp, pkg/inverted/filter.go:24-31 */
@@ -494,7 +496,7 @@ int coltt_hnsw_reserve(coltt_handle_t h, uint64_t n_slots, uint64_t n_upper_rows
  * coltt_hnsw_insert_batch_device(ids == NULL, first_id, ...) calls keep working on it.
  * Derived state.  The neighbourhood blocks of the product-quantised walk are left stale, as coltt_hnsw_load leaves them: the next walk that reads them
  * rebuilds.  The slots are renumbered, so filters built before the call are stale (COLTT_E_INVALID), exactly as after coltt_hnsw_load: rebuild them
- * from their ids.  Slot-indexed tables of the caller (the metadata blobs of coltt_hnsw_commit) are renumbered by out_new_of_old.
+ * from their ids, or have them renumbered with the index by coltt_hnsw_compact_carry (below).  Slot-indexed tables of the caller (the metadata blobs of coltt_hnsw_commit) are renumbered by out_new_of_old.
  * No-op.  An index without tombstones is left alone: nothing is launched, filters stay valid, the stats report slots_after == slots_before and the map
  * is the identity.  An index whose vertices are all dead becomes the empty index and accepts Inserts afterwards.
  * out_new_of_old (may be NULL) receives new(s) for the slots s before the call, 0xffffffff for a tombstoned one; cap_map < the slot count with a
@@ -522,6 +524,54 @@ int coltt_hnsw_compact(coltt_handle_t h, uint64_t stage_bytes_or_0, uint32_t* ou
  * (dead = 0xffffffff), out_new_upper_off [live] indexed by NEW slot (0xffffffff for a vertex of level 0), the totals; every output may be NULL. */
 int coltt_hnsw_compact_map_host(const uint32_t* del_bits, uint64_t n_slots, const int32_t* levels, uint32_t* out_new_of_old,
                                 uint32_t* out_new_upper_off, uint64_t* out_live, uint64_t* out_upper_rows);
+/* CARRYING RESIDENT FILTERS AND ATTRIBUTE COLUMNS THROUGH A COMPACTION (coltt_hnsw_compact_carry).  coltt_hnsw_compact leaves every filter and every
+ * column stale; a column's values exist on the device only, and a hot term's filter costs a coltt_hnsw_filter_create to replay.  This call is the same
+ * compaction — the same code path, the same stats, map, refusals and failure behaviour — after which the LISTED objects are valid at the new generation
+ * under the same handles.  Objects that are not listed go stale as before.
+ * Definition (live and new() as above).  A carried filter F' covers new(F.slots) slots — the live slots that were below F's coverage — has bit new(s)
+ * = F's bit s for every live s below F.slots, allowed = |F and live|, and as its list the ascending slots of that set.  It agrees with
+ * coltt_hnsw_filter_create(h, the ids of F and live) on the compacted index in every observable but coltt_hnsw_filter_info's out_slots: the allowed count,
+ * coltt_hnsw_filter_ids, its value as a leaf of any programme, and every filtered entry point (the row walk, the walk over the quantiser's codes, EXACT,
+ * AUTO, both _batch calls): ids, score bits, counts, paths and stats.  A carried column covers new(covered) slots, holds at slot new(s) the value and
+ * the set bit slot s held, has n_set = |set and live| and keeps its type: coltt_hnsw_attr_get by id and every predicate over it answer for the live
+ * vertices as before the call.
+ * out_allowed[i] / out_set[i] (may be NULL) = the allowed count of filters[i] / the set count of columns[i] after the call.  A handle may appear more than
+ * once in a list: the object is carried once.  carry->filters / columns: the distinct objects listed.
+ * No-op and empty.  On an index without tombstones nothing is launched; the listed objects are validated all the same and stay valid.  On an index whose
+ * vertices are all dead the result is the empty index, carried filters are valid empty filters and carried columns cover 0 slots.
+ * Errors, all checked before anything changes.  An unknown handle: COLTT_E_NOT_FOUND.  An object of another index, a stale object, a NULL list with
+ * n > 0: COLTT_E_INVALID; coltt_last_error() names the list and the position.  A short map and a tombstoned entrypoint are refused as by
+ * coltt_hnsw_compact; the objects stay valid in both cases.
+ * How.  One kernel (filter_carry.hpp) packs the bits at the tombstoned slots away — per bitmap word a pext by the word's live mask, placed at the bit
+ * position the rank table names — for all carried filters and the "set" bitmaps of all carried columns in one launch; the filters' slot lists and the
+ * counts come from the list kernel of coltt_hnsw_filter_eval; a column's values move with the index's own per-slot arrays through the staging block.
+ * The carry reads what the compaction already holds on the device (tombstones, rank table, old_of_new): no id and no value crosses the bus.
+ * Failure.  Every allocation of the carry (the new bitmaps and the lists, sized by the OLD allowed counts) is made before the first kernel:
+ * COLTT_E_NOMEM leaves the index and the objects as they were.  The carried filters are written out of place into one slab per call and swapped into the
+ * objects after the stream has synchronised; a device failure leaves the empty index, as coltt_hnsw_compact does, and the listed objects stale — no
+ * filter is ever half-written.  A carried filter that was an output of a coltt_hnsw_filter_eval_batch leaves that call's shared allocations to its
+ * siblings, which go stale unless they are listed too.
+ * Locking.  Handles are looked up first, then the index's lock is taken exclusive, then every listed column's own lock exclusive (index before column: the
+ * order of coltt_hnsw_attr_set).  coltt_hnsw_filter_info reads a filter under the index's shared lock: it sees the pair (allowed, slots) of before or of
+ * after the call, never a mix.  Not carried: anything through Commit / Load / BulkLoad.  Not served: collection groups. */
+typedef struct coltt_hnsw_carry_stats {
+  uint64_t filters, columns;                             /* distinct objects carried */
+  uint64_t bitmap_words, list_entries, column_values;    /* written for them */
+  float ms;                                              /* device time of the carry launches alone */
+} coltt_hnsw_carry_stats;
+int coltt_hnsw_compact_carry(coltt_handle_t h, uint64_t stage_bytes_or_0,
+                             const coltt_handle_t* filters, size_t n_filters, uint64_t* out_allowed /*[n_filters], may be NULL*/,
+                             const coltt_handle_t* columns, size_t n_columns, uint64_t* out_set /*[n_columns], may be NULL*/,
+                             uint32_t* out_new_of_old /*[cap_map], may be NULL*/, uint64_t cap_map,
+                             coltt_hnsw_compact_stats* stats /*may be NULL*/, coltt_hnsw_carry_stats* carry /*may be NULL*/);
+/* host only, no device: the definition of a carried bitmap.  bits: n_words words over the old slots (words past it read as 0); del_bits as above (NULL =
+ * none).  out_bits [ceil(live / 32)]: bit new(s) = bit s for every live s; *out_allowed = the bits set in it; *out_live = live.  Every output may be NULL. */
+int coltt_hnsw_carry_bits_host(const uint32_t* bits, uint64_t n_words, const uint32_t* del_bits, uint64_t n_slots,
+                               uint32_t* out_bits, uint64_t* out_allowed, uint64_t* out_live);
+/* the very kernels of the carry on caller-supplied bitmaps (host pointers), no index: n_bitmaps bitmaps of n_words words each, on the default device.
+ * out_bits [n_bitmaps][ceil(live / 32)]; out_allowed [n_bitmaps]; out_lists (may be NULL): bitmap p's ascending new slots at out_lists + list_off[p]. */
+int coltt_hnsw_carry_bits_device(const uint32_t* bits, uint64_t n_bitmaps, uint64_t n_words, const uint32_t* del_bits, uint64_t n_slots,
+                                 uint32_t* out_bits, uint64_t* out_allowed /*[n_bitmaps]*/, uint32_t* out_lists /*may be NULL*/, const uint64_t* list_off);
 /* Round 4: indexes whose rows are f32 / 2-byte codes of a byte length that is a multiple of 128 (dim 128, 256, 512, 768, 1024, 1536 ...)
  * keep a second, line-transposed copy of their rows (derived data, like the adjacency-carried norms) and evaluate the level-0
  * distances of a search with EIGHT lanes per row over it — whole 128-byte lines per load instruction — in the reference's summation

@@ -201,6 +201,16 @@ class Hnsw {
     new_of_old->resize(st.slots_before);
     return st;
   }
+  // Compact, after which the listed filters and attribute columns are valid at the new generation under the same handles (coltt_gpu.h,
+  // "Carrying resident filters and attribute columns through a compaction"); what is not listed goes stale.  Defined below the two classes.
+  struct CarryResult {
+    coltt_hnsw_compact_stats stats{}; coltt_hnsw_carry_stats carry{};
+    std::vector<uint64_t> allowed, set;   // per listed filter / column, after the call
+  };
+  class Filter;
+  class AttrColumn;
+  CarryResult CompactCarry(const std::vector<Filter*>& filters, const std::vector<AttrColumn*>& columns, uint64_t stage_bytes = 0,
+                           std::vector<uint32_t>* new_of_old = nullptr);
   SearchResult Search(const Vector& query, unsigned k) const {                                                                       // hnsw.go:243
     std::vector<uint64_t> ids(k); std::vector<float> sc(k); uint32_t n = 0;
     check(coltt_hnsw_search(h_, query.data(), 1, k, 0, ids.data(), sc.data(), &n, nullptr));
@@ -253,7 +263,8 @@ class Hnsw {
     return out;
   }
   // Attribute columns (coltt_gpu.h, "Attribute columns and predicates"): one int64_t (COLTT_ATTR_I64) or double (COLTT_ATTR_F64) per slot beside
-  // the index; comparisons over them are leaves of a filter programme.  Stale after Load / BulkLoad / a Compact that renumbered: set again by ids.
+  // the index; comparisons over them are leaves of a filter programme.  Stale after Load / BulkLoad / a Compact that renumbered: set again by ids
+  // (CompactCarry keeps the listed ones valid).
   class AttrColumn {
    public:
     AttrColumn(const Hnsw& index, int type) : type_(type) { check(coltt_hnsw_attr_create(index.h_, type, &h_)); }
@@ -441,6 +452,25 @@ class Hnsw {
  private:
   coltt_handle_t h_ = 0; uint32_t dim_; int distance_ = COLTT_COSINE;
 };
+
+inline Hnsw::CarryResult Hnsw::CompactCarry(const std::vector<Filter*>& filters, const std::vector<AttrColumn*>& columns, uint64_t stage_bytes,
+                                            std::vector<uint32_t>* new_of_old) {
+  std::vector<coltt_handle_t> fh(filters.size()), ch(columns.size());
+  for (size_t i = 0; i < filters.size(); i++) fh[i] = filters[i] ? filters[i]->handle() : 0;
+  for (size_t i = 0; i < columns.size(); i++) ch[i] = columns[i] ? columns[i]->handle() : 0;
+  CarryResult r;
+  r.allowed.assign(filters.size(), 0); r.set.assign(columns.size(), 0);
+  uint64_t n = 0;
+  if (new_of_old) {
+    check(coltt_hnsw_export_raw(h_, &n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    new_of_old->resize(n);
+  }
+  check(coltt_hnsw_compact_carry(h_, stage_bytes, fh.data(), fh.size(), r.allowed.data(), ch.data(), ch.size(), r.set.data(),
+                                 new_of_old ? new_of_old->data() : nullptr, n, &r.stats, &r.carry));
+  if (new_of_old) new_of_old->resize(r.stats.slots_before);
+  for (size_t i = 0; i < filters.size(); i++) if (filters[i]) filters[i]->allowed_ = r.allowed[i];
+  return r;
+}
 
 // One collection over the GPUs of a node (BASELINE.json configs[4]): ShardVertex routing (pkg/sharding/shard.go:34-41), one FLAT
 // store or HNSW graph per device, per-member search + one RCCL all-gather (or, members sharing a device, host staging) + the
